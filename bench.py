@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- BN254 optimal-ate pairings/s (BASELINE.json metric) on N MI355X of one node.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--log2n L]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--log2n L] [--dump-outputs DIR]
 
 A "step" is one pass of the hot path (sylow_hip_pairing_batch: Miller loop + final exponentiation,
 pairing.rs:870-893) over one batch of 2^L synthetic (P_i, Q_i) pairs PER GPU, inputs and outputs
@@ -31,6 +31,9 @@ One JSON line is printed by rank 0:
  * `cpu_baseline`  the C oracle (a port of the reference) on the host cores -- the all-core loop runs inside the C library on POSIX
                    threads, with nproc / affinity / cgroup quota beside it --, the sign shape, the cargo probe, and an oracle
                    spot check of rows the TIMED launches wrote (`checked` / `mismatches`).
+
+--dump-outputs DIR writes what the last timed step of each half handed its caller (rank 0) as DIR/<name>.npy (see dump_outputs);
+the inputs are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import hashlib
@@ -119,6 +122,38 @@ def make_points(eng, n, seed):
     eng._call("sylow_hip_g2_generator_mul_batch", kb.ptr, q.ptr, qi.ptr, n)
     eng.sync()
     return p, q, ka, kb
+
+
+# ------------------------------------------------------------------------------------------------- output dump
+DUMP_PAIRING_ROWS = 1 << 15           # sampled Gt rows: 32768 x 96 float64 = 24 MiB
+DUMP_FLAG_ROWS = 1 << 20              # sampled verify flags: 2^20 x (4 + 8 index) bytes = 12 MiB
+
+
+def dump_sample(n, m, seed):
+    """Sorted indices of a fixed, seeded sample of m out of n rows (all rows when m >= n)."""
+    if m >= n:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(seed).choice(n, size=m, replace=False))
+
+
+def dump_outputs(out_dir, gt_soa, ok, all_valid):
+    """The outputs of the last timed step of each half, lossless in floats, at most 64 MB in all:
+      pairing_gt.npy           float64 (m, 96)  Gt rows of sylow_hip_pairing_batch: a row's 48 little-endian u64 limbs as 96 u32 words
+                                                (exact in float64); m = min(batch, 2^15) rows, at pairing_gt_index
+      pairing_gt_index.npy     float64 (m,)     the batch index of each dumped row (fixed seed: the same rows in every run)
+      bls_verify_ok.npy        float32 (k,)     per-element booleans of sylow_hip_bls_verify_batch, k = min(batch, 2^20), at bls_verify_ok_index
+      bls_verify_ok_index.npy  float64 (k,)
+      bls_all_valid.npy        float64 (1,)     the AND over ranks of the booleans"""
+    os.makedirs(out_dir, exist_ok=True)
+    gi = dump_sample(gt_soa.shape[1], DUMP_PAIRING_ROWS, SEED)
+    rows = np.ascontiguousarray(gt_soa[:, gi].T)                             # (m, 48) u64, AoS
+    vi = dump_sample(ok.shape[0], DUMP_FLAG_ROWS, SEED + 1)
+    arrays = {"pairing_gt": rows.view(np.uint32).astype(np.float64), "pairing_gt_index": gi.astype(np.float64),
+              "bls_verify_ok": ok[vi].astype(np.float32), "bls_verify_ok_index": vi.astype(np.float64),
+              "bls_all_valid": np.array([all_valid], dtype=np.float64)}
+    assert sum(a.nbytes for a in arrays.values()) <= 64 * 10 ** 6
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 # ------------------------------------------------------------------------------------------------- CPU leg (rank 0, N = 1)
@@ -434,7 +469,10 @@ def main():
     ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg (and the oracle spot check)")
     ap.add_argument("--plant-bad", type=int, default=-1, metavar="RANK", help="corrupt one signature on that rank (aux leg): the global AND must read 0")
     ap.add_argument("--force-dist", action="store_true", help="initialise the process group (and the native ncclComm_t) even for one rank")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs (rank 0) as DIR/<name>.npy, float32/float64, <= 64 MB")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # bare `python bench.py --gpus N`: this process has not touched the GPU (no torch import yet) and never will — it starts the
@@ -523,6 +561,7 @@ def main():
 
     elapsed, kern_ms, kern_ms_min, kern_ms_max = timed_loop(step)
     probe_p = probe_read()
+    gt_dump = gt.download() if (args.dump_outputs and rank == 0) else None     # before anything else writes gt (the stagger A/B does)
 
     # rows of what the timed launches wrote, for the oracle spot check in the CPU leg
     check = None
@@ -600,7 +639,11 @@ def main():
     v_elapsed, verify_ms, verify_ms_min, verify_ms_max = timed_loop(verify_weak)
     probe_v = probe_read()
     all_valid_weak = int(flag.item())
-    n_bad_fused = int(nv - int(ok.download().sum()))
+    ok_timed = ok.download()                   # the aux leg below reuses `ok`
+    n_bad_fused = int(nv - int(ok_timed.sum()))
+    if gt_dump is not None:
+        dump_outputs(args.dump_outputs, gt_dump, ok_timed, all_valid_weak)
+        del gt_dump
 
     # ---- untimed aux leg: the other BLS shapes, strong scaling, aggregates ----------------
     aux = {}
