@@ -76,7 +76,10 @@ int32_t sylow_hip_trim(size_t keep_bytes);
  * glued_miller_loop_batch, evm_ecpairing_batch with >= 2 pairs per job, pairing_product*, the aggregate verifiers; 19.5 KB per pair, by
  * default as many whole rounds of 2^16 jobs as fit 12 GB).  With a limit the job slices shrink to what fits (slower below one round of
  * k-slot jobs = 1.28 GB * k: the table-driven loop then runs under-filled), and a batch-wide product whose chunks no longer fit takes the
- * in-register schedule (no table at all, ~25 % more Miller-loop work).  Results are identical for every limit.  0 restores the default.
+ * in-register schedule (no table at all, ~25 % more Miller-loop work).  The limit also bounds sylow_hip_g1_msm's working set (default
+ * 1 GB): its points then go through in chunks that fit.  Below one chunk of 256 points it takes its per-point route, whose scratch
+ * (about 161 bytes per point plus the scalar multiplication's window tables) the limit does NOT bound.  Results are identical for every
+ * limit.  0 restores the default.
  * Process-wide; takes effect at the next call. */
 int32_t sylow_hip_set_scratch_limit(size_t bytes);
 /* Route selectors and thresholds (A/B measurements, crossover runs, forcing a route in a test).  Process-wide, read at every call; a value
@@ -313,6 +316,22 @@ int32_t sylow_hip_g2_double_batch(const uint64_t* a_xy, const uint8_t* a_inf, ui
 /* @shape p_xy=u64[8*n_jobs*n_terms] p_inf=u8[n_jobs*n_terms]? k=u64[4*n_jobs*n_terms] out_xy=u64[8*n_jobs] out_inf=u8[n_jobs] */
 int32_t sylow_hip_g1_lincomb_batch(const uint64_t* p_xy, const uint8_t* p_inf, const uint64_t* k, uint64_t* out_xy, uint8_t* out_inf,
                                    size_t n_jobs, size_t n_terms, void* stream);
+/* sum_i k_i * P_i as ONE G1 point (bucket method).  p_xy [8][n] affine + optional flags, k [4][n] scalars with the
+ * same contract as sylow_hip_g1_lincomb_batch (Fp values: k >= p is reduced like Fp::new, i.e. the reference's
+ * Mul<&Fp>), out [8][1] affine + out_inf [1].  n = 0 gives the identity.  Stream-ordered, no host synchronisation.
+ * Output bit-identical to sylow_hip_g1_lincomb_batch(..., n_jobs = 1, n_terms = n).  Points are taken as given (no on-curve
+ * check).  Scratch: about 80 + 7.4 W bytes per point and 232 bytes per bucket (W windows of 2^(c-1) buckets); under
+ * sylow_hip_set_scratch_limit the points go through in chunks that fit. */
+/* @shape p_xy=u64[8*n] p_inf=u8[n]? k=u64[4*n] out_xy=u64[8] out_inf=u8[1] */
+int32_t sylow_hip_g1_msm(const uint64_t* p_xy, const uint8_t* p_inf, const uint64_t* k, size_t n,
+                         uint64_t* out_xy, uint8_t* out_inf, void* stream);
+/* The same with the plan given explicitly (A/B runs, crossover measurements, forcing a route in a test); a value < 0 is the default
+ * sylow_hip_g1_msm uses.  window: the width c (4..16, else SYLOW_HIP_E_ARG) of the bucket route, default c0 = floor(log2 n) - 4 clamped
+ * to 8..16, or c0 +- 1 where that leaves the top window more bits.  min_n: the smallest n sent to the bucket route, default 2^18 = 262144 (measured); below it a scalar multiplication per point and the batch sum
+ * (0: the bucket route for every n >= 1).  The output does not depend on either. */
+/* @shape p_xy=u64[8*n] p_inf=u8[n]? k=u64[4*n] out_xy=u64[8] out_inf=u8[1] */
+int32_t sylow_hip_g1_msm_tuned(const uint64_t* p_xy, const uint8_t* p_inf, const uint64_t* k, size_t n, int32_t window, int64_t min_n,
+                               uint64_t* out_xy, uint8_t* out_inf, void* stream);
 /* Mul<&Fr> for &Gt (groups/gt.rs:161-187): out_i = gt_i "times" k_i, i.e. gt_i^k_i in Fp12, by the reference's own
  * 256-step signed-digit square-and-multiply (negative digits multiply by the conjugate).  k: Fr values, [4][n]. */
 /* @shape gt=u64[48*n] k=u64[4*n] out=u64[48*n] */

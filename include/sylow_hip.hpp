@@ -210,6 +210,21 @@ inline std::vector<G1Affine> aggregate(const std::vector<G1Affine>& p, const std
   check(sylow_hip_g1_lincomb_batch(dp.as<uint64_t>(), nullptr, dk.as<uint64_t>(), dout.as<uint64_t>(), dinf.as<uint8_t>(), n_jobs, n_terms, nullptr), "sylow_hip_g1_lincomb_batch");
   return from_device_soa<G1Affine>(dout, n_jobs);
 }
+// sum_i k[i] * P[i] as one point by the bucket method (sylow_hip_g1_msm); *infinity (if given) receives the identity flag.
+// Same point as aggregate(p, k, 1, p.size()).
+// window / min_n >= 0 pin the plan (sylow_hip_g1_msm_tuned); the point does not depend on them.
+inline G1Affine msm(const std::vector<G1Affine>& p, const std::vector<Fp>& k, bool* infinity = nullptr, int32_t window = -1, int64_t min_n = -1) {
+  if (k.size() != p.size()) throw Error("msm: shape mismatch");
+  auto dp = to_device_soa(p); auto dk = to_device_soa(k);
+  DeviceBuffer dout(sizeof(G1Affine) + 8), dinf(8);
+  check(sylow_hip_g1_msm_tuned(dp.as<uint64_t>(), nullptr, dk.as<uint64_t>(), p.size(), window, min_n, dout.as<uint64_t>(), dinf.as<uint8_t>(), nullptr),
+        "sylow_hip_g1_msm_tuned");
+  uint8_t flag = 0;
+  check(sylow_hip_memcpy_d2h(&flag, dinf.as<void>(), 1, nullptr), "d2h");
+  const G1Affine r = from_device_soa<G1Affine>(dout, 1)[0];       // synchronises the stream
+  if (infinity) *infinity = flag != 0;
+  return r;
+}
 struct Messages {                                    // concatenated bytes + offsets on the device
   DeviceBuffer bytes, offsets; size_t n;
   explicit Messages(const std::vector<std::vector<uint8_t>>& msgs) : bytes(total(msgs) + 8), offsets((msgs.size() + 1) * 8), n(msgs.size()) {

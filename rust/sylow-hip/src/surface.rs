@@ -496,6 +496,34 @@ pub fn lincomb(dev: &Device, points: &[G1Affine], weights: &[Fr], n_jobs: usize,
     })?;
     download_g1(dev, &out)
 }
+/// sum_i scalars[i] * points[i] as one point by the bucket method (`sylow_hip_g1_msm`); the same point as
+/// `lincomb(dev, points, scalars, 1, points.len())`.
+pub fn msm(dev: &Device, points: &[G1Affine], scalars: &[Fr]) -> Result<G1Projective, HipError> {
+    assert!(scalars.len() == points.len());
+    let n = points.len();
+    let dp = upload_g1(dev, points)?;
+    let dk = dev.upload_soa::<4>(&fr_words(scalars))?;
+    let out = DeviceG1 { xy: dev.alloc::<u64>(8)?, inf: dev.alloc::<u8>(1)?, n: 1 };
+    // SAFETY: n points and scalars (possibly empty), one output point.
+    device::check(unsafe {
+        ffi::sylow_hip_g1_msm(dp.xy.as_ptr(), dp.inf.as_ptr(), dk.as_ptr(), n, out.xy.as_mut_ptr(), out.inf.as_mut_ptr(), dev.stream)
+    })?;
+    Ok(download_g1(dev, &out)?.remove(0))
+}
+/// `msm` with the plan pinned (`sylow_hip_g1_msm_tuned`): window width 4..16 and the smallest n on the bucket route; < 0 = the
+/// defaults.  The point does not depend on either.
+pub fn msm_tuned(dev: &Device, points: &[G1Affine], scalars: &[Fr], window: i32, min_n: i64) -> Result<G1Projective, HipError> {
+    assert!(scalars.len() == points.len());
+    let n = points.len();
+    let dp = upload_g1(dev, points)?;
+    let dk = dev.upload_soa::<4>(&fr_words(scalars))?;
+    let out = DeviceG1 { xy: dev.alloc::<u64>(8)?, inf: dev.alloc::<u8>(1)?, n: 1 };
+    // SAFETY: n points and scalars (possibly empty), one output point.
+    device::check(unsafe {
+        ffi::sylow_hip_g1_msm_tuned(dp.xy.as_ptr(), dp.inf.as_ptr(), dk.as_ptr(), n, window, min_n, out.xy.as_mut_ptr(), out.inf.as_mut_ptr(), dev.stream)
+    })?;
+    Ok(download_g1(dev, &out)?.remove(0))
+}
 /// `Mul<Fr> for Gt` (gt.rs:188-215): gt[i] ^ k[i], the reference's own 256-step signed-digit algorithm.
 pub fn gt_pow_batch(dev: &Device, gt: &[[u64; 48]], k: &[Fr]) -> Result<Vec<GtOut>, HipError> {
     assert_eq!(gt.len(), k.len());

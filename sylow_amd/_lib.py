@@ -142,6 +142,8 @@ SIGNATURES = {
     "sylow_hip_clock_probe": [c_u64p],
     "sylow_hip_wall_clock_khz": [ctypes.POINTER(c_i32)],
     "sylow_hip_g1_sum_batch": [c_u64p, c_u8p, c_sz, c_u64p, c_u8p, c_vp],
+    "sylow_hip_g1_msm": [c_u64p, c_u8p, c_u64p, c_sz, c_u64p, c_u8p, c_vp],
+    "sylow_hip_g1_msm_tuned": [c_u64p, c_u8p, c_u64p, c_sz, c_i32, ctypes.c_int64, c_u64p, c_u8p, c_vp],
     "sylow_hip_pairing_host": [c_u64p, c_u8p, c_u64p, c_u8p, c_u64p, c_sz, c_sz],
     "sylow_hip_bls_verify_host": [c_u64p, c_u8p, c_u8p, c_u64p, c_u64p, c_u8p, c_u8p, c_sz, c_sz],
     "sylow_hip_pairing_host_bytes": [c_u8p, c_u8p, c_u64p, c_u8p, c_u8p, c_sz, c_sz],

@@ -368,6 +368,17 @@ def aggregate(points: "G1Affine", weights: "Fr", n_jobs: int, n_terms: int) -> "
     return G1Affine(xy, inf)
 
 
+def msm(points: "G1Affine", scalars) -> "G1Affine":
+    """sum_i scalars[i] * points[i] as one point (bucket method on the GPU): KZG-style commitments, random linear combinations,
+    weighted aggregation over a whole batch.  scalars: Fr, or [n, 4] Fp words (values >= p are reduced like Fp::new).  Same
+    point as aggregate(points, scalars, 1, n)."""
+    v = scalars.v if isinstance(scalars, Fr) else np.ascontiguousarray(scalars, dtype=np.uint64).reshape(-1, 4)
+    if len(points) != v.shape[0]:
+        raise ValueError(f"msm: {len(points)} points but {v.shape[0]} scalars")
+    xy, inf = engine().g1_msm(points.xy, v, points.infinity)
+    return G1Affine(xy, inf)
+
+
 class G2PreComputed:
     """G2Affine::precompute() (pairing.rs:556,676-708): q plus the 87 line-coefficient triples, [n, 87*24] words."""
 

@@ -166,7 +166,8 @@ class Engine:
         return mhz, clk, waves, (int(w[:, 3].max()) / khz if khz else None)
 
     def set_scratch_limit(self, nbytes: int = 0):
-        """Upper bound for the multi-pair routes' line tables (sylow_hip_set_scratch_limit; 0 = the default of 12 GB).  Process-wide."""
+        """Upper bound for the multi-pair routes' line tables and g1_msm's working set (sylow_hip_set_scratch_limit; 0 = the defaults of
+        12 GB and 1 GB).  Process-wide."""
         _lib.check(self.lib.sylow_hip_set_scratch_limit(nbytes), "sylow_hip_set_scratch_limit")
 
     def shutdown(self):
@@ -459,6 +460,23 @@ class Engine:
         dpi = self._flags(p_inf, n) if n else None
         do, doi = self.empty((8, 1)), self.empty((1,), np.uint8)
         self._call("sylow_hip_g1_sum_batch", self._ptr(dp), self._ptr(dpi), n, do.ptr, doi.ptr)
+        return self.from_device_soa(do), doi.download()
+
+    def g1_msm(self, p_xy, k, p_inf=None, window=-1, min_n=-1):
+        """sum_i k_i * P_i as one G1 point by the bucket method (sylow_hip_g1_msm): ([1, 8] affine words, [1] flag), bit-identical to
+        g1_lincomb(p_xy, k, 1, n).  k: [n, 4] Fp / Fr words (k >= p is reduced like Fp::new).  window / min_n >= 0 pin the plan
+        (sylow_hip_g1_msm_tuned: window width 4..16, smallest n on the bucket route); < 0 = the defaults."""
+        p_xy, k = _aos(p_xy, 8), _aos(k, 4)
+        n = p_xy.shape[0]
+        assert k.shape[0] == n
+        dp = self.to_device_soa(p_xy, 8) if n else None
+        dk = self.to_device_soa(k, 4) if n else None
+        dpi = self._flags(p_inf, n) if n else None
+        do, doi = self.empty((8, 1)), self.empty((1,), np.uint8)
+        if window < 0 and min_n < 0:
+            self._call("sylow_hip_g1_msm", self._ptr(dp), self._ptr(dpi), self._ptr(dk), n, do.ptr, doi.ptr)
+        else:
+            self._call("sylow_hip_g1_msm_tuned", self._ptr(dp), self._ptr(dpi), self._ptr(dk), n, int(window), int(min_n), do.ptr, doi.ptr)
         return self.from_device_soa(do), doi.download()
 
     def pairing(self, p_xy, q_xy, p_inf=None, q_inf=None, pipelined=True, chunk=0, out=None):
