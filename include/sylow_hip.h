@@ -250,6 +250,15 @@ int32_t sylow_hip_fp12_sparse_mul_batch(const uint64_t* f, const uint64_t* ell, 
  * op 0: round trip; 1: a*b; 2: 2ab via the fused two-product pass; 3: 2a(b-a) through lazy add/sub + normalise */
 /* @shape a=u64[*] b=u64[*]? out=u64[*] */
 int32_t sylow_hip_f29_hook_batch(int32_t op, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n, void* stream);
+/* test hook for the same core on RAW limbs: operands are [9][n] int32 limb planes, applied exactly as given (no conversion).
+ * op 0: norm(a); 1: norm_x8(a); 2: norm_sub3(a, b); 3: mul(a, b) inlined; 4: mul(a, b) through the out-of-line leaf; 5: sqr(a);
+ * 6: dot2(a, b, c, d); 7: dot2_ilp(a, b, c, d); 8: reduce_from(limb(i) = k0 a[i] + k1 b[i]); 9: reduce_terms(a, b; k0, k1);
+ * 10: reduce_terms(a, b, c, d; four 16-bit coefficients, k0 = k[0] | k[1] << 16, k1 = k[2] | k[3] << 16); 11: norm_terms(a, b; k0, k1);
+ * 12: norm_terms as op 10; 13: u2_xi_lin(x = (a, b), k0, y = (c, d), k1), out [18][n]; 14: to_fp(a), out = 8 u32 words and a zero
+ * word; 15: from_fp(a[0..7] as u32 words).  Out [9][n] except op 13. */
+/* @shape a=i32[9*n] b=i32[9*n]? c=i32[9*n]? d=i32[9*n]? out=i32[*] */
+int32_t sylow_hip_f29_raw_hook_batch(int32_t op, const int32_t* a, const int32_t* b, const int32_t* c, const int32_t* d, int32_t k0,
+                                     int32_t k1, int32_t* out, size_t n, void* stream);
 
 /* ---- groups: src/groups/group.rs, g1.rs, g2.rs ----------------------------------------------- */
 /* Mul<&Fp> for &G1Projective / &G2Projective (group.rs:639-667): out_i = k_i * P_i.

@@ -267,6 +267,29 @@ pub fn f29_hook_batch(dev: &Device, op: i32, a: &[[u64; 4]], b: &[[u64; 4]]) -> 
     device::check(unsafe { ffi::sylow_hip_f29_hook_batch(op, da.as_ptr(), db.as_ptr(), out.as_mut_ptr(), n, dev.stream) })?;
     Ok(dev.download_aos::<4>(&out, n)?)
 }
+/// Raw-limb test hook of the carry-free core: operands and output are `[i32; 9]` limb vectors, passed through unconverted (op codes in
+/// include/sylow_hip.h; op 13 returns 18 limbs per element, the other ops 9).
+pub fn f29_raw_hook_batch(dev: &Device, op: i32, ops: [Option<&[[i32; 9]]>; 4], k0: i32, k1: i32) -> Result<Vec<Vec<i32>>, HipError> {
+    let n = ops[0].expect("operand a").len();
+    let soa = |x: &[[i32; 9]]| -> Vec<i32> {
+        assert_eq!(x.len(), n);
+        (0..9).flat_map(|k| x.iter().map(move |e| e[k])).collect()
+    };
+    let mut bufs = Vec::new();
+    for x in ops.iter() {
+        bufs.push(match x {
+            Some(x) => Some(dev.upload::<i32>(&soa(x))?),
+            None => None,
+        });
+    }
+    let w = if op == 13 { 18 } else { 9 };
+    let out = dev.alloc::<i32>(w * n)?;
+    let p = |i: usize| bufs[i].as_ref().map_or(ptr::null(), |d| d.as_ptr());
+    // SAFETY: every operand present is 9 * n limbs, the output w * n (the width op 13 writes).
+    device::check(unsafe { ffi::sylow_hip_f29_raw_hook_batch(op, p(0), p(1), p(2), p(3), k0, k1, out.as_mut_ptr(), n, dev.stream) })?;
+    let flat = dev.download(&out)?;
+    Ok((0..n).map(|i| (0..w).map(|k| flat[k * n + i]).collect()).collect())
+}
 pub fn fp12_hook_batch(dev: &Device, op: i32, a: &[[u64; 48]], b: Option<&[[u64; 48]]>) -> Result<Vec<[u64; 48]>, HipError> {
     let n = a.len();
     let da = dev.upload_soa::<48>(a)?;

@@ -277,8 +277,9 @@ BN_DEV Fp f29_to_fp(const F29& a) {
 // stored results go through one pass that subtracts q p with q = round(value / p) estimated from the top limb and
 // propagates carries at the same time: r normalised, |value(r)| < 0.51 p.
 // `limb(i)` returns limb i of the lazy combination as int64; requirements: |limb(i)| < 2^36 for i < 8 and
-// |limb(8)| < 2^31.  Estimate accuracy: value / 2^232 = limb(8) + eps with |eps| < 2^8, p / 2^232 = 3171406.4,
-// K = floor(2^44 / 3171406): |value - q p| < p/2 + (2^8 + 1) 2^232 + 2^-13 p < 0.51 p.
+// |limb(8)| < 2^31.  Estimate accuracy: value / 2^232 = limb(8) + eps with |eps| < 2^8, p / 2^232 = 3171406.4;
+// K = 5547168 is 43.6 above 2^44 / 3171406.4, so q = round(limb(8) K / 2^44) is off by |limb(8)| 2.5e-12 < 0.006 at most:
+// |value - q p| < p/2 + 2^8 2^232 + 0.006 p < 0.51 p.  (The callers' combined top limbs: tests/test_f29_model.py, CALL_SITES.)
 template <class LIMB>
 BN_DEV F29 f29_reduce_from(LIMB limb) {
   i32 p[9]; f29_p(p);
@@ -594,7 +595,8 @@ BN_DEV F29 f29_lin2(const F29& a, int ka, const F29& b, int kb) {
   return f29_reduce_terms(x, k);
 }
 BN_DEV U2 u2_lin2(const U2& a, int ka, const U2& b, int kb) { return U2{f29_lin2(a.c0, ka, b.c0, kb), f29_lin2(a.c1, ka, b.c1, kb)}; }
-// r = reduce(k * xi * x + m * y),  xi = 9 + u:  (9 x0 - x1, x0 + 9 x1).   |x limbs|, |y limbs| < 2^31
+// r = reduce(k * xi * x + m * y),  xi = 9 + u:  (9 x0 - x1, x0 + 9 x1).   |x limbs|, |y limbs| < 2^31 for limbs 0..7 with
+// 10 |k| + |m| <= 32; the top limbs must keep the combined one inside the reduce pass's 2^31: 10 |k| |x[8]| + |m| |y[8]| < 2^31
 BN_DEV U2 u2_xi_lin(const U2& x, int k, const U2& y, int m) {
   return U2{f29_reduce_from([&](int i) { return ((i64)x.c0.v[i] * 9 - x.c1.v[i]) * k + (i64)y.c0.v[i] * m; }),
             f29_reduce_from([&](int i) { return ((i64)x.c0.v[i] + (i64)x.c1.v[i] * 9) * k + (i64)y.c1.v[i] * m; })};

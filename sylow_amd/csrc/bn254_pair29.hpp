@@ -504,7 +504,7 @@ BN_DEV W2 w2_twist_b() {
 // (27 - 3 u) c.  NOT used where the raw Miller value is the result (miller_loop_batch, glued_miller_loop_batch, the line tables).
 BN_DEV F29 f29_iso_s2() { return F29{{0x05beeef0, 0x1f76bf90, 0x1d5e46cf, 0x17f6764e, 0x1df385e5, 0x0d7a8334, 0x152215eb, 0x01b6eac1, -290196}}; }   // s^2 2^261 mod p, balanced
 BN_DEV F29 f29_iso_s3() { return F29{{0x1af1f8a3, 0x00cd9858, 0x1dce6a34, 0x142e620a, 0x1bc0c667, 0x0ae94d20, 0x0db9310b, 0x12572b72, 0x000405e6}}; }   // s^3
-BN_DEV W2 w2_mul_27m3u(const W2& a) {                                    // (a0 + a1 u)(27 - 3 u) = (27 a0 + 3 a1) + (27 a1 - 3 a0) u, R-class; any 32-bit limbs
+BN_DEV W2 w2_mul_27m3u(const W2& a) {                                    // (a0 + a1 u)(27 - 3 u) = (27 a0 + 3 a1) + (27 a1 - 3 a0) u, R-class; any 32-bit low limbs, |top limb| < 2^31 / 30
   const F29 ao = xchg9(a.c);
   const F29* const t[2] = {&a.c, &ao};
   const i32 c[2] = {bn_keep(27), bn_keep_v(lane_odd() ? -3 : 3)};

@@ -130,6 +130,67 @@ __global__ void __launch_bounds__(BLOCK) k_f29_hook(int op, const u64* a, const 
   store_fp(out, n, i, 0, r);
 }
 
+// test hook for the carry-free core on RAW limbs (no conversion on the way in or out): one routine of bn254_f29.hpp per op, applied to
+// the 9 x int32 SoA operands exactly as given, so that tests/test_gpu_f29_bounds.py can drive the routines at the bounds they state
+// and compare every output word with tools/f29_model.py.  k0 / k1: coefficients; ops 10 and 12 take four, two signed 16-bit halves
+// each (k0 = k[0] | k[1] << 16, k1 = k[2] | k[3] << 16).  Output [9][n]; op 13 [18][n]; op 14 the 8 u32 words and a zero word.
+BN_DEV F29 load_f29(const int32_t* p, size_t n, size_t i) {
+  F29 r;
+#pragma unroll
+  for (int k = 0; k < 9; ++k) r.v[k] = p ? p[(size_t)k * n + i] : 0;
+  return r;
+}
+BN_DEV void store_f29(int32_t* p, size_t n, size_t i, int w0, const F29& a) {
+#pragma unroll
+  for (int k = 0; k < 9; ++k) p[(size_t)(w0 + k) * n + i] = a.v[k];
+}
+__global__ void __launch_bounds__(BLOCK) k_f29_raw_hook(int op, const int32_t* pa, const int32_t* pb, const int32_t* pc, const int32_t* pd,
+                                                        int32_t k0, int32_t k1, int32_t* out, size_t n) {
+  size_t i = TID;
+  if (i >= n) return;
+  const F29 a = load_f29(pa, n, i), b = load_f29(pb, n, i), c = load_f29(pc, n, i), d = load_f29(pd, n, i);
+  const i32 q[4] = {(i32)(int16_t)(k0 & 0xffff), k0 >> 16, (i32)(int16_t)(k1 & 0xffff), k1 >> 16};
+  F29 r;
+  if (op == 0) r = f29_norm(a);
+  else if (op == 1) r = f29_norm_x8(a);
+  else if (op == 2) r = f29_norm_sub3(a, b);
+  else if (op == 3) r = f29_mul(a, b);
+  else if (op == 4) r = f29_mul_leaf(W_ARGS(a), W_ARGS(b));
+  else if (op == 5) r = f29_sqr(a);
+  else if (op == 6) r = f29_dot2(a, b, c, d);
+  else if (op == 7) r = f29_dot2_ilp(a, b, c, d);
+  else if (op == 8) r = f29_reduce_from([&](int k) { return (i64)a.v[k] * k0 + (i64)b.v[k] * k1; });
+  else if (op == 9) r = f29_lin2(a, k0, b, k1);
+  else if (op == 10) {
+    const F29* const x[4] = {&a, &b, &c, &d};
+    const i32 k[4] = {bn_keep(q[0]), bn_keep(q[1]), bn_keep(q[2]), bn_keep(q[3])};
+    r = f29_reduce_terms(x, k);
+  } else if (op == 11) {
+    const F29* const x[2] = {&a, &b};
+    const i32 k[2] = {bn_keep(k0), bn_keep(k1)};
+    r = f29_norm_terms(x, k);
+  } else if (op == 12) {
+    const F29* const x[4] = {&a, &b, &c, &d};
+    const i32 k[4] = {bn_keep(q[0]), bn_keep(q[1]), bn_keep(q[2]), bn_keep(q[3])};
+    r = f29_norm_terms(x, k);
+  } else if (op == 13) {
+    const U2 u = u2_xi_lin(U2{a, b}, k0, U2{c, d}, k1);
+    store_f29(out, n, i, 9, u.c1);
+    r = u.c0;
+  } else if (op == 14) {
+    const Fp f = f29_to_fp(a);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) r.v[k] = (i32)f.v[k];
+    r.v[8] = 0;
+  } else {
+    Fp f;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) f.v[k] = (u32)a.v[k];
+    r = f29_from_fp(f);
+  }
+  store_f29(out, n, i, 0, r);
+}
+
 // ------------------------------------------------------------------ layout helpers --------------
 __global__ void __launch_bounds__(BLOCK) k_aos_to_soa(const u64* __restrict__ aos, u64* __restrict__ soa, size_t words, size_t n) {
   size_t t = TID;
@@ -569,6 +630,14 @@ int32_t sylow_hip_host_xoshiro_fp(uint64_t seed, uint64_t* out_host, size_t n, s
 int32_t sylow_hip_f29_hook_batch(int32_t op, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n, void* stream) {
   ARGCHK(a && b && out); if (!n) return SYLOW_HIP_OK;
   k_f29_hook<<<GRID(n)>>>(op, a, b, out, n); LAUNCHED();
+}
+
+// test hook (see k_f29_raw_hook): operands the op does not take may be NULL; ops 10 - 12 read a NULL operand as zero
+int32_t sylow_hip_f29_raw_hook_batch(int32_t op, const int32_t* a, const int32_t* b, const int32_t* c, const int32_t* d, int32_t k0,
+                                     int32_t k1, int32_t* out, size_t n, void* stream) {
+  const bool two = op == 2 || op == 3 || op == 4 || op == 6 || op == 7 || op == 13, four = op == 6 || op == 7 || op == 13;
+  ARGCHK(a && out && op >= 0 && op <= 15 && (b || !two) && ((c && d) || !four)); if (!n) return SYLOW_HIP_OK;
+  k_f29_raw_hook<<<GRID(n)>>>(op, a, b, c, d, k0, k1, out, n); LAUNCHED();
 }
 
 int32_t sylow_hip_flags_all(const uint8_t* flags, size_t n, int32_t* out_dev, void* stream) {

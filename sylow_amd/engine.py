@@ -250,6 +250,23 @@ class Engine:
         self._call("sylow_hip_f29_hook_batch", int(op), da.ptr, db.ptr, do.ptr, n)
         return self.from_device_soa(do)
 
+    def f29_raw(self, op, a, b=None, c=None, d=None, k0=0, k1=0):
+        """sylow_hip_f29_raw_hook_batch: operands are (n, 9) int32 limb arrays (None = absent); returns (n, 9) int32, (n, 18) for op 13"""
+        a = np.ascontiguousarray(a, dtype=np.int32).reshape(-1, 9)
+        n = a.shape[0]
+
+        def soa(x):
+            if x is None:
+                return None
+            x = np.ascontiguousarray(x, dtype=np.int32).reshape(-1, 9)
+            assert x.shape[0] == n, (x.shape, n)
+            return self.to_device(np.ascontiguousarray(x.T))
+        da, db, dc, dd = soa(a), soa(b), soa(c), soa(d)
+        w = 18 if op == 13 else 9
+        do = self.empty((w, n), np.int32)
+        self._call("sylow_hip_f29_raw_hook_batch", int(op), da.ptr, self._ptr(db), self._ptr(dc), self._ptr(dd), int(k0), int(k1), do.ptr, n)
+        return np.ascontiguousarray(do.download().T)
+
     def fp12_hook(self, op, a, b=None):
         a = _aos(a, 48)
         n = a.shape[0]

@@ -111,6 +111,31 @@ def test_f29_core_vs_saturated_core(engine):
     # inversion: Bernstein-Yang safegcd (op 4) and the Fermat chain (op 5) agree with each other and with pow(x, p-2, p); inv(0) = 0
     inv = [pow(x, P - 2, P) for x in va]
     assert ints(engine.f29_hook(4, a, b)) == inv and ints(engine.f29_hook(5, a, b)) == inv
+    # ops 0 - 3 and 6 step by step through the exact host model (tools/f29_model.py): the same routines on the same limbs, with every
+    # i32 / i64 value checked for wrap-around, then the device's conversions out of Montgomery form
+    model = f29_model_hook(va, vb)
+    for op in (0, 1, 2, 3, 6):
+        assert ints(engine.f29_hook(op, a, b)) == model[op], op
+
+
+def f29_model_hook(va, vb):
+    """k_f29_hook's ops 0 - 3 and 6 on tools/f29_model.py: load_fp (x R mod p), f29_from_fp, the op, f29_to_fp, store_fp (/ R)"""
+    import os
+    import sys
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
+    import f29_model as M
+    rinv = pow(1 << 256, -1, P)
+    out = {0: [], 1: [], 2: [], 3: [], 6: []}
+    lazy = lambda f, x, y: [M.i32(f(s, t)) for s, t in zip(x, y)]
+    add, sub = (lambda s, t: s + t), (lambda s, t: s - t)
+    for x, y in zip(va, vb):
+        fx = M.from_fp(M.int_to_words((x << 256) % P))
+        fy = M.from_fp(M.int_to_words((y << 256) % P))
+        t = M.norm(lazy(sub, lazy(add, lazy(add, fx, fy), fx), fy))
+        res = {0: fx, 1: M.mul(fx, fy), 2: M.dot2(fx, fy, fy, fx), 3: M.mul(t, lazy(sub, fy, fx)), 6: M.sqr(M.reduce_from(fx))}
+        for op, r in res.items():
+            out[op].append(M.words_value(M.to_fp(r)) * rinv % P)
+    return out
 
 
 def test_f29_tower_vs_saturated_tower(engine, coracle):

@@ -49,6 +49,7 @@ del S["fp12_residue_mul_batch"]
 S["fp12_cyclotomic_sqr_batch"] = field("fp12", "a out".split())
 S["fp12_sparse_mul_batch"] = "f=u64[48*n] ell=u64[24*n] out=u64[48*n]"
 S["f29_hook_batch"] = "a=u64[*] b=u64[*]? out=u64[*]"
+S["f29_raw_hook_batch"] = "a=i32[9*n] b=i32[9*n]? c=i32[9*n]? d=i32[9*n]? out=i32[*]"
 S["fp12_hook_batch"] = "a=u64[48*n] b=u64[*]? out=u64[48*n]"
 S["aos_to_soa"] = "aos=u64[words*n] soa=u64[words*n]"
 S["soa_to_aos"] = "soa=u64[words*n] aos=u64[words*n]"
