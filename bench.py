@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- BN254 optimal-ate pairings/s (BASELINE.json metric) on N MI355X of one node.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--log2n L] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--log2n L] [--dump-outputs DIR] [--full [--no-aux] [--no-cpu]]
 
 A "step" is one pass of the hot path (sylow_hip_pairing_batch: Miller loop + final exponentiation,
 pairing.rs:870-893) over one batch of 2^L synthetic (P_i, Q_i) pairs PER GPU, inputs and outputs
@@ -14,21 +14,24 @@ The metric has two halves and BOTH run through the same loop (W warm-up steps, t
 HIP events around every step on the launch stream): K steps of 2^L pairings (`value`, `ms_per_step`), then K steps of 2^L BLS
 verifications incl. the AND over ranks (`config.bls_verifies_per_s`, `config.bls_verify_ms_per_step`; lib.rs:223-236).
 
+A plain run does only what the headline needs: set-up, the two halves' warm-up and timed steps, the dump, the line.  `--full` adds
+everything else the line can carry: the `aux` leg and the `cpu_baseline` leg (`--no-aux` / `--no-cpu` drop one of them again).
+
 One JSON line is printed by rank 0:
  * `roofline`      the roof that BINDS the dominant kernel, plk::k_pairing: VALU issue (cycle-weighted by instruction class) --
                    `achieved` = ideal issue cycles of one launch / its live HIP-event duration, `peak` = 1024 SIMDs x 2.4 GHz,
                    `frac_clock_free` = the same ratio taken inside one rocprofv3 pass (no clock enters); LIVE in every run (round 6):
                    `sustained_mhz` = the engine clock the K timed launches held (every wavefront adds its s_memtime / s_memrealtime
                    deltas: sylow_hip_clock_probe), `simd_cycles_per_pairing_live` and `frac_at_sustained_clock` from it, and
-                   `stagger_gain_*` = plain / skewed launch times of an A/B run through the ABI option; the contract's HBM pricing
+                   `stagger_gain_*` = plain / skewed launch times of an A/B run through the ABI option (an aux figure: null without that leg); the contract's HBM pricing
                    (576 algorithmic bytes per pairing: ~2x10^4 field multiplications on 576 bytes, tiny by nature) stays beside it as
                    `hbm_*`, `traffic` = HBM bytes per launch from the PMC counters; the verify kernel's figures are `verify_*`;
                    the driver's record keeps a prefix of this object's keys, so what certifies the line comes first;
- * `aux`           the other BLS shapes at batch 2^20 (two-pairing form, same signer, aggregates, strong scaling), the batch-size sweep,
+ * `aux`           (--full) the other BLS shapes at batch 2^20 (two-pairing form, same signer, aggregates, strong scaling), the batch-size sweep,
                    the end-to-end (host arrays in, host results out) pipeline, and at N = 1 the other single-GPU
                    configs (C2a Fp mul/add -- the HBM-bound kernels --, C2b G1 scalar-mul, C3 2^18 pairings, C5 byte-level
                    ecPairing) each with its own algorithmic GB/s and fraction of the HBM roof;
- * `cpu_baseline`  the C oracle (a port of the reference) on the host cores -- the all-core loop runs inside the C library on POSIX
+ * `cpu_baseline`  (--full, N = 1) the C oracle (a port of the reference) on the host cores -- the all-core loop runs inside the C library on POSIX
                    threads, with nproc / affinity / cgroup quota beside it --, the sign shape, the cargo probe, and an oracle
                    spot check of rows the TIMED launches wrote (`checked` / `mismatches`).
 
@@ -465,14 +468,16 @@ def main():
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--log2n", type=int, default=20, help="pairings per GPU per step = 2^L")
-    ap.add_argument("--no-aux", action="store_true", help="skip the untimed BLS-verify / other-config aux leg")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg (and the oracle spot check)")
+    ap.add_argument("--full", action="store_true", help="also run the untimed aux leg and the CPU baseline leg (off: only what the headline needs)")
+    ap.add_argument("--no-aux", action="store_true", help="with --full: skip the untimed BLS-verify / other-config aux leg")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline leg (and the oracle spot check)")
     ap.add_argument("--plant-bad", type=int, default=-1, metavar="RANK", help="corrupt one signature on that rank (aux leg): the global AND must read 0")
     ap.add_argument("--force-dist", action="store_true", help="initialise the process group (and the native ncclComm_t) even for one rank")
     ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs (rank 0) as DIR/<name>.npy, float32/float64, <= 64 MB")
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    run_aux, run_cpu = args.full and not args.no_aux, args.full and not args.no_cpu
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # bare `python bench.py --gpus N`: this process has not touched the GPU (no torch import yet) and never will — it starts the
@@ -565,7 +570,7 @@ def main():
 
     # rows of what the timed launches wrote, for the oracle spot check in the CPU leg
     check = None
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if rank == 0 and world == 1 and run_cpu:
         idx = np.sort(np.random.default_rng(SEED).choice(n, size=min(16, n), replace=False))
         check = tuple(np.ascontiguousarray(d.download()[:, idx].T) for d in (p, q, gt))
 
@@ -612,7 +617,11 @@ def main():
     sig, sigi = eng.empty((8, nv)), eng.empty((nv,), np.uint8)
     ok = eng.empty((nv,), np.uint8)
     eng._call("sylow_hip_g2_scalar_mul_subgroup_batch", g2.ptr, None, sk.ptr, pk.ptr, pki.ptr, nv)
-    dtsg, sign_ms = timed_ranks(lambda: eng._call("sylow_hip_bls_sign_batch", sk.ptr, dm.ptr, doff.ptr, sig.ptr, sigi.ptr, nv), 3, "bls_sign")
+    sign = lambda: eng._call("sylow_hip_bls_sign_batch", sk.ptr, dm.ptr, doff.ptr, sig.ptr, sigi.ptr, nv)
+    if run_aux:                               # the sign rate is an aux figure; the verify loop needs the signatures only
+        dtsg, sign_ms = timed_ranks(sign, 3, "bls_sign")
+    else:
+        sign()
     if args.plant_bad == rank:                # sig_j <- sig_{j+1}: a valid point, the wrong signature
         s_h = sig.download()
         j = (nv // world) // 3               # inside this rank's block of the strong-scaling leg too
@@ -647,7 +656,7 @@ def main():
 
     # ---- untimed aux leg: the other BLS shapes, strong scaling, aggregates ----------------
     aux = {}
-    if not args.no_aux:
+    if run_aux:
         def verify_two():
             nonlocal flag2
             eng._call("sylow_hip_bls_verify_two_pairings_batch", pk.ptr, None, dm.ptr, doff.ptr, sig.ptr, None, ok.ptr, nv)
@@ -851,7 +860,7 @@ def main():
         }
         if aux:
             out["aux"] = aux
-        if not args.no_cpu and world == 1:
+        if run_cpu and world == 1:
             out["cpu_baseline"] = cpu_baseline(check)
         if dist is not None:
             out["collective_backend"] = backend

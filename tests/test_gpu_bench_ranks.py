@@ -8,6 +8,7 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -18,7 +19,7 @@ def run_bench(extra):
     s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
     env = dict(os.environ, SYLOW_BENCH_BACKEND="gloo", SYLOW_BENCH_SINGLE_DEVICE="1", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--log2n", "12", "--steps", "1", "--warmup", "1", "--no-cpu"] + extra
+           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--log2n", "12", "--steps", "1", "--warmup", "1", "--full", "--no-cpu"] + extra
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -74,7 +75,7 @@ def run_bench_nccl_one_rank(extra):
     s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK="0", LOCAL_RANK="0", WORLD_SIZE="1")
     env.pop("SYLOW_BENCH_BACKEND", None); env.pop("SYLOW_BENCH_SINGLE_DEVICE", None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--force-dist", "--log2n", "12", "--steps", "1", "--warmup", "1", "--no-cpu"] + extra
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--force-dist", "--log2n", "12", "--steps", "1", "--warmup", "1", "--full", "--no-cpu"] + extra
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     return json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
@@ -92,7 +93,7 @@ def test_one_rank_nccl_native_communicator():
 
 def test_single_rank_bench_self_check():
     """The N = 1 line at a small batch: oracle spot check of the timed output, all single-GPU configs, CPU leg."""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--log2n", "13", "--steps", "2", "--warmup", "1"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--log2n", "13", "--steps", "2", "--warmup", "1", "--full"],
                        capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
@@ -122,3 +123,27 @@ def test_single_rank_bench_self_check():
     assert "C2c_g2_scalar_mul_2^13" in cfg
     c1 = cfg["C1_single_calls"]                         # one pairing / sign / verify per call: the single-wavefront latency routes
     assert c1["verify_ok"] == 1 and 0 < c1["pairing_ms"] < 50 and 0 < c1["verify_ms"] < 50
+
+
+def test_plain_run_is_lean_and_dumps_what_full_dumps(tmp_path):
+    """A plain run prints the headline without the legs that only --full runs (`aux`, `cpu_baseline`), and its timed steps write
+    the same outputs as a --full run's with the same arguments."""
+    out = {}
+    for mode, extra in (("plain", []), ("full", ["--full", "--no-cpu"])):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--log2n", "12", "--steps", "2", "--warmup", "1",
+               "--dump-outputs", str(tmp_path / mode)] + extra
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT)
+        assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        out[mode] = json.loads(lines[0])
+    plain, full = out["plain"], out["full"]
+    assert "aux" not in plain and "cpu_baseline" not in plain and "aux" in full and "cpu_baseline" not in full
+    assert all(plain[k] == full[k] for k in ("metric", "unit", "higher_is_better", "dtype", "steps", "warmup", "scaling"))
+    assert plain["value"] > 0 and plain["ms_per_step"] > 0 and plain["roofline"]["kernel_ms"] > 0
+    assert plain["config"]["bls_all_valid"] == 1 and plain["config"]["bls_verify_steps"] == 2 and plain["config"]["bls_verifies_per_s"] > 0
+    assert plain["roofline"]["stagger_gain_2^12"] is None and full["roofline"]["stagger_gain_2^12"] is not None
+    files = sorted(os.listdir(tmp_path / "plain"))
+    assert len(files) == 5 and files == sorted(os.listdir(tmp_path / "full"))
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / "plain" / f), np.load(tmp_path / "full" / f)), f

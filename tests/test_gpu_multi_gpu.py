@@ -57,7 +57,7 @@ def test_native_collectives_n_ranks_vs_oracle():
 @needs_two
 def test_driver_bench_command_n_ranks_rccl():
     for n in rank_counts():
-        args = [os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--log2n", "16", "--steps", "2", "--warmup", "1", "--no-cpu"]
+        args = [os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--log2n", "16", "--steps", "2", "--warmup", "1", "--full", "--no-cpu"]
         out = launch(n, args)
         print(f"[multi-gpu pre-flight] bench N={n}: value={out['value']:.0f} pairings/s, verifies={out['config']['bls_verifies_per_s']:.0f}/s, "
               f"strong={json.dumps(out['aux']['strong'])}, kernel_ms_rank0={json.dumps(out['aux']['kernel_ms_rank0'])}")

@@ -1,4 +1,4 @@
-"""Workload driver for tools/prof_configs.sh: every configuration bench.py prints, at bench.py's sizes, each bracketed by two
+"""Workload driver for tools/prof_configs.sh: every configuration bench.py --full prints, at bench.py's sizes, each bracketed by two
 MARKER launches (a tiny k_fp_unop with a grid size no workload uses) so that the summariser can cut the ordered dispatch list of a
 rocprofv3 pass into per-configuration windows -- several configurations share kernels (k_pair_lines, k_glued_from_tables ...), so
 kernel names alone do not attribute a dispatch.  Window i = dispatches strictly between marker 2i and marker 2i + 1; it holds

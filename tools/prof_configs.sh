@@ -1,6 +1,6 @@
 #!/bin/bash
 # usage: prof_configs.sh <tag> [--only name,name]
-# rocprofv3 evidence for EVERY configuration bench.py prints: one --kernel-trace run for durations, then one --pmc
+# rocprofv3 evidence for EVERY configuration bench.py --full prints: one --kernel-trace run for durations, then one --pmc
 # run per counter group (a trace domain is never combined with --pmc; FETCH_SIZE and WRITE_SIZE in passes of their own, as
 # MI355X_MICROARCH.md prescribes), all over the same workload driver (tools/prof_configs.py, which brackets every configuration
 # with marker launches).  tools/prof_summarize.py cuts each pass into per-configuration windows and writes
@@ -25,4 +25,4 @@ python3 tools/prof_summarize.py $OUT "profiles/$TAG"
 python3 tools/kernel_usage.py plk_pairing plk_quad plk_multi plk_verify plk_group g1 hash sign sign_wide tower runtime > $OUT/kernel_usage.txt 2>&1
 cp profiles/pmc_current.json $OUT/pmc_previous.json 2>/dev/null
 cp $OUT/pmc_current.json profiles/pmc_current.json          # on the GPU box's copy of the tree: bench.py reads it from there
-python3 bench.py --steps ${BENCH_STEPS:-10} --warmup 3 > $OUT/bench_full_line.json 2> $OUT/bench.err
+python3 bench.py --full --steps ${BENCH_STEPS:-10} --warmup 3 > $OUT/bench_full_line.json 2> $OUT/bench.err
