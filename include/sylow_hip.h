@@ -583,7 +583,13 @@ int32_t sylow_hip_bls_batch_verify_weighted(const uint64_t* pk_xy, const uint8_t
 
 /* ---- test hooks (stable enough for the repo's own tests; not part of the drop-in surface) ------------------------------------
  * Granger-Scott cyclotomic square (pairing.rs:309-350) and the raw Fp12 selector: 0..7 one-element-per-lane tower ops (tower.hip), 8 / 9 product /
- * cyclotomic square on the carry-free core, 10 / 11 exp_by_neg_z (carry-free / saturated), 16..29 the lane-pair Fp12 layer. */
+ * cyclotomic square on the carry-free core, 10 / 11 exp_by_neg_z (carry-free / saturated), 16..31 the lane-pair Fp12 layer: 16 product,
+ * 17 square, 18 sparse product (b = ell_0, ell_vw, ell_vv), 19 cyclotomic square, 20..22 Frobenius 1..3, 23 exp_by_neg_z, 24..27 product,
+ * square, inverse, cyclotomic square on the saturated core, 28 conjugate, 29 sparse product with ell_0 = (element index & 1), 30 / 31 the
+ * Miller loop's doubling / addition step (a = R (X, Y, Z) then Q (x, y); b = P (x, y); out = the new R then ell_0, ell_vw P.y, ell_vv P.x).
+ * The same routines at the same offset on the other layouts: 32..47 lane quads (offsets 0..7, 13..15), 48..63 / 64..79 one wavefront per
+ * one / two elements (offsets 0..7, 14, 15; 2 is the product by the line (ell_0, 0, ell_vv; 0, ell_vw, 0), 8 the final exponentiation,
+ * 10 the inverse).  Another op, or a missing b where the op reads one, is SYLOW_HIP_E_ARG. */
 /* @shape a=u64[48*n] out=u64[48*n] */
 int32_t sylow_hip_fp12_cyclotomic_sqr_batch(const uint64_t* a, uint64_t* out, size_t n, void* stream);
 /* @shape a=u64[48*n] b=u64[*]? out=u64[48*n] */

@@ -282,6 +282,25 @@ def g2_precompute(q_aff):
     return out
 
 
+def g2_doubling_step(r_proj, p_aff):
+    """one doubling step of R (projective, [n, 24]) with its line at P (affine, [n, 8]) -> [n, 48]: the new R, then
+    ell_0, ell_vw * P.y, ell_vv * P.x"""
+    r, p = _u64(r_proj, 24), _u64(p_aff, 8)
+    assert r.shape[0] == p.shape[0]
+    out = np.empty((r.shape[0], 48), dtype=np.uint64)
+    lib().oracle_g2_doubling_step(_p(r), _p(p), _p(out), ctypes.c_size_t(r.shape[0]))
+    return out
+
+
+def g2_addition_step(r_proj, q_aff, p_aff):
+    """one addition step R + Q (R projective [n, 24], Q affine [n, 16]) with its line at P (affine, [n, 8]) -> [n, 48] as above"""
+    r, q, p = _u64(r_proj, 24), _u64(q_aff, 16), _u64(p_aff, 8)
+    assert r.shape[0] == q.shape[0] == p.shape[0]
+    out = np.empty((r.shape[0], 48), dtype=np.uint64)
+    lib().oracle_g2_addition_step(_p(r), _p(q), _p(p), _p(out), ctypes.c_size_t(r.shape[0]))
+    return out
+
+
 def miller_loop(p_aff, q_aff):
     p, q = _u64(p_aff, 8), _u64(q_aff, 16)
     out = np.empty((p.shape[0], 48), dtype=np.uint64)

@@ -937,6 +937,30 @@ API void oracle_g2_precompute(const u64 *q, u64 *coeffs, size_t n) {
     for (int j = 0; j < 87; ++j) { u64 *o = coeffs + (i * 87 + j) * 24; st2(o, c[j].e0); st2(o + 8, c[j].e1); st2(o + 16, c[j].e2); }
   }
 }
+/* One step of G2Affine::precompute (pairing.rs:756-772, 798-818) and its line evaluated at P as line_mul multiplies it in: R projective
+ * (24 words), Q affine (16 words, addition only), P affine (8 words) -> the stepped R (24 words), then ell_0, ell_vw y_P, ell_vv x_P (24 words) */
+static void miller_step_out(u64 *o, g2p r, ell l, g1a p) {
+  st2(o, r.x); st2(o + 8, r.y); st2(o + 16, r.z);
+  st2(o + 24, l.e0); st2(o + 32, fp2_scale(l.e1, p.y)); st2(o + 40, fp2_scale(l.e2, p.x));
+}
+API void oracle_g2_doubling_step(const u64 *r, const u64 *p, u64 *out, size_t n) {
+  oracle_init();
+  for (size_t i = 0; i < n; ++i) {
+    g2p q = {ld2(r + 24 * i), ld2(r + 24 * i + 8), ld2(r + 24 * i + 16)};
+    g1a pa = {ld(p + 8 * i), ld(p + 8 * i + 4), 0};
+    ell l = g2_doubling_step(&q);
+    miller_step_out(out + 48 * i, q, l, pa);
+  }
+}
+API void oracle_g2_addition_step(const u64 *r, const u64 *qa, const u64 *p, u64 *out, size_t n) {
+  oracle_init();
+  for (size_t i = 0; i < n; ++i) {
+    g2p q = {ld2(r + 24 * i), ld2(r + 24 * i + 8), ld2(r + 24 * i + 16)};
+    g1a pa = {ld(p + 8 * i), ld(p + 8 * i + 4), 0};
+    ell l = g2_addition_step(&q, ld2(qa + 16 * i), ld2(qa + 16 * i + 8));
+    miller_step_out(out + 48 * i, q, l, pa);
+  }
+}
 /* raw Miller loop (strict replay of pairing.rs:590-619,676-818): P affine (8 words), Q affine (16 words) -> f */
 API void oracle_miller_loop(const u64 *p, const u64 *q, u64 *out, size_t n) {
   oracle_init();

@@ -105,7 +105,14 @@ namespace plkh {        // lane-pair units
 // selectors of plk_pairing.hip's Fp12 kernel (sylow_hip_fp12_hook_batch, and the Fp12 entry points of tower.hip)
 enum { OPW_MUL = 16, OPW_SQR = 17, OPW_SPARSE = 18, OPW_CYCSQR = 19, OPW_FROB1 = 20, OPW_FROB2 = 21, OPW_FROB3 = 22, OPW_EXPZ = 23,
        OPW_S_MUL = 24, OPW_S_SQR = 25, OPW_S_INV = 26, OPW_S_CYCSQR = 27, OPW_CONJ = 28,
-       OPW_SPARSE_UNIT = 29, OPW_LAST = 29 };   // 29: first line coefficient = (element index & 1), the other two from `b` as for 18
+       OPW_SPARSE_UNIT = 29, OPW_DBL = 30, OPW_ADD = 31, OPW_LAST = 31 };   // 29: first line coefficient = (element index & 1), the other two from `b` as for 18
+// 30 / 31: g2_doubling_step29 / g2_addition_step29 (ISO = false).  a: R = (X, Y, Z) in words 0..23, Q = (bx, by) in words 24..39 (31 only);
+// b: P = (x, y) in words 0..7.  out: the stepped R in words 0..23, then the line as the Miller loop multiplies it in: l0, l1 y_P, l2 x_P.
+// The same routines on the other layouts, at the same offset from their block's base: op = OPB_* + (OPW_* - OPW_MUL).  The one-wavefront
+// blocks have no saturated routines; their offsets 8 and 10 are final_exponentiation29_wide and w12_inv_wide.
+enum { OPB_QUAD = 32, OPB_WIDE1 = 48, OPB_WIDE2 = 64, OPB_END = 80, OPX_FINAL_EXP = 8, OPX_INV = 10 };
+// the offsets each block serves: lane-pair 0..15, quad 0..7 and 13..15, wide 0..8, 10, 14, 15; and those that read `b`
+constexpr unsigned OPX_QUAD_SET = 0xE0FFu, OPX_WIDE_SET = 0xC5FFu, OPX_NEEDS_B = 0xE005u;
 // plk_pairing.hip: one Fp12 operation on the lane-pair layer (op = an OPW_* selector; OPW_SPARSE: b = 24 words)
 int32_t fp12_op(int32_t op, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n, void* stream);
 int32_t build_lines29(const uint64_t* q_xy, size_t n, size_t idx, bn254::i32* table, void* stream);   // plk_verify.hip; q_xy NULL = generator
@@ -117,6 +124,7 @@ size_t wide_batch_max();
 size_t wide_verify_max();
 int32_t miller_raw_wide_batch(const uint64_t* p_xy, const uint64_t* q_xy, uint64_t* f_out, size_t n, void* stream);
 int32_t final_exp_wide_batch(const uint64_t* f, uint64_t* gt_out, size_t n, void* stream);
+int32_t fp12_op_wide(int epw, int32_t off, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n, void* stream);   // test hook, ops OPB_WIDE1 / 2 + off
 int32_t verify_two_pairings_wide_batch(const uint64_t* pk_xy, const uint8_t* pk_inf, const uint64_t* h, const uint8_t* h_inf, const uint64_t* sig_xy, const uint8_t* sig_inf,
                                        uint64_t* scratch, uint8_t* ok, size_t n, void* stream);
 int32_t pairing_wide_batch(const uint64_t* p_xy, const uint8_t* p_inf, const uint64_t* q_xy, const uint8_t* q_inf, uint64_t* scratch, uint64_t* gt_out, size_t n, void* stream);
@@ -128,6 +136,7 @@ size_t tail_split(size_t n);       // the remainder of a batch of whole rounds +
 int32_t pairing_quad_range(const uint64_t* p_xy, const uint8_t* p_inf, const uint64_t* q_xy, const uint8_t* q_inf, uint64_t* gt_out, size_t n, size_t m, void* stream);
 int32_t miller_loop_quad_batch(const uint64_t* p_xy, const uint64_t* q_xy, uint64_t* f_out, size_t n, void* stream);
 int32_t final_exp_quad_batch(const uint64_t* f, uint64_t* gt_out, size_t n, void* stream);
+int32_t fp12_op_quad(int32_t off, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n, void* stream);   // test hook, ops OPB_QUAD + off
 int32_t verify_fused_quad(int pk_is_table, const uint64_t* pk_xy, const uint8_t* pk_inf, const bn254::i32* pk_table, const uint64_t* hneg, const uint8_t* hneg_inf,
                           const uint64_t* sig_xy, const uint8_t* sig_inf, const bn254::i32* gen, uint8_t* ok, size_t n, size_t m, void* stream);
 // plk_group.hip: EIP-197 pair decoding + validation into SoA arrays (one lane pair per 192-byte pair)

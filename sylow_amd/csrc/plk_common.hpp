@@ -30,6 +30,52 @@ BN_DEV void store_s12(u64* base, size_t n, size_t i, int odd, const S12& a) {
   store_s2(base, n, i, 0, odd, a.c0.c0); store_s2(base, n, i, 8, odd, a.c0.c1); store_s2(base, n, i, 16, odd, a.c0.c2);
   store_s2(base, n, i, 24, odd, a.c1.c0); store_s2(base, n, i, 32, odd, a.c1.c1); store_s2(base, n, i, 40, odd, a.c1.c2);
 }
+// ---- test hook (sylow_hip_fp12_hook_batch) shared by the lane-pair and the lane-quad unit: one routine of the carry-free tower on element i,
+// off = op - the block's base (host.hpp OPW_* - OPW_MUL).  `b` holds the second operand, the three line coefficients (ell_0, ell_vw, ell_vv:
+// 24 words) for the sparse products, or P for the Miller steps.  Compiled with BN_QUAD 1 the routines reach the leaf-pair forms: the
+// product, square, sparse products and Frobenius maps W2_MUL2; the cyclotomic square and exp_by_neg_z W2_MUL2 through w_fp4_square_fold
+// and the product; the doubling step W2_MUL_SQR, W2_SQR2, W2_SQR_MUL and W2_MUL2; the addition step W2_MUL2 and W2_SQR2; the line
+// scaling after either step W2_SCALE2.
+BN_DEV void w12_hook_op(int off, S12& sr, const S12& sx, const u64* b, size_t n, size_t i, int odd) {
+  using namespace plkh;
+  constexpr int MUL = OPW_MUL;
+  W12 x, y, r;
+  w12_from_s12(x, sx);
+  if (off == OPW_DBL - MUL || off == OPW_ADD - MUL) {            // Miller steps (ISO = false): R in x.c0, Q in x.c1.c0 / c1.c1, P in b
+    const F29 px = f29_reduce(f29_from_fp(load_fp(b, n, i, 0))), py = f29_reduce(f29_from_fp(load_fp(b, n, i, 4)));
+    G2W q{x.c0.c0, x.c0.c1, x.c0.c2};
+    W2 l0, l1, l2, s1, s2;
+    if (off == OPW_ADD - MUL) g2_addition_step29(q, x.c1.c0, x.c1.c1, l0, l1, l2);
+    else g2_doubling_step29<false>(q, l0, l1, l2);
+    W2_SCALE2(s1, s2, l1, py, l2, px);                             // the Miller loop's line_mul: l1 y_P, l2 x_P
+    r.c0 = W6{q.x, q.y, q.z};
+    r.c1 = W6{l0, s1, s2};
+  } else {
+    if (b) {
+      S12 sy;
+      if (off == OPW_SPARSE - MUL || off == OPW_SPARSE_UNIT - MUL) {   // three line coefficients: 24 words, whatever the width of the array behind them
+        sy.c0.c0 = load_s2(b, n, i, 0, odd); sy.c0.c1 = load_s2(b, n, i, 8, odd); sy.c0.c2 = load_s2(b, n, i, 16, odd);
+        sy.c1 = sy.c0;
+      } else {
+        load_s12(sy, b, n, i, odd);
+      }
+      w12_from_s12(y, sy);
+    }
+    switch (off) {
+      case OPW_MUL - MUL: w12_mul_nl(r, x, y); break;
+      case OPW_SQR - MUL: r = w12_sqr(x); break;
+      case OPW_SPARSE - MUL: r = w12_sparse_mul(x, y.c0.c0, y.c0.c1, y.c0.c2); break;
+      case OPW_CYCSQR - MUL: w12_cyclotomic_sqr_nl(r, x); break;
+      case OPW_FROB1 - MUL: w12_frobenius_nl<1>(r, x); break;
+      case OPW_FROB2 - MUL: w12_frobenius_nl<2>(r, x); break;
+      case OPW_FROB3 - MUL: w12_frobenius_nl<3>(r, x); break;
+      case OPW_CONJ - MUL: r = w12_conj(x); break;
+      case OPW_SPARSE_UNIT - MUL: r = w12_sparse_mul_unit(x, (i32)(i & 1), y.c0.c1, y.c0.c2); break;
+      default: exp_by_neg_z29(r, x); break;
+    }
+  }
+  w12_to_s12(sr, r);
+}
 // ---- staggered launches (plk_pairing.hip: k_pairing; plk_verify.hip: k_bls_verify_fused) -------------------------------------------------
 // Blocks [first, first + count) run only the first half of their element's work (the Miller loop) and park the value; blocks >= nblk finish
 // the parked chunks (b - nblk + first).  See k_pairing for why.

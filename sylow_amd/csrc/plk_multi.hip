@@ -640,6 +640,61 @@ __global__ void HEAVY_BOUNDS k_final_exp_wide_batch(const u64* fa, const u64* fb
   const bool one = s12_is_one(g);
   if (is_one && !odd) is_one[i] = one ? 1 : 0;
 }
+// test hook: one routine of the one-wavefront layer (ops OPB_WIDE1 / OPB_WIDE2 + off of sylow_hip_fp12_hook_batch; operands as for the
+// lane-pair hook, plk_common.hpp w12_hook_op), one wavefront per EPW elements.  The three product kinds each on its own: off 0 WK_DENSE,
+// 1 WK_SQUARE, 2 WK_LINE on the line (l0, 0, l2; 0, l4, 0) built from b's three coefficients (ell_0, ell_vw = l4, ell_vv = l2).  The
+// element index is clamped as in k_miller_wide_batch, so that both halves of a wavefront reach every barrier; only live rows are stored.
+template <int EPW>
+__global__ void HEAVY_BOUNDS k_wide_op(int off, const u64* a, const u64* b, u64* out, size_t n) {
+  using namespace plkh;
+  constexpr int MUL = OPW_MUL;
+  __shared__ WideLds lds[EPW];
+  const int half = EPW == 2 ? (int)(threadIdx.x >> 5) : 0;
+  const size_t e0 = (size_t)EPW * blockIdx.x + (size_t)half;
+  const bool live = e0 < n;
+  const size_t i = live ? e0 : n - 1;
+  const int odd = pair_role(threadIdx.x);
+  const WideLdsPtr x = (WideLdsPtr)&lds[half];
+  S12 sx, sr;
+  load_s12(sx, a, n, i, odd);
+  if (off == OPX_FINAL_EXP) {
+    final_exponentiation29_wide<EPW>(sr, sx, &lds[half]);
+  } else {
+    const W2 zero{F29{{0, 0, 0, 0, 0, 0, 0, 0, 0}}};
+    W12 u, v, r;
+    w12_from_s12(u, sx);
+    if (b && (off == OPW_SPARSE - MUL || off == OPW_DBL - MUL || off == OPW_ADD - MUL)) {
+      v.c0 = W6{w2_from_s2(load_s2(b, n, i, 0, odd)), zero, w2_from_s2(load_s2(b, n, i, 16, odd))};     // the line; or P's x, y in v.c0.c0
+      v.c1 = W6{zero, w2_from_s2(load_s2(b, n, i, 8, odd)), zero};
+    } else if (b) {
+      S12 sy;
+      load_s12(sy, b, n, i, odd);
+      w12_from_s12(v, sy);
+    }
+    switch (off) {
+      case OPW_MUL - MUL: r = w12_mul_wide<EPW, WK_DENSE>(u, v, x); break;
+      case OPW_SQR - MUL: r = w12_mul_wide<EPW, WK_SQUARE>(u, u, x); break;
+      case OPW_SPARSE - MUL: r = w12_mul_wide<EPW, WK_LINE>(u, v, x); break;
+      case OPW_CYCSQR - MUL: r = w12_cyclotomic_sqr_wide<EPW>(u, x); break;
+      case OPW_FROB1 - MUL: r = w12_frobenius_wide<1, EPW>(u, x); break;
+      case OPW_FROB2 - MUL: r = w12_frobenius_wide<2, EPW>(u, x); break;
+      case OPW_FROB3 - MUL: r = w12_frobenius_wide<3, EPW>(u, x); break;
+      case OPW_EXPZ - MUL: exp_by_neg_z29_wide<EPW>(r, u, &lds[half]); break;
+      case OPX_INV: r = w12_inv_wide<EPW>(u, x); break;
+      default: {                                                  // Miller steps (ISO = false): R in u.c0, Q in u.c1.c0 / c1.c1, P in b
+        const F29 px = f29_reduce(f29_from_fp(load_fp(b, n, i, 0))), py = f29_reduce(f29_from_fp(load_fp(b, n, i, 4)));
+        G2W q{u.c0.c0, u.c0.c1, u.c0.c2};
+        W2 l0, l1, l2;                                            // l1, l2 come out already scaled by y_P, x_P
+        if (off == OPW_ADD - MUL) g2_addition_step29_wide<EPW>(q, u.c1.c0, u.c1.c1, l0, l1, l2, px, py, x);
+        else g2_doubling_step29_wide<false, EPW>(q, l0, l1, l2, px, py, x);
+        r.c0 = W6{q.x, q.y, q.z};
+        r.c1 = W6{l0, l1, l2};
+      }
+    }
+    w12_to_s12(sr, r);
+  }
+  if (live && wide_j<EPW>((int)(threadIdx.x & 63u)) == 0) store_s12(out, n, i, odd, sr);
+}
 // final_exponentiation(prod of the raw values of job j's pairs), one wavefront per job: raw SoA stride n_pairs (k_miller_wide_batch),
 // job j owns pairs [offsets[j], offsets[j + 1]) (an empty job is the identity); Gt values (SoA stride n_jobs) and / or flags
 __global__ void HEAVY_BOUNDS k_final_exp_wide_jobs(const u64* raw, size_t n_pairs, const u64* offsets, size_t n_jobs, u64* gout, uint8_t* is_one) {
@@ -882,6 +937,12 @@ int32_t miller_raw_wide_batch(const uint64_t* p_xy, const uint64_t* q_xy, uint64
     plk::k_miller_wide_batch<2, false><<<dim3((unsigned)((n + 1) / 2)), dim3(64), 0, st>>>(p_xy, nullptr, q_xy, nullptr, f_out, nullptr, nullptr, nullptr, nullptr, nullptr, n);
   else
     plk::k_miller_wide_batch<1, false><<<dim3((unsigned)n), dim3(64), 0, st>>>(p_xy, nullptr, q_xy, nullptr, f_out, nullptr, nullptr, nullptr, nullptr, nullptr, n);
+  LAUNCHED();
+}
+int32_t fp12_op_wide(int epw, int32_t off, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (epw == 2) plk::k_wide_op<2><<<dim3((unsigned)((n + 1) / 2)), dim3(64), 0, st>>>(off, a, b, out, n);
+  else plk::k_wide_op<1><<<dim3((unsigned)n), dim3(64), 0, st>>>(off, a, b, out, n);
   LAUNCHED();
 }
 // final_exponentiation(f_i), i < n <= wide_batch_max()

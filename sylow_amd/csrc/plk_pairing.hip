@@ -72,8 +72,8 @@ __global__ void HEAVY_BOUNDS k_pairing(const u64* pxy, const uint8_t* pinf, cons
   probe_end(pb, st.clk);
 }
 
-// test hook: the lane-pair Fp12 layer one operation at a time (ops 16.. of sylow_hip_fp12_hook_batch); `b` carries the second
-// operand, or the three line coefficients (ell_0, ell_vw, ell_vv) in its first 24 words for the sparse product
+// test hook: the lane-pair Fp12 layer one operation at a time (ops 16.. of sylow_hip_fp12_hook_batch; plk_common.hpp w12_hook_op); `b`
+// carries the second operand, the three line coefficients (ell_0, ell_vw, ell_vv) in its first 24 words for the sparse products, or P
 using namespace plkh;      // the OPW_* selectors (host.hpp)
 __global__ void HEAVY_BOUNDS k_w12_op(int op, const u64* a, const u64* b, u64* out, size_t n) {
   const size_t t = TID, i = pair_index(t);
@@ -81,36 +81,14 @@ __global__ void HEAVY_BOUNDS k_w12_op(int op, const u64* a, const u64* b, u64* o
   if (i >= n) return;
   S12 sx, sy, sr;
   load_s12(sx, a, n, i, odd);
-  if (b) {
-    if (op == OPW_SPARSE || op == OPW_SPARSE_UNIT) {      // three line coefficients: 24 words, whatever the width of the array behind them
-      sy.c0.c0 = load_s2(b, n, i, 0, odd); sy.c0.c1 = load_s2(b, n, i, 8, odd); sy.c0.c2 = load_s2(b, n, i, 16, odd);
-      sy.c1 = sy.c0;
-    } else {
-      load_s12(sy, b, n, i, odd);
-    }
-  }
   if (op >= OPW_S_MUL && op <= OPW_S_CYCSQR) {       // saturated lane-pair layer (bn254_pair.hpp)
+    if (b) load_s12(sy, b, n, i, odd);
     if (op == OPW_S_MUL) sr = s12_mul(sx, sy);
     else if (op == OPW_S_SQR) sr = s12_sqr(sx);
     else if (op == OPW_S_INV) sr = s12_inv(sx);
     else sr = cyclotomic_sqr(sx);
   } else {
-    W12 x, y, r;
-    w12_from_s12(x, sx);
-    if (b) w12_from_s12(y, sy);
-    switch (op) {
-      case OPW_MUL: w12_mul_nl(r, x, y); break;
-      case OPW_SQR: r = w12_sqr(x); break;
-      case OPW_SPARSE: r = w12_sparse_mul(x, y.c0.c0, y.c0.c1, y.c0.c2); break;
-      case OPW_CYCSQR: w12_cyclotomic_sqr_nl(r, x); break;
-      case OPW_FROB1: w12_frobenius_nl<1>(r, x); break;
-      case OPW_FROB2: w12_frobenius_nl<2>(r, x); break;
-      case OPW_FROB3: w12_frobenius_nl<3>(r, x); break;
-      case OPW_CONJ: r = w12_conj(x); break;
-      case OPW_SPARSE_UNIT: r = w12_sparse_mul_unit(x, (i32)(i & 1), y.c0.c1, y.c0.c2); break;
-      default: exp_by_neg_z29(r, x); break;
-    }
-    w12_to_s12(sr, r);
+    w12_hook_op(op - OPW_MUL, sr, sx, b, n, i, odd);
   }
   store_s12(out, n, i, odd, sr);
 }
@@ -194,10 +172,18 @@ int32_t sylow_hip_pairing_batch(const uint64_t* p_xy, const uint8_t* p_inf, cons
   return e != hipSuccess ? host::fail(e, "kernel launch") : rc;
 }
 // test hook: raw Fp12 selector.  0..11: the one-element-per-lane layer (tower.hip: 8 product on the carry-free core, 9 cyclotomic square on
-// it, 10 / 11 exp_by_neg_z on the carry-free / saturated core); 16..29: the lane-pair Fp12 layer (plk::k_w12_op)
+// it, 10 / 11 exp_by_neg_z on the carry-free / saturated core); 16..31: the lane-pair Fp12 layer and Miller steps (plk::k_w12_op);
+// 32..47 the same on lane quads (plk_quad.hip), 48..63 / 64..79 on one wavefront per one / two elements (plk_multi.hip), at the offsets of host.hpp
 int32_t sylow_hip_fp12_hook_batch(int32_t op, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n, void* stream) {
-  ARGCHK(a && out && op >= 0 && (op <= 11 || (op >= 16 && op <= plk::OPW_LAST))); if (!n) return SYLOW_HIP_OK;
-  if (op < 16) return towerh::fp12_hook(op, a, b, out, n, stream);
+  using namespace plkh;
+  const int off = (op - OPW_MUL) & 15;
+  ARGCHK(a && out && op >= 0 && (op <= 11 || (op >= OPW_MUL && op < OPB_END)));
+  ARGCHK(op < OPB_QUAD || ((op < OPB_WIDE1 ? OPX_QUAD_SET : OPX_WIDE_SET) >> off) & 1);
+  ARGCHK(op < OPW_MUL || b || !((OPX_NEEDS_B >> off) & 1));
+  if (!n) return SYLOW_HIP_OK;
+  if (op < OPW_MUL) return towerh::fp12_hook(op, a, b, out, n, stream);
+  if (op >= OPB_WIDE1) return fp12_op_wide(op >= OPB_WIDE2 ? 2 : 1, off, a, b, out, n, stream);
+  if (op >= OPB_QUAD) return fp12_op_quad(off, a, b, out, n, stream);
   plk::k_w12_op<<<GRID(2 * n)>>>(op, a, b, out, n); LAUNCHED();
 }
 }  // extern "C"

@@ -72,9 +72,23 @@ __global__ void HEAVY_BOUNDS k_bls_verify_fused_quad(const u64* pkxy, const uint
   bls_verify_fused_body<PK_TABLE>(pkxy, pkinf, pk_table, hneg, hneg_inf, sigxy, siginf, gen_table, okout, n, m, none);
   probe_end(pb, clk);
 }
+// test hook: the lane-pair tower's routines on quads, one at a time (ops OPB_QUAD + off of sylow_hip_fp12_hook_batch; plk_common.hpp
+// w12_hook_op names the leaf-pair form each one reaches); all four lanes of a quad leave together, sub-pair 0 stores
+__global__ void HEAVY_BOUNDS k_w12_op_quad(int off, const u64* a, const u64* b, u64* out, size_t n) {
+  const size_t t = TID, i = quad_index(t);
+  const int odd = pair_role(t);
+  if (i >= n) return;
+  S12 sx, sr;
+  load_s12(sx, a, n, i, odd);
+  w12_hook_op(off, sr, sx, b, n, i, odd);
+  if (quad_sub(t) == 0) store_s12(out, n, i, odd, sr);
+}
 }  // namespace plk
 
 namespace plkh {
+int32_t fp12_op_quad(int32_t off, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n, void* stream) {
+  plk::k_w12_op_quad<<<GRID(4 * n)>>>(off, a, b, out, n); LAUNCHED();
+}
 // Largest batch that takes a quad per element: up to one wavefront per SIMD of quads (16 per wavefront: 4 x CUs x 16 elements; 16 384 on this
 // part).  Above that the lane-pair kernel's single round is as fast.  SYLOW_HIP_OPT_QUAD_MAX moves it (0: never).
 size_t quad_batch_max() {

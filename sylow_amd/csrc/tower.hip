@@ -123,7 +123,7 @@ int32_t sylow_hip_fp12_cyclotomic_sqr_batch(const uint64_t* a, uint64_t* out, si
 }
 
 // test hook: raw k_fp12_op selector (8: product on the carry-free core, 9: cyclotomic square on it,
-// 10 / 11: exp_by_neg_z on the carry-free / saturated core); selectors 16..28 (the lane-pair Fp12 layer) are served by
+// 10 / 11: exp_by_neg_z on the carry-free / saturated core); selectors 16..79 (the lane-pair, lane-quad and one-wavefront layers) are served by
 // sylow_hip_fp12_hook_batch in plk_pairing.hip, which forwards the others here
 }  // extern "C"
 namespace towerh {

@@ -97,3 +97,124 @@ def fp2_sqrt(a):
             if _R().fp2_square((x0, x1)) == (a0 % P, a1 % P):
                 return (x0, x1)
     return None
+
+
+# ---- crafted inputs: values whose INTERNAL 29-bit digits are extreme, Fp12 shapes, points off the usual random path -------------------
+M29 = (1 << 29) - 1
+RP_INV = pow(pow(2, 261, P), P - 2, P)           # the carry-free core holds x * 2^261 mod p
+TOP_BOUND = P >> 233                             # |top limb| of a value near p / 2
+
+
+def crafted_values():
+    """canonical x whose internal representation v = x * 2^261 mod p (centred, |v| < p / 2) has extreme digits: low limbs all 2^29 - 1,
+    zero, alternating, or 2^28, under top limbs from 0 to the bounds +-p / 2^234; then 1 and p - 1 (0 is the all-zero pattern)"""
+    lows = [sum(M29 << (29 * i) for i in range(8)),                       # all ones
+            0,                                                             # all zero
+            sum((M29 if i % 2 else 0) << (29 * i) for i in range(8)),      # alternating
+            sum((M29 if i % 2 == 0 else 1) << (29 * i) for i in range(8)),
+            sum((1 << 28) << (29 * i) for i in range(8))]
+    tops = [0, 1, -1, 1_400_000, -1_400_000, 700_001, -700_001]
+    out = []
+    for lo in lows:
+        for t in tops:
+            v = lo + (t << 232)
+            assert abs(v) < 0.46 * P
+            out.append(v * RP_INV % P)
+    # the top limb at its bounds: -TOP_BOUND is reached as given; TOP_BOUND - 1 with these low limbs lies above p / 2 by less than the
+    # reduce pass's rounding, which maps it to its negative representative (top limb -TOP_BOUND - 1 or - 2)
+    for lo in lows:
+        for t in (1_585_000, -TOP_BOUND, TOP_BOUND - 1):
+            out.append((lo + (t << 232)) * RP_INV % P)
+    return out + [1, P - 1]
+
+
+def fp_cbrt(a):
+    """a cube root of a in Fp, or None.  p = 1 mod 9, so the 3-Sylow part needs a discrete log (Adleman-Manders-Miller)"""
+    a %= P
+    if a == 0:
+        return 0
+    if pow(a, (P - 1) // 3, P) != 1:
+        return None
+    s, t = 0, P - 1
+    while t % 3 == 0:
+        t //= 3
+        s += 1
+    z = 2
+    while pow(z, (P - 1) // 3, P) == 1:
+        z += 1
+    c = pow(z, t, P)                              # generates the subgroup of order 3^s
+    x0 = pow(a, pow(3, -1, t), P)                 # x0^3 = a * b with b = a^(t m) in that subgroup
+    b = pow(x0, 3, P) * pow(a, P - 2, P) % P
+    g = pow(c, 3 ** (s - 1), P)                   # order 3
+    j = 0
+    for k in range(s):                            # b = c^j, digit by digit
+        h = pow(b * pow(c, (3 ** s - j) % 3 ** s, P) % P, 3 ** (s - 1 - k), P)
+        j += [1, g, g * g % P].index(h) * 3 ** k
+    assert j % 3 == 0
+    x = x0 * pow(c, (3 ** s - j // 3) % 3 ** s, P) % P
+    assert pow(x, 3, P) == a
+    return x
+
+
+def crafted_g1_points(count=None):
+    """affine G1 points (x, y) on y^2 = x^3 + 3 with a crafted x, and with a crafted y (x = cbrt(y^2 - 3)), alternating"""
+    R = _R()
+    vals = crafted_values()
+    by_x, by_y = [], []
+    for v in vals:
+        y = R.fp_sqrt((v * v * v + 3) % P)
+        if y is not None:
+            by_x.append((v, y))
+        x = fp_cbrt((v * v - 3) % P)
+        if x is not None:
+            by_y.append((x, v))
+    out = [pt for pair in zip(by_x, by_y) for pt in pair]
+    return out[:count] if count else out
+
+
+def crafted_g2_points(count=None):
+    """affine twist points (x, y), x = (c0, c1) from the crafted values, y = sqrt(x^3 + b'): on the curve, NOT in the r-torsion"""
+    R = _R()
+    vals = crafted_values()
+    out = []
+    for k, v in enumerate(vals):
+        x = (v, vals[(7 * k + 3) % len(vals)])
+        y = fp2_sqrt(R.fp2_add(R.fp2_mul(R.fp2_square(x), x), R.TWIST_B))
+        if y is not None:
+            out.append((x, y))
+    return out[:count] if count else out
+
+
+def crafted_g2_projective(count=None):
+    """homogeneous (X, Y, Z) = (x Z, y Z, Z) over crafted twist points with a crafted Z in Fp2"""
+    R = _R()
+    vals = crafted_values()
+    out = []
+    for k, (x, y) in enumerate(crafted_g2_points()):
+        z = (vals[(5 * k + 1) % len(vals)], vals[(11 * k + 2) % len(vals)])
+        if z == (0, 0):
+            z = (vals[k % len(vals)] or 1, 0)
+        out.append((R.fp2_mul(x, z), R.fp2_mul(y, z), z))
+    return out[:count] if count else out
+
+
+def crafted_fp12_rows():
+    """Fp12 elements (12 Fp coefficients each, in limb order c0.c0.c0, c0.c0.c1, ..., c1.c2.c1) of special shape: 0, 1, elements of the
+    Fp, Fp2 and Fp6 subfields, c0 = 0, c1 = 0, one non-zero coefficient in each of the 12 slots, all 12 equal to one extreme value"""
+    vals = crafted_values()
+    ext = [v for v in vals if v not in (0, 1)]
+    pick = lambda k: ext[(k * 13 + 5) % len(ext)]
+    rows = [[0] * 12, [1] + [0] * 11]
+    for k in range(3):
+        rows.append([pick(k)] + [0] * 11)                                    # Fp
+        rows.append([pick(k + 3), pick(k + 4)] + [0] * 10)                   # Fp2
+        rows.append([pick(k + 6 + i) for i in range(6)] + [0] * 6)           # Fp6
+        rows.append([0] * 6 + [pick(k + 12 + i) for i in range(6)])          # c0 = 0
+        rows.append([pick(k + 18 + i) for i in range(6)] + [0] * 6)          # c1 = 0
+    for slot in range(12):
+        r = [0] * 12
+        r[slot] = pick(slot + 24)
+        rows.append(r)
+    for v in (ext[0], ext[6], ext[-3], P - 1):
+        rows.append([v] * 12)
+    return rows

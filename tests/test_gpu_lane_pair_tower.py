@@ -3,13 +3,12 @@ fp12 hook (ops 16..29), on random inputs and on inputs crafted so that the INTER
 import numpy as np
 import pytest
 
-from helpers import P, SEED, Xoshiro
+from helpers import RP_INV, SEED, Xoshiro, crafted_values  # noqa: F401
 from oracle import pyref as R
 
 pytestmark = pytest.mark.gpu
 OP = {"mul": 16, "sqr": 17, "sparse": 18, "cycsqr": 19, "frob1": 20, "frob2": 21, "frob3": 22, "expz": 23,
       "s_mul": 24, "s_sqr": 25, "s_inv": 26, "s_cycsqr": 27, "conj": 28, "sparse_unit": 29}
-RP_INV = pow(pow(2, 261, P), P - 2, P)           # the carry-free core holds x * 2^261 mod p
 
 
 def unit_lines(coracle, b):
@@ -18,24 +17,6 @@ def unit_lines(coracle, b):
     u[:, :8] = 0
     u[1::2, 0] = 1
     return u
-
-
-def crafted_values():
-    """canonical x whose internal representation v = x * 2^261 mod p (centred, |v| < 0.45 p) has extreme digits"""
-    m29 = (1 << 29) - 1
-    lows = [sum(m29 << (29 * i) for i in range(8)),                       # all ones
-            0,                                                             # all zero
-            sum((m29 if i % 2 else 0) << (29 * i) for i in range(8)),      # alternating
-            sum((m29 if i % 2 == 0 else 1) << (29 * i) for i in range(8)),
-            sum((1 << 28) << (29 * i) for i in range(8))]
-    tops = [0, 1, -1, 1_400_000, -1_400_000, 700_001, -700_001]
-    out = []
-    for lo in lows:
-        for t in tops:
-            v = lo + (t << 232)
-            assert abs(v) < 0.46 * P
-            out.append(v * RP_INV % P)
-    return out
 
 
 def test_lane_pair_fp12_ops_random(engine, coracle):
