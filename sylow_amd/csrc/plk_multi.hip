@@ -747,8 +747,9 @@ __global__ void HEAVY_BOUNDS k_final_exp_flag(const u64* fin, size_t n_in, u64* 
 // (pairing.rs:970-1022) consuming tables a host cached from sylow_hip_g2_precompute_batch: coeffs is the canonical SoA array
 // [87*24][m] (triple t of table k = words 24t..24t+23 = ell.0, ell.1, ell.2), pair i reads table tab_idx[i] (or table i when
 // tab_idx is NULL).  No G2 arithmetic: per step one shared squaring and, per pair, three coefficient loads, two scalings by the
-// G1 coordinates and one sparse product.  Canonical words enter the carry-free core directly: the 29-bit digits of x times
-// R'^2 mod p in one carry-free product (R' = 2^261), output N-class.
+// G1 coordinates and one sparse product.  The words enter the carry-free core directly: the 29-bit digits of x times R'^2 mod p
+// in one carry-free product (R' = 2^261), output N-class -- for every 256-bit x, so words >= p (up to 2^256 - 1 = 5.29 p) reduce like
+// Fp::new without a separate step (tools/f29_model.py from_plain, tests/test_f29_model.py).
 BN_DEV F29 f29_from_plain(const Fp& x) {
   F29 d;
   d.v[0] = (i32)(x.v[0] & BN_M29);

@@ -218,3 +218,54 @@ def crafted_fp12_rows():
     for v in (ext[0], ext[6], ext[-3], P - 1):
         rows.append([v] * 12)
     return rows
+
+
+# ---- non-canonical representatives: the C ABI reduces inputs >= p like Fp::new (include/sylow_hip.h) ------------------------------
+U256 = 1 << 256
+REP_SPECIAL = [P, 2 * P, 5 * P, P + 1, U256 - 1]          # == 0, 0, 0, 1 and 2^256 - 1 - 5 p: the words a caller may pass raw
+_KMAX5 = U256 - 5 * P                                      # x + 5 p fits 256 bits exactly when x < 2^256 - 5 p (5 p < 2^256 < 6 p)
+
+
+def _add_limbs(a, b):
+    """(N, 4) uint64 + (N, 4) uint64 with carries (no carry out: the callers stay below 2^256)"""
+    out = np.empty_like(a)
+    carry = np.zeros(a.shape[0], dtype=np.uint64)
+    for k in range(4):
+        s = a[:, k] + b[:, k]
+        c1 = s < a[:, k]
+        s2 = s + carry
+        c2 = s2 < s
+        out[:, k] = s2
+        carry = (c1 | c2).astype(np.uint64)
+    return out
+
+
+def representatives(arr, seed=0, largest=False):
+    """every 4-word Fp value x (canonical, < p) of a uint64 array of any shape replaced by x + k p, k >= 1: a random k in 1..4, or 1..5
+    where x < 2^256 - 5 p (largest=False), or the largest k that fits (largest=True: 5 below 2^256 - 5 p, else 4, so the canonical
+    value 2^256 - 1 - 5 p becomes 2^256 - 1).  Zeros take k = 1, 2, 5, 3, 4 in turn (p, 2p, 5p first) so that a handful of zero
+    coordinates already meets the special words.  Same shape and dtype out."""
+    a = np.ascontiguousarray(arr, dtype=np.uint64)
+    x = a.reshape(-1, 4)
+    assert ints_lt(x, P).all(), "representatives() needs canonical input"
+    fits5 = ints_lt(x, _KMAX5)
+    if largest:
+        k = np.where(fits5, 5, 4)
+    else:
+        g = np.random.default_rng(seed)
+        k = np.where(fits5, g.integers(1, 6, size=x.shape[0]), g.integers(1, 5, size=x.shape[0]))
+        zero = ~x.any(axis=1)
+        k[zero] = np.array([1, 2, 5, 3, 4])[np.arange(int(zero.sum())) % 5]
+    kp = limbs([j * P for j in range(6)])
+    return _add_limbs(x, kp[k]).reshape(a.shape)
+
+
+def ints_lt(x, c):
+    """row-wise x < c for (N, 4) little-endian uint64 limbs and an integer c < 2^256"""
+    cl = limbs([c])[0]
+    lt = np.zeros(x.shape[0], dtype=bool)
+    eq = np.ones(x.shape[0], dtype=bool)
+    for k in (3, 2, 1, 0):
+        lt |= eq & (x[:, k] < cl[k])
+        eq &= x[:, k] == cl[k]
+    return lt

@@ -334,6 +334,40 @@ def test_from_fp_round_trip():
             assert M.words_value(M.to_fp(a)) == x
 
 
+def test_from_plain_on_every_256_bit_word():
+    """f29_from_plain (plk_multi.hip) feeds the raw words of the table-driven Miller loop -- G1 coordinates and line coefficients -- to
+    the carry-free core.  The header lets a caller pass any 256-bit word (>= p reduced like Fp::new), up to 2^256 - 1 ~ 5.29 p: the
+    digits are exact (the top digit takes bits 232..255), the product by R'^2 wraps no i32 / i64 (the model raises), and the output is
+    the N class the comment claims -- normalized, value = X R' mod p up to a multiple of p, inside [-(V/169) p, (V/169 + 1) p), V < 5.3"""
+    src = open(os.path.join(ROOT, "sylow_amd", "csrc", "plk_multi.hip")).read()
+    rr = re.search(r"BN_DEV F29 f29_from_plain\(const Fp& x\) \{.*?const F29 rr\{\{([^}]*)\}\};", src, re.S).group(1)
+    assert [int(x, 16) for x in rr.split(",")] == M.RR and M.value(M.RR) == M.RP * M.RP % P
+    rng = random.Random(9)
+    top = (1 << 256) - 1
+    xs = [0, 1, P - 1, P, P + 1, 2 * P, 5 * P, top - 5 * P, top - 5 * P + 1, top, top - 1, 1 << 255, (1 << 256) - (1 << 232)]
+    xs += [sum(((1 << 29) - 1 if (i + j) % 2 else 0) << (29 * i) for i in range(9)) & top for j in range(2)]   # alternating full digits
+    xs += [rng.randrange(1 << 256) for _ in range(300)] + [rng.randrange(P) + k * P for k in range(1, 6) for _ in range(20)]
+    worst = 0.0
+    for x in xs:
+        if x > top:
+            continue
+        w = M.int_to_words(x)
+        d = M.plain_digits(w)
+        assert M.value(d) == x and all(0 <= v < B29 for v in d[:8]) and 0 <= d[8] < 1 << 24, hex(x)
+        r = M.from_plain(w)                                   # raises Overflow on any wrap
+        v = M.value(r)
+        assert M.normalized(r) and M.L(r) <= 1, hex(x)
+        assert (v - x * M.RP) % P == 0, hex(x)
+        bound = M.V(d) * M.V(M.RR) / 169
+        assert -bound * P <= v < (bound + 1) * P, hex(x)
+        worst = max(worst, M.V(d))
+    assert 5.28 < worst < 5.3                                 # 2^256 / p = 5.29
+    # the representatives of one value give congruent outputs: the kernels' results (canonical on the way out) are the same
+    for x in (0, 1, P - 1, rng.randrange(P)):
+        outs = {M.value(M.from_plain(M.int_to_words(x + k * P))) % P for k in range(6) if x + k * P <= top}
+        assert len(outs) == 1
+
+
 # ---- call sites ------------------------------------------------------------------------------------------------------------------
 # Every coefficient the kernels pass to the linear passes.  Keys: ("call", file, wrapper, first coefficient, second coefficient) for the
 # u2_/w2_/f29_ lin2 and xi_lin wrappers, ("init", file, initializer text) for the coefficient arrays handed to f29_reduce_terms /

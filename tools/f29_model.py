@@ -294,6 +294,28 @@ def from_fp(words):
     return r
 
 
+RR = [0x059bac10, 0x0d1503a3, 0x018016b8, 0x10ab0ca8, 0x02632639, 0x02c0169f, 0x169bfd53, 0x11869d4c, 0x002a11a6]   # R'^2 mod p
+
+
+def plain_digits(words):
+    """the 29-bit digits f29_from_plain cuts from 8 little-endian u32 words (any 256-bit value: the top digit holds bits 232..255)"""
+    x = [u32(w, "from_plain word") for w in words]
+    assert len(x) == 8
+    d = [x[0] & M29] + [0] * 8
+    for i in range(1, 9):
+        bit = 29 * i
+        w, sh = bit >> 5, bit & 31
+        lo = x[w] >> sh
+        hi = ((x[w + 1] << (32 - sh)) & 0xFFFFFFFF) if (sh > 3 and w + 1 < 8) else 0
+        d[i] = (lo | hi) & M29
+    return d
+
+
+def from_plain(words):
+    """f29_from_plain (plk_multi.hip): X's digits times R'^2 mod p in one carry-free product -> X R' mod p, normalized"""
+    return mul(plain_digits(words), RR)
+
+
 def _cond_sub(r, c, o8=0):
     """the borrow chain of the device: r - c over 8 words (then o8 - 0 - borrow when o8 takes part); keep r when it borrows"""
     s, borrow = [], 0
