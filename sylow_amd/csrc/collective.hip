@@ -77,8 +77,7 @@ int32_t sylow_hip_pairing_product_all(const uint64_t* p_xy, const uint8_t* p_inf
   }
   if (rc == SYLOW_HIP_OK) rc = sylow_hip_aos_to_soa(all, soa, 48, (size_t)world, stream);
   if (rc == SYLOW_HIP_OK) rc = sylow_hip_fp12_product_final_exp(soa, (size_t)world, gt_out, is_one, stream);
-  const int32_t rc2 = ws.release();
-  return rc != SYLOW_HIP_OK ? rc : rc2;
+  return host::finish(rc, ws);
 }
 
 // Aggregate verification over a batch sharded across the ranks of `comm` (NULL = this process alone): every rank reduces its shard to
@@ -110,8 +109,7 @@ static int32_t aggregate_verify(const uint64_t* pk_xy, const uint8_t* pk_inf, si
   } else if (rc == SYLOW_HIP_OK) {
     rc = sylow_hip_fp12_product_final_exp(mine, 1, gt_out, is_one, stream);
   }
-  const int32_t rc2 = ws.release();
-  return rc != SYLOW_HIP_OK ? rc : rc2;
+  return host::finish(rc, ws);
 }
 int32_t sylow_hip_bls_aggregate_verify_batch(const uint64_t* pk_xy, const uint8_t* pk_inf, size_t n_pk, const uint8_t* msgs, const uint64_t* msg_offsets,
                                              const uint64_t* sig_xy, const uint8_t* sig_inf, size_t n, void* comm, uint64_t* gt_out, uint8_t* is_one, void* stream) {

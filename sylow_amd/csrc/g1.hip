@@ -390,21 +390,18 @@ int32_t sylow_hip_g1_sum_batch(const uint64_t* p_xy, const uint8_t* p_inf, size_
   int32_t rc = ws.acquire(12 * (n ? n : 1) * sizeof(u64), (hipStream_t)stream);
   if (rc != SYLOW_HIP_OK) return rc;
   rc = g1h::sum(p_xy, p_inf, n, (uint64_t*)ws.p, out_xy, out_inf, 1, 0, 0, stream);
-  const int32_t r2 = ws.release();
-  return rc != SYLOW_HIP_OK ? rc : r2;
+  return host::finish(rc, ws);
 }
 int32_t sylow_hip_g1_scalar_mul_batch(const uint64_t* p_xy, const uint8_t* p_inf, const uint64_t* k, uint64_t* out_xy, uint8_t* out_inf, size_t n, void* stream) {
   ARGCHK(p_xy && k && out_xy && out_inf); if (!n) return SYLOW_HIP_OK;
   // single calls and small batches: eight lanes per product (sign_wide.hip) -- one product 1.0 -> ~0.35 ms
-  if (plkh::wide_batch_max() != 0 && n <= g1h::sign_wide_max()) return g1h::g1_scalar_mul_wide(p_xy, p_inf, k, out_xy, out_inf, n, stream);
+  if (plkh::small_routes_on() && n <= g1h::sign_wide_max()) return g1h::g1_scalar_mul_wide(p_xy, p_inf, k, out_xy, out_inf, n, stream);
   // window tables in a leased global block, one contiguous KB per lane (bn254_pairing.hpp: G1TableGlobal); a failed
   // lease keeps them in the stack frame
   host::Lease ws;
   uint8_t* tables = g1_window_tables(ws, n, stream);
   k_g1_scalar_mul<<<GRID(n)>>>(p_xy, p_inf, k, out_xy, out_inf, n, tables);
-  const hipError_t e = hipGetLastError();
-  const int32_t rc = ws.release();
-  return e != hipSuccess ? host::fail(e, "kernel launch") : rc;
+  return host::finish(SYLOW_HIP_OK, ws);
 }
 int32_t sylow_hip_g1_add_batch(const uint64_t* a_xy, const uint8_t* a_inf, const uint64_t* b_xy, const uint8_t* b_inf, uint64_t* out_xy, uint8_t* out_inf, size_t n, void* stream) {
   ARGCHK(a_xy && b_xy && out_xy && out_inf); if (!n) return SYLOW_HIP_OK;
@@ -465,7 +462,7 @@ int32_t sylow_hip_evm_ecadd_batch(const uint8_t* in, uint8_t* out, uint8_t* stat
 int32_t sylow_hip_evm_ecmul_batch(const uint8_t* in, uint8_t* out, uint8_t* status, size_t n, void* stream) {
   ARGCHK(in && out && status); if (!n) return SYLOW_HIP_OK;
   // single calls and small batches: eight lanes per product (sign_wide.hip) -- one ecMul 1.1 -> ~0.36 ms
-  if (plkh::wide_batch_max() != 0 && n <= g1h::sign_wide_max()) return g1h::evm_ecmul_wide(in, out, status, n, stream);
+  if (plkh::small_routes_on() && n <= g1h::sign_wide_max()) return g1h::evm_ecmul_wide(in, out, status, n, stream);
   k_evm_ecmul<<<GRID(n)>>>(in, out, status, n); LAUNCHED();
 }
 int32_t sylow_hip_g1_to_be_bytes_batch(const uint64_t* p_xy, const uint8_t* p_inf, uint8_t* out, size_t n, void* stream) {

@@ -31,7 +31,7 @@ constexpr size_t HASH_WIDE_MAX = 16384;       // 8 messages per wavefront: up to
 int32_t hash_to_g1_dst(const uint8_t* msgs, const uint64_t* msg_offsets, const DstPrime& dp, uint64_t* out_xy, uint8_t* out_inf, size_t n, int negate, void* stream) {
   if (!n) return SYLOW_HIP_OK;
   // single calls and small batches: eight lanes per message (sign_wide.hip) -- one hash ~1.0 -> 0.36 ms, the head of every single verification
-  if (plkh::wide_batch_max() != 0 && n <= HASH_WIDE_MAX) return hash_to_g1_wide(msgs, msg_offsets, dp, out_xy, out_inf, n, negate, stream);
+  if (plkh::small_routes_on() && n <= HASH_WIDE_MAX) return hash_to_g1_wide(msgs, msg_offsets, dp, out_xy, out_inf, n, negate, stream);
   k_hash_to_g1<<<GRID(n)>>>(msgs, msg_offsets, dp, out_xy, out_inf, nullptr, n, negate, nullptr); LAUNCHED();
 }
 // H(m_i) projective, straight into a summation tree's scratch array acc [12][n] (library DST): the shape of "sum of the hashes"

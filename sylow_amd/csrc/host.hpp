@@ -8,6 +8,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 
 extern thread_local char sylow_g_err[256];
 namespace host {
@@ -25,6 +26,14 @@ struct Lease {
   int32_t release();                 // records the block's completion event on the stream; idempotent
   ~Lease() { release(); }
 };
+// The one way to end an entry point that holds leases and has launched kernels.  Reads the sticky launch error and releases every lease, in
+// argument order, whatever the outcome; returns the first failure: an earlier `rc`, else the launch error, else the first failing release.
+template <class... L> int32_t finish(int32_t rc, L&... leases) {
+  const hipError_t e = hipGetLastError();
+  if (rc == SYLOW_HIP_OK && e != hipSuccess) rc = fail(e, "kernel launch");
+  for (const int32_t r : {leases.release()...}) if (rc == SYLOW_HIP_OK) rc = r;
+  return rc;
+}
 // per-device line tables of the G2 generator (G2Affine::precompute of the constant, pairing.rs:676-708), built on first use
 int32_t gen_lines29(const bn254::i32** out, hipStream_t st);    // carry-free lane-pair line table (plk_common.hpp: LINE_TABLE_WORDS)
 int32_t g1_gen_comb(const bn254::i32** out, hipStream_t st);     // fixed-base table of the G1 generator (g1.hip), built on first use
@@ -73,7 +82,6 @@ struct Fork {
 #define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return host::fail(e_, #x); } while (0)
 #define ARGCHK(c) do { if (!(c)) { snprintf(sylow_g_err, sizeof(sylow_g_err), "bad argument: %s", #c); return SYLOW_HIP_E_ARG; } } while (0)
 #define GRID(n) dim3((unsigned)(((n) + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, (hipStream_t)stream
-#define LAUNCH_RC() (hipGetLastError() == hipSuccess ? SYLOW_HIP_OK : host::fail(hipErrorLaunchFailure, "kernel launch"))
 #define LAUNCHED() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return host::fail(e_, "kernel launch"); return SYLOW_HIP_OK; } while (0)
 
 // ---- launchers exported between units (argument lists as the C entry points of include/sylow_hip.h) ----------------------
@@ -119,8 +127,9 @@ int32_t build_lines29(const uint64_t* q_xy, size_t n, size_t idx, bn254::i32* ta
 size_t line_table_bytes();                                                                             // plk_verify.hip
 size_t g2_comb_bytes();                                                                                // plk_group.hip
 int32_t build_g2_comb(bn254::i32* table, void* stream);                                                // plk_group.hip
-// plk_multi.hip: small batches on one wavefront per element (0 from wide_batch_max = route disabled)
-size_t wide_batch_max();
+// plk_multi.hip: small batches on one wavefront per element, and the eight-lane routes of sign_wide.hip (small_routes_on: SYLOW_HIP_OPT_WIDE_TAIL != 0)
+bool small_routes_on();
+size_t wide_batch_max();           // 0 when the small-batch routes are off
 size_t wide_verify_max();
 int32_t miller_raw_wide_batch(const uint64_t* p_xy, const uint64_t* q_xy, uint64_t* f_out, size_t n, void* stream);
 int32_t final_exp_wide_batch(const uint64_t* f, uint64_t* gt_out, size_t n, void* stream);

@@ -446,8 +446,7 @@ int32_t sylow_hip_g1_msm_tuned(const uint64_t* p_xy, const uint8_t* p_inf, const
       int32_t rc = ws.acquire(P.bytes, (hipStream_t)stream);
       if (rc != SYLOW_HIP_OK) return rc;
       rc = msmh::bucket_route(p_xy, p_inf, k, n, P, ws.p, out_xy, out_inf, stream);
-      const int32_t r2 = ws.release();
-      return rc != SYLOW_HIP_OK ? rc : r2;
+      return host::finish(rc, ws);
     }
   }
   // small n (or a budget below one chunk of the bucket route): a scalar multiplication per lane, then the batch sum
@@ -456,8 +455,7 @@ int32_t sylow_hip_g1_msm_tuned(const uint64_t* p_xy, const uint8_t* p_inf, const
     int32_t rc = ws.acquire(12 * sizeof(u64), (hipStream_t)stream);
     if (rc != SYLOW_HIP_OK) return rc;
     rc = g1h::sum_tree((uint64_t*)ws.p, 0, out_xy, out_inf, 1, 0, 0, stream);
-    const int32_t r2 = ws.release();
-    return rc != SYLOW_HIP_OK ? rc : r2;
+    return host::finish(rc, ws);
   }
   host::Lease ws;
   int32_t rc = ws.acquire(n * (8 * sizeof(u64) + 1) + 12 * n * sizeof(u64) + 256, (hipStream_t)stream);
@@ -467,8 +465,7 @@ int32_t sylow_hip_g1_msm_tuned(const uint64_t* p_xy, const uint8_t* p_inf, const
   uint8_t* inf = (uint8_t*)(xy + 8 * n);
   rc = sylow_hip_g1_scalar_mul_batch(p_xy, p_inf, k, xy, inf, n, stream);
   if (rc == SYLOW_HIP_OK) rc = g1h::sum(xy, inf, n, acc, out_xy, out_inf, 1, 0, 0, stream);
-  const int32_t r2 = ws.release();
-  return rc != SYLOW_HIP_OK ? rc : r2;
+  return host::finish(rc, ws);
 }
 int32_t sylow_hip_g1_msm(const uint64_t* p_xy, const uint8_t* p_inf, const uint64_t* k, size_t n, uint64_t* out_xy, uint8_t* out_inf, void* stream) {
   return sylow_hip_g1_msm_tuned(p_xy, p_inf, k, n, -1, -1, out_xy, out_inf, stream);

@@ -5,6 +5,8 @@
 #include "host.hpp"
 #include "bn254_pair29.hpp"
 
+#include <atomic>
+
 namespace plk {
 using namespace bn254;
 using namespace bn254::pl;
@@ -157,14 +159,44 @@ constexpr int LINE_TABLE_WORDS = LINE_TABLE_LINES * 36 + LINE_TABLE_LINES;
 
 namespace plkh {
 // plk_pairing.hip: fills `sg` for a staggered launch of `nblk` blocks, `full` of them whole chunks (count = 0: plain launch)
-// `resident` = blocks of the kernel one CU holds (hipOccupancyMaxActiveBlocksPerMultiprocessor, queried by the caller for ITS kernel)
+// `resident` = blocks of the kernel one CU holds (blocks_per_cu of the caller's kernel)
 hipError_t stagger_setup(plk::Stagger& sg, host::Lease& ws, size_t nblk, size_t full, hipStream_t st, int resident);
-template <class K> int blocks_per_cu(K kernel) {          // cached per kernel; 2 (what the kernels are built for) if the query fails
-  static const int v = [&] {
+// Blocks of kernel K one CU holds, cached per kernel and per device; 2 (what the kernels are built for) if the query fails
+template <auto K> int blocks_per_cu() {
+  auto query = [] {
     int b = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, kernel, BLOCK, 0) != hipSuccess || b < 1) { (void)hipGetLastError(); b = 2; }
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, K, BLOCK, 0) != hipSuccess || b < 1) { (void)hipGetLastError(); b = 2; }
     return b;
-  }();
+  };
+  static std::atomic<int> cache[64];          // 0: not asked yet
+  int d = 0;
+  if (hipGetDevice(&d) != hipSuccess || d < 0 || d >= 64) { (void)hipGetLastError(); return query(); }
+  int v = cache[d].load(std::memory_order_relaxed);
+  if (!v) cache[d].store(v = query(), std::memory_order_relaxed);
   return v;
+}
+// Whole rounds staggered on lane pairs + the remainder (tail_split) on quads beside them, for a batch of n elements on stream `st`.
+//   launch_main(m, blocks, sg): the lane-pair kernel (`resident` = its blocks_per_cu) on the first m elements, `blocks` blocks, on st
+//   launch_tail(m, tail, side): the quad route on elements [m, m + tail) on stream `side`; returns its status
+// The side stream forks behind everything st holds on entry; the park block is released right behind the main kernel (the tail does not read it).
+template <class Main, class Tail>
+int32_t launch_rounds_and_tail(size_t n, hipStream_t st, int resident, Main&& launch_main, Tail&& launch_tail) {
+  const size_t tail = tail_split(n), m = n - tail;
+  host::Fork fk;
+  hipStream_t side = tail ? fk.open(st) : st;
+  // staggered launch (see k_pairing): needs one full resident set of blocks made of whole chunks
+  const size_t nblk = (2 * m + BLOCK - 1) / BLOCK, full = (2 * m) / BLOCK;
+  plk::Stagger sg;
+  host::Lease park;
+  const hipError_t es = stagger_setup(sg, park, nblk, full, st, resident);
+  if (es != hipSuccess) return host::fail(es, "stagger flags");
+  launch_main(m, (unsigned)(nblk + sg.count), sg);
+  int32_t rc = host::finish(SYLOW_HIP_OK, park);
+  if (tail && rc == SYLOW_HIP_OK) {
+    rc = launch_tail(m, tail, side);
+    const int32_t joined = fk.join(st);
+    if (rc == SYLOW_HIP_OK) rc = joined;
+  }
+  return rc;
 }
 }  // namespace plkh

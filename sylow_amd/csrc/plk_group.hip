@@ -719,18 +719,14 @@ int32_t sylow_hip_g2_scalar_mul_batch(const uint64_t* p_xy, const uint8_t* p_inf
   host::Lease ws;
   uint8_t* tables = plkh_window_tables(ws, 2 * n, stream);
   plk::k_g2_scalar_mul<<<GRID(2 * n)>>>(p_xy, p_inf, k, out_xy, out_inf, n, tables);
-  const hipError_t e = hipGetLastError();
-  const int32_t rc = ws.release();
-  return e != hipSuccess ? host::fail(e, "kernel launch") : rc;
+  return host::finish(SYLOW_HIP_OK, ws);
 }
 int32_t sylow_hip_g2_scalar_mul_subgroup_batch(const uint64_t* p_xy, const uint8_t* p_inf, const uint64_t* k, uint64_t* out_xy, uint8_t* out_inf, size_t n, void* stream) {
   ARGCHK(p_xy && k && out_xy && out_inf); if (!n) return SYLOW_HIP_OK;
   host::Lease ws;
   uint8_t* tables = plkh_window_tables(ws, 2 * n, stream);
   plk::k_g2_scalar_mul_gls<<<GRID(2 * n)>>>(p_xy, p_inf, k, out_xy, out_inf, n, tables);
-  const hipError_t e = hipGetLastError();
-  const int32_t rc = ws.release();
-  return e != hipSuccess ? host::fail(e, "kernel launch") : rc;
+  return host::finish(SYLOW_HIP_OK, ws);
 }
 int32_t sylow_hip_g2_generator_mul_batch(const uint64_t* k, uint64_t* out_xy, uint8_t* out_inf, size_t n, void* stream) {
   ARGCHK(k && out_xy && out_inf); if (!n) return SYLOW_HIP_OK;
@@ -760,7 +756,7 @@ int32_t sylow_hip_g2_from_be_bytes_batch(const uint8_t* in, uint64_t* out_xy, ui
 int32_t sylow_hip_gt_pow_batch(const uint64_t* gt, const uint64_t* k, uint64_t* out, size_t n, void* stream) {
   ARGCHK(gt && k && out); if (!n) return SYLOW_HIP_OK;
   // single calls and small batches: one wavefront per element (one power 3.1 -> ~0.8 ms)
-  if (plkh::wide_batch_max() != 0 && n <= 2048) { plk::k_gt_pow_wide<<<dim3((unsigned)n), dim3(64), 0, (hipStream_t)stream>>>(gt, k, out, n); LAUNCHED(); }
+  if (plkh::small_routes_on() && n <= 2048) { plk::k_gt_pow_wide<<<dim3((unsigned)n), dim3(64), 0, (hipStream_t)stream>>>(gt, k, out, n); LAUNCHED(); }
   plk::k_gt_pow<<<GRID(2 * n)>>>(gt, k, out, n); LAUNCHED();
 }
 int32_t sylow_hip_g2_add_batch(const uint64_t* a_xy, const uint8_t* a_inf, const uint64_t* b_xy, const uint8_t* b_inf, uint64_t* out_xy, uint8_t* out_inf, size_t n, void* stream) {

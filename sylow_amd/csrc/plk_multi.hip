@@ -3,6 +3,7 @@
 #include "plk_common.hpp"
 
 #include <atomic>
+#include <type_traits>
 
 namespace plk {
 // ------------------------------------------------------------------ glued pairing ----------------------------------------
@@ -865,8 +866,6 @@ static bool use_tables(size_t n_jobs, size_t n_pairs) {
   const size_t need = table_bytes_per_job(table_slots(n_jobs, n_pairs)) * (n_jobs < 1024 ? n_jobs : 1024);
   return need <= table_budget();
 }
-// SYLOW_HIP_OPT_WIDE_TAIL = 0: the single final exponentiation of the one-boolean shapes on one lane pair (default: on the whole wavefront)
-static int wide_tail() { return host::option(SYLOW_HIP_OPT_WIDE_TAIL) == 0 ? 0 : 1; }
 // SYLOW_HIP_OPT_WIDE_PACK = t: the small-batch kernels put two elements on a wavefront above t elements (0 = never, 1 = always: A/B runs and
 // tests/test_gpu_routes.py).  Default: the number of compute units -- one wavefront per CU is the fastest shape (1.72 ms per pairing up
 // to 256), a second wavefront on a CU already costs more (1.9 ms) than a wavefront of two elements (1.76 ms), and from there on the
@@ -878,19 +877,22 @@ static size_t wide_pack() {
   return (size_t)(cus ? cus : 256);
 }
 // Two elements per wavefront (16 lane pairs each) cost a second product pass in the dense Fp12 products of the final exponentiation only.
+static bool packed(size_t units) { return wide_pack() && units > wide_pack(); }
+// The one-wavefront kernels come in two layouts, one or two elements per wavefront (the kernels' template argument): launch(epw, grid) gets the
+// layout as a std::integral_constant and the grid of 64-lane blocks that covers `units` elements in it
+template <class Launch> static void launch_wide(bool two, size_t units, Launch&& launch) {
+  if (two) launch(std::integral_constant<int, 2>{}, dim3((unsigned)((units + 1) / 2)));
+  else launch(std::integral_constant<int, 1>{}, dim3((unsigned)units));
+}
 static void launch_miller_wide(const u64* pa, const uint8_t* pa_inf, const u64* qa, const uint8_t* qa_inf, u64* fa,
                                const u64* pb, const uint8_t* pb_inf, const u64* qb, const uint8_t* qb_inf, u64* fb, size_t n, hipStream_t st, int bcast_b = 0) {
   const size_t units = pb ? 2 * n : n;
-  if (wide_pack() && units > wide_pack())
-    plk::k_miller_wide_batch<2><<<dim3((unsigned)((units + 1) / 2)), dim3(64), 0, st>>>(pa, pa_inf, qa, qa_inf, fa, pb, pb_inf, qb, qb_inf, fb, n, bcast_b);
-  else
-    plk::k_miller_wide_batch<1><<<dim3((unsigned)units), dim3(64), 0, st>>>(pa, pa_inf, qa, qa_inf, fa, pb, pb_inf, qb, qb_inf, fb, n, bcast_b);
+  launch_wide(packed(units), units, [&](auto epw, dim3 grid) {
+    plk::k_miller_wide_batch<decltype(epw)::value><<<grid, dim3(64), 0, st>>>(pa, pa_inf, qa, qa_inf, fa, pb, pb_inf, qb, qb_inf, fb, n, bcast_b);
+  });
 }
 static void launch_final_exp_wide(const u64* fa, const u64* fb, size_t n, u64* gout, uint8_t* is_one, hipStream_t st) {
-  if (wide_pack() && n > wide_pack())
-    plk::k_final_exp_wide_batch<2><<<dim3((unsigned)((n + 1) / 2)), dim3(64), 0, st>>>(fa, fb, n, gout, is_one);
-  else
-    plk::k_final_exp_wide_batch<1><<<dim3((unsigned)n), dim3(64), 0, st>>>(fa, fb, n, gout, is_one);
+  launch_wide(packed(n), n, [&](auto epw, dim3 grid) { plk::k_final_exp_wide_batch<decltype(epw)::value><<<grid, dim3(64), 0, st>>>(fa, fb, n, gout, is_one); });
 }
 // eq_i = [ a_i == b_i ] for Gt values (SoA stride n, canonical limbs)
 __global__ void __launch_bounds__(BLOCK) k_gt_eq_flags(const u64* a, const u64* b, size_t n, uint8_t* eq) {
@@ -905,15 +907,18 @@ namespace plkh {
 // Small batches on one wavefront per one or two elements (k_miller_wide_batch / k_final_exp_wide_batch): up to this many pairings the
 // latency route beats the one-lane-pair kernels (2048 resident wavefronts of two elements each, and one more half-round; docs/DESIGN_LOG.md R5-8.3)
 // SYLOW_HIP_OPT_WIDE_MAX / _WIDE_VERIFY_MAX move the two caps (crossover runs, tools/dbg/time_small.py)
+// SYLOW_HIP_OPT_WIDE_TAIL = 0 switches every small-batch route off: the one-wavefront routes below (both caps 0), the single final exponentiation
+// of the one-boolean shapes (then on one lane pair), and the eight-lane routes of sign_wide.hip
+bool small_routes_on() { return host::option(SYLOW_HIP_OPT_WIDE_TAIL) != 0; }
 size_t wide_batch_max() {
   const size_t v = (size_t)host::option_or(SYLOW_HIP_OPT_WIDE_MAX, 0);
-  return !wide_tail() ? 0 : v ? v : wide_pack() ? 6144 : 2048;      // 6144 pairings: three half-rounds of wavefronts, 3.6 against 4.2 ms; 7168: 4.6
+  return !small_routes_on() ? 0 : v ? v : wide_pack() ? 6144 : 2048;      // 6144 pairings: three half-rounds of wavefronts, 3.6 against 4.2 ms; 7168: 4.6
 }
 // ... and up to this many verifications (2 n Miller loops + n final exponentiations; two rounds of wavefronts at the cap: 4096
 // verifications 3.8 against 5.4 ms on the lane-pair kernel, 6144: 5.7 against 5.4)
 size_t wide_verify_max() {
   const size_t v = (size_t)host::option_or(SYLOW_HIP_OPT_WIDE_VERIFY_MAX, 0);
-  return !wide_tail() ? 0 : v ? v : wide_pack() ? 4096 : 1024;
+  return !small_routes_on() ? 0 : v ? v : wide_pack() ? 4096 : 1024;
 }
 // pairing(P_i, Q_i), i < n: raw values through `scratch` (48 n words), Gt values to gt_out (SoA stride n)
 int32_t pairing_wide_batch(const uint64_t* p_xy, const uint8_t* p_inf, const uint64_t* q_xy, const uint8_t* q_inf, uint64_t* scratch, uint64_t* gt_out, size_t n, void* stream) {
@@ -934,16 +939,14 @@ int32_t verify_wide_batch(const uint64_t* pk_xy, const uint8_t* pk_inf, const ui
 // the reference's raw Miller values (no identity flags: the raw entry point has none), i < n <= wide_batch_max()
 int32_t miller_raw_wide_batch(const uint64_t* p_xy, const uint64_t* q_xy, uint64_t* f_out, size_t n, void* stream) {
   hipStream_t st = (hipStream_t)stream;
-  if (wide_pack() && n > wide_pack())
-    plk::k_miller_wide_batch<2, false><<<dim3((unsigned)((n + 1) / 2)), dim3(64), 0, st>>>(p_xy, nullptr, q_xy, nullptr, f_out, nullptr, nullptr, nullptr, nullptr, nullptr, n);
-  else
-    plk::k_miller_wide_batch<1, false><<<dim3((unsigned)n), dim3(64), 0, st>>>(p_xy, nullptr, q_xy, nullptr, f_out, nullptr, nullptr, nullptr, nullptr, nullptr, n);
+  launch_wide(packed(n), n, [&](auto epw, dim3 grid) {
+    plk::k_miller_wide_batch<decltype(epw)::value, false><<<grid, dim3(64), 0, st>>>(p_xy, nullptr, q_xy, nullptr, f_out, nullptr, nullptr, nullptr, nullptr, nullptr, n);
+  });
   LAUNCHED();
 }
 int32_t fp12_op_wide(int epw, int32_t off, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n, void* stream) {
   hipStream_t st = (hipStream_t)stream;
-  if (epw == 2) plk::k_wide_op<2><<<dim3((unsigned)((n + 1) / 2)), dim3(64), 0, st>>>(off, a, b, out, n);
-  else plk::k_wide_op<1><<<dim3((unsigned)n), dim3(64), 0, st>>>(off, a, b, out, n);
+  launch_wide(epw == 2, n, [&](auto e, dim3 grid) { plk::k_wide_op<decltype(e)::value><<<grid, dim3(64), 0, st>>>(off, a, b, out, n); });
   LAUNCHED();
 }
 // final_exponentiation(f_i), i < n <= wide_batch_max()
@@ -1008,9 +1011,7 @@ static int32_t multi_pairing_tables(const uint64_t* p_xy, const uint8_t* p_inf, 
       plk::k_final_exp_jobs<<<GRID(2 * jb)>>>(raw, jb, job0, jb, n_jobs, gt_out, is_one);
     }
   }
-  const hipError_t e = hipGetLastError();
-  rc = ws.release();
-  return e != hipSuccess ? host::fail(e, "kernel launch") : rc;
+  return host::finish(SYLOW_HIP_OK, ws);
 }
 
 extern "C" {
@@ -1064,7 +1065,7 @@ static int32_t miller_product_tree(const uint64_t* p_xy, const uint8_t* p_inf, c
   if (rc != SYLOW_HIP_OK) return rc;
   u64 *off = (u64*)ws.p, *bufa = off + n_off, *bufb = bufa + n_a;
   // ONE pair (the collapsed halves of the aggregate verifiers): pure latency on one lane pair -- the whole wavefront takes it
-  if (n_pairs == 1 && skip_infinity && wide_tail()) {
+  if (n_pairs == 1 && skip_infinity && plkh::small_routes_on()) {
     plk::k_miller_single_wide<<<1, 64, 0, st>>>(p_xy, p_inf, q_xy, q_inf, 1, range, bufa);
     *result = bufa;
     return SYLOW_HIP_OK;
@@ -1099,11 +1100,6 @@ static int32_t miller_product_tree(const uint64_t* p_xy, const uint8_t* p_inf, c
   *result = cur;
   return SYLOW_HIP_OK;
 }
-static int32_t finish(host::Lease& ws) {
-  const hipError_t e = hipGetLastError();
-  const int32_t rc = ws.release();
-  return e != hipSuccess ? host::fail(e, "kernel launch") : rc;
-}
 // FEW jobs with few pairs (a single ecPairing call, a single Groth16-style check, a handful of them): one wavefront per pair for the
 // Miller loops, one per job for the product of its pairs and the final exponentiation -- 1.1 + 1.3 ms of latency whatever the job size,
 // against a whole glued loop and a final exponentiation on one lane pair per job (one job of 4 pairs: 7.9 ms).  The jobs' pair ranges
@@ -1120,23 +1116,23 @@ static int32_t single_job_product(const uint64_t* p_xy, const uint8_t* p_inf, co
     u64* prod = nullptr;
     int32_t rc = miller_product_tree(p_xy, p_inf, q_xy, q_inf, n_pairs, 1, ws, &prod, stream, pair_offsets);
     if (rc != SYLOW_HIP_OK) return rc;
-    plk::k_final_exp_flag<<<1, 64, 0, st>>>(prod, 1, gt_out, is_one, wide_tail());
-    return finish(ws);
+    plk::k_final_exp_flag<<<1, 64, 0, st>>>(prod, 1, gt_out, is_one, plkh::small_routes_on());
+    return host::finish(SYLOW_HIP_OK, ws);
   }
   int32_t rc = ws.acquire(48 * n_pairs * sizeof(u64), st);
   if (rc != SYLOW_HIP_OK) return rc;
   u64* raw = (u64*)ws.p;
   launch_miller_wide(p_xy, p_inf, q_xy, q_inf, raw, nullptr, nullptr, nullptr, nullptr, nullptr, n_pairs, st);
   plk::k_final_exp_wide_jobs<<<dim3((unsigned)n_jobs), dim3(64), 0, st>>>(raw, n_pairs, pair_offsets, n_jobs, gt_out, is_one);
-  return finish(ws);
+  return host::finish(SYLOW_HIP_OK, ws);
 }
 int32_t sylow_hip_pairing_product_batch(const uint64_t* p_xy, const uint8_t* p_inf, const uint64_t* q_xy, const uint8_t* q_inf,
                                         size_t n_pairs, int32_t skip_infinity, uint64_t* gt_out, uint8_t* is_one, void* stream) {
   ARGCHK((gt_out || is_one) && (n_pairs == 0 || (p_xy && q_xy)));
   hipStream_t st = (hipStream_t)stream;
-  if (n_pairs == 0) { plk::k_final_exp_flag<<<1, 64, 0, st>>>(nullptr, 0, gt_out, is_one, wide_tail()); LAUNCHED(); }
+  if (n_pairs == 0) { plk::k_final_exp_flag<<<1, 64, 0, st>>>(nullptr, 0, gt_out, is_one, plkh::small_routes_on()); LAUNCHED(); }
   host::Lease ws;
-  if (n_pairs >= 2 && n_pairs <= 256 && skip_infinity && plkh::wide_batch_max() != 0) {
+  if (n_pairs >= 2 && n_pairs <= 256 && skip_infinity && plkh::small_routes_on()) {
     // a short product: one wavefront per Miller loop, then one wavefront multiplies the values and exponentiates (2.0 - 3.0 ms against 3.3)
     int32_t rc = ws.acquire((48 * n_pairs + 2) * sizeof(u64), st);
     if (rc != SYLOW_HIP_OK) return rc;
@@ -1144,13 +1140,13 @@ int32_t sylow_hip_pairing_product_batch(const uint64_t* p_xy, const uint8_t* p_i
     plk::k_chunk_offsets<<<1, 64, 0, st>>>(off, 1, n_pairs, n_pairs, nullptr);
     launch_miller_wide(p_xy, p_inf, q_xy, q_inf, raw, nullptr, nullptr, nullptr, nullptr, nullptr, n_pairs, st);
     plk::k_final_exp_wide_jobs<<<1, 64, 0, st>>>(raw, n_pairs, off, 1, gt_out, is_one);
-    return finish(ws);
+    return host::finish(SYLOW_HIP_OK, ws);
   }
   u64* prod = nullptr;
   int32_t rc = miller_product_tree(p_xy, p_inf, q_xy, q_inf, n_pairs, skip_infinity, ws, &prod, stream);
   if (rc != SYLOW_HIP_OK) return rc;
-  plk::k_final_exp_flag<<<1, 64, 0, st>>>(prod, 1, gt_out, is_one, wide_tail());
-  return finish(ws);
+  plk::k_final_exp_flag<<<1, 64, 0, st>>>(prod, 1, gt_out, is_one, plkh::small_routes_on());
+  return host::finish(SYLOW_HIP_OK, ws);
 }
 int32_t sylow_hip_pairing_product_partial_batch(const uint64_t* p_xy, const uint8_t* p_inf, const uint64_t* q_xy, const uint8_t* q_inf,
                                                 size_t n_pairs, int32_t skip_infinity, uint64_t* f_out, void* stream) {
@@ -1161,9 +1157,8 @@ int32_t sylow_hip_pairing_product_partial_batch(const uint64_t* p_xy, const uint
   u64* prod = nullptr;
   int32_t rc = miller_product_tree(p_xy, p_inf, q_xy, q_inf, n_pairs, skip_infinity, ws, &prod, stream);
   if (rc != SYLOW_HIP_OK) return rc;
-  hipError_t e = hipMemcpyAsync(f_out, prod, 48 * sizeof(u64), hipMemcpyDeviceToDevice, st);
-  rc = finish(ws);
-  return e != hipSuccess ? host::fail(e, "hipMemcpyAsync(partial product)") : rc;
+  const hipError_t e = hipMemcpyAsync(f_out, prod, 48 * sizeof(u64), hipMemcpyDeviceToDevice, st);
+  return host::finish(e != hipSuccess ? host::fail(e, "hipMemcpyAsync(partial product)") : SYLOW_HIP_OK, ws);
 }
 // Aggregate verification (examples/verify_multiple_messages_same_signer.rs:41-60, threshold_signing.rs:92-121): the reference
 // glues the 2n pairs (sig_i, G2gen), (-H(m_i), pk_i) into one product and compares it with the identity.  Bilinearity collapses the
@@ -1227,15 +1222,11 @@ static int32_t aggregate_partial(const uint64_t* pk_xy, const uint8_t* pk_inf, s
       rc = miller_product_tree(pa2, p2inf, qa2, q2inf, 1, 1, wa, &pa, stream);
     }
   }
-  const int32_t rj = fork.join(st);
-  if (rc == SYLOW_HIP_OK) rc = rj;
+  const int32_t joined = fork.join(st);
+  if (rc == SYLOW_HIP_OK) rc = joined;
   if (rc == SYLOW_HIP_OK) plk::k_fp12_mul_pair<<<1, 64, 0, st>>>(pa, pb, f_out);
-  const hipError_t e = hipGetLastError();
   if (wb.slot >= 0) wb.st = st;      // the caller's stream has joined the side stream and still reads the block: its release is ordered there
-  const int32_t r1 = wa.release(), r2 = wb.release(), r3 = ws.release();
-  if (rc != SYLOW_HIP_OK) return rc;
-  if (e != hipSuccess) return host::fail(e, "kernel launch");
-  return r1 != SYLOW_HIP_OK ? r1 : r2 != SYLOW_HIP_OK ? r2 : r3;
+  return host::finish(rc, wa, wb, ws);
 }
 int32_t sylow_hip_bls_aggregate_partial_batch(const uint64_t* pk_xy, const uint8_t* pk_inf, size_t n_pk, const uint8_t* msgs, const uint64_t* msg_offsets,
                                               const uint64_t* sig_xy, const uint8_t* sig_inf, size_t n, uint64_t* f_out, void* stream) {
@@ -1249,7 +1240,7 @@ int32_t sylow_hip_bls_weighted_partial_batch(const uint64_t* pk_xy, const uint8_
 int32_t sylow_hip_fp12_product_final_exp(const uint64_t* parts, size_t k, uint64_t* gt_out, uint8_t* is_one, void* stream) {
   ARGCHK((gt_out || is_one) && (parts || !k));
   hipStream_t st = (hipStream_t)stream;
-  if (k <= 1) { plk::k_final_exp_flag<<<1, 64, 0, st>>>(parts, k, gt_out, is_one, wide_tail()); LAUNCHED(); }
+  if (k <= 1) { plk::k_final_exp_flag<<<1, 64, 0, st>>>(parts, k, gt_out, is_one, plkh::small_routes_on()); LAUNCHED(); }
   host::Lease ws;
   const size_t n_a = 48 * ((k + 1) / 2), n_b = 48 * ((k + 3) / 4);
   int32_t rc = ws.acquire((n_a + n_b) * sizeof(u64), st);
@@ -1269,8 +1260,8 @@ int32_t sylow_hip_fp12_product_final_exp(const uint64_t* parts, size_t k, uint64
     plk::k_fp12_tree_tail<<<1, BLOCK, 0, st>>>((u64*)cur, m, m, nxt);
     cur = nxt;
   }
-  plk::k_final_exp_flag<<<1, 64, 0, st>>>(cur, 1, gt_out, is_one, wide_tail());
-  return finish(ws);
+  plk::k_final_exp_flag<<<1, 64, 0, st>>>(cur, 1, gt_out, is_one, plkh::small_routes_on());
+  return host::finish(SYLOW_HIP_OK, ws);
 }
 
 int32_t sylow_hip_evm_ecpairing_batch(const uint8_t* in, const uint64_t* pair_offsets, size_t n_jobs, size_t n_pairs,
@@ -1298,7 +1289,6 @@ int32_t sylow_hip_evm_ecpairing_batch(const uint8_t* in, const uint64_t* pair_of
     else plk::k_multi_pairing<plk::KMAXW><<<GRID(2 * n_jobs)>>>(pxy, pinf, qxy, qinf, pair_offsets, n_jobs, n_pairs, /*skip_infinity=*/1, nullptr, isone, 0);
   }
   if (rc == SYLOW_HIP_OK) k_evm_pair_finalize<<<GRID(n_jobs)>>>(pst, pair_offsets, n_jobs, isone, result, status);
-  const int32_t rc2 = finish(lease);
-  return rc != SYLOW_HIP_OK ? rc : rc2;
+  return host::finish(rc, lease);
 }
 }  // extern "C"

@@ -108,7 +108,7 @@ static int stagger_mode() { return (int)host::option_or(SYLOW_HIP_OPT_STAGGER, 1
 // Fills `sg` for a staggered launch of `nblk` blocks (`full` of them whole chunks) when the batch is at least two rounds of the resident
 // blocks (2 per CU): measured on k_pairing, 2^17 elements 14.46 -> 14.00 ms, 2^18 27.86 -> 27.33, 2^19 54.95 -> 54.3, 2^20 108.5 -> 108.0;
 // exactly one round (2^16) LOSES 2 % (the parked half runs its final exponentiations beside the other half's), so smaller batches stay plain.
-// Leaves sg.count = 0 (plain launch) when the lease fails.  The caller releases `ws` after the launch.
+// Leaves sg.count = 0 (plain launch) when the lease fails.  The caller (launch_rounds_and_tail, plk_common.hpp) releases `ws` after the launch.
 hipError_t stagger_setup(plk::Stagger& sg, host::Lease& ws, size_t nblk, size_t full, hipStream_t st, int resident) {
   sg = plk::Stagger{0, 0, (unsigned)nblk, stagger_mode() == 2 ? 1u : 0u, nullptr, nullptr, host::clock_probe()};
   // the first resident set is `resident` blocks per CU (2 for these kernels: asked of the occupancy API, not assumed); its second half parks
@@ -140,36 +140,22 @@ int32_t sylow_hip_pairing_batch(const uint64_t* p_xy, const uint8_t* p_inf, cons
   ARGCHK(p_xy && q_xy && gt_out); if (!n) return SYLOW_HIP_OK;
   // a few pairings are pure latency on one lane pair each: a wavefront per pairing instead; same Gt, an identity on either side gives the
   // identity of Gt either way (pairing.rs:876-886)
+  hipStream_t st = (hipStream_t)stream;
   if (n <= plkh::wide_batch_max()) {      // small batches: one wavefront per pairing (2.3 ms against 5.4 ms on one lane pair each)
     host::Lease ws;
-    int32_t rc = ws.acquire(48 * n * sizeof(u64), (hipStream_t)stream);
+    int32_t rc = ws.acquire(48 * n * sizeof(u64), st);
     if (rc != SYLOW_HIP_OK) return rc;
-    rc = plkh::pairing_wide_batch(p_xy, p_inf, q_xy, q_inf, (u64*)ws.p, gt_out, n, stream);
-    const int32_t r2 = ws.release();
-    return rc != SYLOW_HIP_OK ? rc : r2;
+    return host::finish(plkh::pairing_wide_batch(p_xy, p_inf, q_xy, q_inf, (u64*)ws.p, gt_out, n, stream), ws);
   }
   // mid-size batches (up to one wavefront per SIMD of quads): a lane QUAD per element, 1.5 x the speed of a lone lane pair (plk_quad.hip)
   if (n <= plkh::quad_batch_max()) return plkh::pairing_quad_range(p_xy, p_inf, q_xy, q_inf, gt_out, n, n, stream);
   // A batch of k whole rounds of one wavefront per SIMD plus a short tail would leave the tail's few blocks as second wavefronts of their SIMDs
   // for a whole extra pairing time (32 768 pairings 4.3 ms, 33 000: 7.3 ms): the tail takes the quad route on a side stream BESIDE the rounds
-  hipStream_t st = (hipStream_t)stream;
-  const size_t tail = plkh::tail_split(n), m = n - tail;
-  host::Fork fk;
-  hipStream_t side = tail ? fk.open(st) : st;
-  // staggered launch (see k_pairing): needs one full resident set of blocks (2 per CU) made of whole chunks
-  const size_t nblk = (2 * m + BLOCK - 1) / BLOCK, full = (2 * m) / BLOCK;
-  plk::Stagger sg;
-  host::Lease ws;
-  HIPCHK(plkh::stagger_setup(sg, ws, nblk, full, st, plkh::blocks_per_cu(plk::k_pairing)));
-  plk::k_pairing<<<dim3((unsigned)(nblk + sg.count)), dim3(BLOCK), 0, st>>>(p_xy, p_inf, q_xy, q_inf, gt_out, n, m, sg);
-  const hipError_t e = hipGetLastError();
-  int32_t rc = ws.release();
-  if (tail && e == hipSuccess && rc == SYLOW_HIP_OK) {
-    rc = plkh::pairing_quad_range(p_xy + m, p_inf ? p_inf + m : nullptr, q_xy + m, q_inf ? q_inf + m : nullptr, gt_out + m, n, tail, side);
-    const int32_t rj = fk.join(st);
-    if (rc == SYLOW_HIP_OK) rc = rj;
-  }
-  return e != hipSuccess ? host::fail(e, "kernel launch") : rc;
+  return plkh::launch_rounds_and_tail(n, st, plkh::blocks_per_cu<plk::k_pairing>(),
+    [&](size_t m, unsigned blocks, const plk::Stagger& sg) { plk::k_pairing<<<dim3(blocks), dim3(BLOCK), 0, st>>>(p_xy, p_inf, q_xy, q_inf, gt_out, n, m, sg); },
+    [&](size_t m, size_t tail, hipStream_t side) {
+      return plkh::pairing_quad_range(p_xy + m, p_inf ? p_inf + m : nullptr, q_xy + m, q_inf ? q_inf + m : nullptr, gt_out + m, n, tail, side);
+    });
 }
 // test hook: raw Fp12 selector.  0..11: the one-element-per-lane layer (tower.hip: 8 product on the carry-free core, 9 cyclotomic square on
 // it, 10 / 11 exp_by_neg_z on the carry-free / saturated core); 16..31: the lane-pair Fp12 layer and Miller steps (plk::k_w12_op);

@@ -153,42 +153,41 @@ int32_t build_lines29(const uint64_t* q_xy, size_t n, size_t idx, bn254::i32* ta
 template <bool PK_TABLE>
 static int32_t launch_fused(const uint64_t* pk_xy, const uint8_t* pk_inf, const bn254::i32* pk_table, const uint8_t* msgs, const uint64_t* msg_offsets,
                             const DstPrime& dp, const uint64_t* sig_xy, const uint8_t* sig_inf, const bn254::i32* gen, uint8_t* ok, size_t n, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
   host::Lease ws;
-  int32_t rc = ws.acquire(8 * n * sizeof(u64) + n, (hipStream_t)stream);
+  int32_t rc = ws.acquire(8 * n * sizeof(u64) + n, st);
   if (rc != SYLOW_HIP_OK) return rc;
   u64* hneg = (u64*)ws.p;
   uint8_t* hinf = (uint8_t*)(hneg + 8 * n);
   rc = g1h::hash_to_g1(msgs, msg_offsets, hneg, hinf, n, /*negate=*/1, stream);
-  if (rc == SYLOW_HIP_OK && n <= plkh::quad_batch_max()) {      // mid-size batches: a lane quad per element (plk_quad.hip)
+  if (rc == SYLOW_HIP_OK && n <= plkh::quad_batch_max())        // mid-size batches: a lane quad per element (plk_quad.hip)
     rc = plkh::verify_fused_quad(PK_TABLE ? 1 : 0, pk_xy, pk_inf, pk_table, hneg, hinf, sig_xy, sig_inf, gen, ok, n, n, stream);
-    const int32_t r2 = ws.release();
-    return rc != SYLOW_HIP_OK ? rc : r2;
-  }
-  // whole rounds + a short tail: the tail on quads on a side stream beside the rounds (sylow_hip_pairing_batch, plk_pairing.hip); the side stream
-  // forks here, behind the hashing kernel
-  const size_t tail = rc == SYLOW_HIP_OK ? plkh::tail_split(n) : 0, m = n - tail;
-  host::Fork fk;
-  hipStream_t side = tail ? fk.open((hipStream_t)stream) : (hipStream_t)stream;
-  plk::Stagger sg{0, 0, 0, 0, nullptr, nullptr, nullptr};
-  host::Lease wp;
-  const size_t nblk = (2 * m + BLOCK - 1) / BLOCK, full = (2 * m) / BLOCK;
-  if (rc == SYLOW_HIP_OK) {
-    const hipError_t es = plkh::stagger_setup(sg, wp, nblk, full, (hipStream_t)stream, plkh::blocks_per_cu(plk::k_bls_verify_fused<PK_TABLE>));
-    if (es != hipSuccess) rc = host::fail(es, "stagger flags");
-  }
-  if (rc == SYLOW_HIP_OK)
-    plk::k_bls_verify_fused<PK_TABLE><<<dim3((unsigned)(nblk + sg.count)), dim3(BLOCK), 0, (hipStream_t)stream>>>(pk_xy, pk_inf, pk_table, hneg, hinf, sig_xy, sig_inf, gen, ok, n, m, sg);
-  hipError_t e = hipGetLastError();
-  if (tail && rc == SYLOW_HIP_OK && e == hipSuccess) {
-    rc = plkh::verify_fused_quad(PK_TABLE ? 1 : 0, (PK_TABLE || !pk_xy) ? pk_xy : pk_xy + m, (PK_TABLE || !pk_inf) ? pk_inf : pk_inf + m, pk_table, hneg + m, hinf + m,
-                                 sig_xy + m, sig_inf ? sig_inf + m : nullptr, gen, ok + m, n, tail, side);
-    const int32_t rj = fk.join((hipStream_t)stream);
-    if (rc == SYLOW_HIP_OK) rc = rj;
-  }
-  const int32_t r3 = wp.release();
-  const int32_t r2 = ws.release();
+  else if (rc == SYLOW_HIP_OK)
+    // whole rounds + a short tail: the tail on quads on a side stream beside the rounds (sylow_hip_pairing_batch, plk_pairing.hip); the side stream
+    // forks here, behind the hashing kernel.  The tail's arrays start at element m; a table key or a NULL array is not advanced.
+    rc = plkh::launch_rounds_and_tail(n, st, plkh::blocks_per_cu<plk::k_bls_verify_fused<PK_TABLE>>(),
+      [&](size_t m, unsigned blocks, const plk::Stagger& sg) {
+        plk::k_bls_verify_fused<PK_TABLE><<<dim3(blocks), dim3(BLOCK), 0, st>>>(pk_xy, pk_inf, pk_table, hneg, hinf, sig_xy, sig_inf, gen, ok, n, m, sg);
+      },
+      [&](size_t m, size_t tail, hipStream_t side) {
+        return plkh::verify_fused_quad(PK_TABLE ? 1 : 0, (PK_TABLE || !pk_xy) ? pk_xy : pk_xy + m, (PK_TABLE || !pk_inf) ? pk_inf : pk_inf + m, pk_table, hneg + m, hinf + m,
+                                       sig_xy + m, sig_inf ? sig_inf + m : nullptr, gen, ok + m, n, tail, side);
+      });
+  return host::finish(rc, ws);
+}
+// Small batches of the per-signature checks: H(m_i) (or -H(m_i)) into a leased block, then check(h, h_inf, scratch): one of plk_multi.hip's
+// one-wavefront-per-element routines, `words` words of scratch per element
+template <class Check>
+static int32_t verify_small(const uint8_t* msgs, const uint64_t* msg_offsets, size_t n, size_t words, int negate, void* stream, Check&& check) {
+  host::Lease ws;
+  int32_t rc = ws.acquire((8 + words) * n * sizeof(u64) + n, (hipStream_t)stream);
   if (rc != SYLOW_HIP_OK) return rc;
-  return e != hipSuccess ? host::fail(e, "kernel launch") : (r2 != SYLOW_HIP_OK ? r2 : r3);
+  u64* h = (u64*)ws.p;
+  u64* scratch = h + 8 * n;
+  uint8_t* hinf = (uint8_t*)(scratch + words * n);
+  rc = g1h::hash_to_g1(msgs, msg_offsets, h, hinf, n, negate, stream);
+  if (rc == SYLOW_HIP_OK) rc = check(h, hinf, scratch);
+  return host::finish(rc, ws);
 }
 
 extern "C" {
@@ -201,18 +200,10 @@ static int32_t verify_one_final_exp(const uint64_t* pk_xy, const uint8_t* pk_inf
   ARGCHK(pk_xy && msgs && msg_offsets && sig_xy && ok); if (!n) return SYLOW_HIP_OK;
   // a few verifications are pure latency on one lane pair each (6.8 ms): the same product e(sig, G2gen) e(-H, pk) with the same reading of
   // identities on one wavefront per Miller loop and per final exponentiation (3 ms)
-  if (n <= plkh::wide_verify_max()) {  // small batches: -H(m_i), then a wavefront per Miller loop and per final exponentiation
-    host::Lease ws;
-    int32_t rc = ws.acquire((8 + 96) * n * sizeof(u64) + n, (hipStream_t)stream);
-    if (rc != SYLOW_HIP_OK) return rc;
-    u64* hneg = (u64*)ws.p;
-    u64* scratch = hneg + 8 * n;
-    uint8_t* hinf = (uint8_t*)(scratch + 96 * n);
-    rc = g1h::hash_to_g1(msgs, msg_offsets, hneg, hinf, n, /*negate=*/1, stream);
-    if (rc == SYLOW_HIP_OK) rc = plkh::verify_wide_batch(pk_xy, pk_inf, hneg, hinf, sig_xy, sig_inf, scratch, ok, n, stream);
-    const int32_t r2 = ws.release();
-    return rc != SYLOW_HIP_OK ? rc : r2;
-  }
+  if (n <= plkh::wide_verify_max())    // small batches: -H(m_i), then a wavefront per Miller loop and per final exponentiation
+    return verify_small(msgs, msg_offsets, n, 96, /*negate=*/1, stream, [&](const u64* hneg, const uint8_t* hinf, u64* scratch) {
+      return plkh::verify_wide_batch(pk_xy, pk_inf, hneg, hinf, sig_xy, sig_inf, scratch, ok, n, stream);
+    });
   DstPrime dp; host::dst_arg(dp, nullptr, 0);
   const bn254::i32* gen = nullptr;
   int32_t rc = host::gen_lines29(&gen, (hipStream_t)stream);
@@ -230,18 +221,10 @@ int32_t sylow_hip_bls_verify_fused_batch(const uint64_t* pk_xy, const uint8_t* p
 int32_t sylow_hip_bls_verify_two_pairings_batch(const uint64_t* pk_xy, const uint8_t* pk_inf, const uint8_t* msgs, const uint64_t* msg_offsets,
                                                 const uint64_t* sig_xy, const uint8_t* sig_inf, uint8_t* ok, size_t n, void* stream) {
   ARGCHK(pk_xy && msgs && msg_offsets && sig_xy && ok); if (!n) return SYLOW_HIP_OK;
-  if (n <= plkh::wide_verify_max()) {  // small batches: H(m_i), a wavefront per one or two Miller loops / final exponentiations, Gt values compared
-    host::Lease ws;
-    int32_t rc = ws.acquire((8 + 192) * n * sizeof(u64) + n, (hipStream_t)stream);
-    if (rc != SYLOW_HIP_OK) return rc;
-    u64* h = (u64*)ws.p;
-    u64* scratch = h + 8 * n;
-    uint8_t* hinf = (uint8_t*)(scratch + 192 * n);
-    rc = g1h::hash_to_g1(msgs, msg_offsets, h, hinf, n, /*negate=*/0, stream);
-    if (rc == SYLOW_HIP_OK) rc = plkh::verify_two_pairings_wide_batch(pk_xy, pk_inf, h, hinf, sig_xy, sig_inf, scratch, ok, n, stream);
-    const int32_t r2 = ws.release();
-    return rc != SYLOW_HIP_OK ? rc : r2;
-  }
+  if (n <= plkh::wide_verify_max())    // small batches: H(m_i), a wavefront per one or two Miller loops / final exponentiations, Gt values compared
+    return verify_small(msgs, msg_offsets, n, 192, /*negate=*/0, stream, [&](const u64* h, const uint8_t* hinf, u64* scratch) {
+      return plkh::verify_two_pairings_wide_batch(pk_xy, pk_inf, h, hinf, sig_xy, sig_inf, scratch, ok, n, stream);
+    });
   DstPrime dp; host::dst_arg(dp, nullptr, 0);
   const bn254::i32* gen = nullptr;
   int32_t rc = host::gen_lines29(&gen, (hipStream_t)stream);
@@ -252,18 +235,10 @@ int32_t sylow_hip_bls_verify_same_signer_batch(const uint64_t* pk_xy, const uint
                                                const uint64_t* sig_xy, const uint8_t* sig_inf, uint8_t* ok, size_t n, void* stream) {
   ARGCHK(pk_xy && msgs && msg_offsets && sig_xy && ok); if (!n) return SYLOW_HIP_OK;
   hipStream_t st = (hipStream_t)stream;
-  if (n <= plkh::wide_verify_max()) {  // small batches: the one-wavefront route of bls_verify_batch with the one key read by every pair
-    host::Lease wsm;
-    int32_t rcs = wsm.acquire((8 + 96) * n * sizeof(u64) + n, st);
-    if (rcs != SYLOW_HIP_OK) return rcs;
-    u64* hneg = (u64*)wsm.p;
-    u64* scratch = hneg + 8 * n;
-    uint8_t* hinf = (uint8_t*)(scratch + 96 * n);
-    rcs = g1h::hash_to_g1(msgs, msg_offsets, hneg, hinf, n, /*negate=*/1, stream);
-    if (rcs == SYLOW_HIP_OK) rcs = plkh::verify_wide_batch(pk_xy, pk_inf, hneg, hinf, sig_xy, sig_inf, scratch, ok, n, stream, /*one_key=*/1);
-    const int32_t r2s = wsm.release();
-    return rcs != SYLOW_HIP_OK ? rcs : r2s;
-  }
+  if (n <= plkh::wide_verify_max())    // small batches: the one-wavefront route of bls_verify_batch with the one key read by every pair
+    return verify_small(msgs, msg_offsets, n, 96, /*negate=*/1, stream, [&](const u64* hneg, const uint8_t* hinf, u64* scratch) {
+      return plkh::verify_wide_batch(pk_xy, pk_inf, hneg, hinf, sig_xy, sig_inf, scratch, ok, n, stream, /*one_key=*/1);
+    });
   DstPrime dp; host::dst_arg(dp, nullptr, 0);
   const bn254::i32* gen = nullptr;
   int32_t rc = host::gen_lines29(&gen, st);
@@ -272,9 +247,7 @@ int32_t sylow_hip_bls_verify_same_signer_batch(const uint64_t* pk_xy, const uint
   if ((rc = ws.acquire(plk::LINE_TABLE_WORDS * sizeof(bn254::i32), st)) != SYLOW_HIP_OK) return rc;
   bn254::i32* table = (bn254::i32*)ws.p;
   plk::k_g2_lines29<<<1, plk::LINES_BLOCK, 0, st>>>(pk_xy, 1, 0, table);     // the key is a 1-element SoA array
-  rc = launch_fused<true>(pk_xy, pk_inf, table, msgs, msg_offsets, dp, sig_xy, sig_inf, gen, ok, n, stream);
-  const int32_t r2 = ws.release();
-  return rc != SYLOW_HIP_OK ? rc : r2;
+  return host::finish(launch_fused<true>(pk_xy, pk_inf, table, msgs, msg_offsets, dp, sig_xy, sig_inf, gen, ok, n, stream), ws);
 }
 // The same check against a line table the host cached for the key (sylow_hip_g2_line_table: `G2PreComputed` cached per pk,
 // examples/verify_multiple_messages_same_signer.rs:41-60): no G2 arithmetic at all, nothing rebuilt per call.

@@ -33,7 +33,7 @@ int32_t sylow_hip_bls_sign_batch(const uint64_t* sk, const uint8_t* msgs, const 
   ARGCHK(sk && msgs && msg_offsets && sig_xy && sig_inf); if (!n) return SYLOW_HIP_OK;
   // single calls and small batches: eight lanes per signature (sign_wide.hip) -- one signature 2.1 -> 0.67 ms; the one-lane kernel below wins
   // once the batch fills the chip's lanes (SYLOW_HIP_OPT_WIDE_TAIL = 0 switches every one-wavefront-per-element route off, this one included)
-  if (plkh::wide_batch_max() != 0 && n <= g1h::sign_wide_max()) return g1h::sign_wide(sk, msgs, msg_offsets, sig_xy, sig_inf, n, stream);
+  if (plkh::small_routes_on() && n <= g1h::sign_wide_max()) return g1h::sign_wide(sk, msgs, msg_offsets, sig_xy, sig_inf, n, stream);
   DstPrime dp; host::dst_arg(dp, nullptr, 0);
   host::Lease ws;
   // window tables in a leased global block, one contiguous KB per lane (bn254_pairing.hpp: G1TableGlobal); a failed lease keeps them in the
@@ -42,8 +42,6 @@ int32_t sylow_hip_bls_sign_batch(const uint64_t* sk, const uint8_t* msgs, const 
   if (ws.acquire(n * G1_TABLE_BYTES_PER_LANE, (hipStream_t)stream) == SYLOW_HIP_OK) tables = (uint8_t*)ws.p;
   else (void)hipGetLastError();
   k_bls_sign<<<GRID(n)>>>(sk, msgs, msg_offsets, dp, sig_xy, sig_inf, n, tables);
-  const hipError_t e = hipGetLastError();
-  const int32_t rc = ws.release();
-  return e != hipSuccess ? host::fail(e, "kernel launch") : rc;
+  return host::finish(SYLOW_HIP_OK, ws);
 }
 }  // extern "C"
