@@ -556,6 +556,22 @@ int32_t sylow_hip_pairing_product_all(const uint64_t* p_xy, const uint8_t* p_inf
  * message; n_pk = 1: pk_xy [16][1].  Identity signatures / keys contribute 1 (pairing() semantics).  n = 0 gives the identity.
  * (As in the reference's example there are no random weights: it answers "is the PRODUCT the identity" -- the product sees the
  * signatures only through their sum, so signatures permuted among the messages still pass; per-element flags: bls_verify_batch.)
+ * Two more shapes of the key array fold the OTHER half the same way; both use the term-major index rule of sylow_hip_g1_lincomb_batch
+ * (element t of job i at t * n_jobs + i), so one huge group and many small ones are both coalesced reads:
+ *   n_pk = c n, c >= 2, n >= 1 -- COMMITTEES: key j belongs to message j mod n and sig_i is committee i's aggregate signature (the
+ *     shape of batch_verify_partial in threshold_signing.rs / dkg.rs and of every validator-set check; n = 1 is "one message, one
+ *     aggregate signature, a list of keys").  prod_t e(-H(msg_i), pk[t n + i]) = e(-H(msg_i), apk_i), apk_i = sum_t pk[t n + i]: a
+ *     segmented G2 sum and n + 1 Miller loops whatever c is.  A caller who holds individual signatures sums them first with
+ *     sylow_hip_g1_sum_batch.
+ *   n = c n_pk, c >= 2, n_pk >= 2 -- KEY REUSE: signature i is under key i mod n_pk.  prod_t e(-H(msg[t n_pk + j]), pk_j) =
+ *     e(-sum_t H(msg[t n_pk + j]), pk_j): a segmented G1 sum and n_pk + 1 Miller loops.
+ *   Any other (n, n_pk) with n > 0, n_pk = 0 included, is SYLOW_HIP_E_ARG.  n_pk = 1 and n_pk = n run exactly as before.
+ * gt_out is the Gt element, hence the words, of the reference's glued_pairing over the n + max(n, n_pk) literal pairs (sig_i, G2gen),
+ * (-H(msg[j mod n]), pk[j mod n_pk]).  A flagged key adds nothing to its sum, whatever its coordinate words hold; a committee whose keys
+ * cancel has apk_i = identity and its pair contributes 1, like pairing().  Key words >= p are reduced like Fp::new.  Precondition, as for
+ * the two older shapes: keys in G2 proper; and summing keys presumes PROOFS OF POSSESSION -- without them a signer can publish a key that
+ * cancels the others' (rogue-key attack).  With comm != NULL every rank passes WHOLE committees / whole periods of keys (shards are cut by
+ * message row); one committee split across ranks is not supported.
  *   _partial_: f_out [48][1] = this shard's Miller product up to a factor in Fp* (see sylow_hip_pairing_product_partial_batch; for hosts
  *              that combine shards themselves, with sylow_hip_fp12_product_final_exp);
  *   _verify_:  the whole check; comm = the host's ncclComm_t for a batch sharded over the GPUs of a node (every rank passes its
@@ -572,7 +588,8 @@ int32_t sylow_hip_bls_aggregate_verify_batch(const uint64_t* pk_xy, const uint8_
  * element from the test).  If every signature is valid the result is the identity; if any is not, the test passes with probability at most
  * 2^-(bits of the weights) over the caller's randomness (keys in G2 proper, as G2Projective::new guarantees).  No counterpart exists upstream --
  * the reference's examples multiply unweighted (the two entry points above); the Gt value equals the reference's glued_pairing over the 2n
- * pairs (w_i sig_i, G2gen), (-w_i H(msg_i), pk_i), which is how it is tested.  Shapes, n_pk, comm and the _partial_ form as above. */
+ * pairs (w_i sig_i, G2gen), (-w_i H(msg_i), pk_i), which is how it is tested.  Shapes, n_pk (committees and key reuse included: weights
+ * stay [4][n], one per message row, and multiply sig_i and H(msg_i); the key sums are never weighted), comm and the _partial_ form as above. */
 /* @shape pk_xy=u64[16*n_pk] pk_inf=u8[n_pk]? msgs=u8[*] msg_offsets=u64[n+1] sig_xy=u64[8*n] sig_inf=u8[n]? weights=u64[4*n] f_out=u64[48] */
 int32_t sylow_hip_bls_weighted_partial_batch(const uint64_t* pk_xy, const uint8_t* pk_inf, size_t n_pk, const uint8_t* msgs, const uint64_t* msg_offsets,
                                              const uint64_t* sig_xy, const uint8_t* sig_inf, const uint64_t* weights, size_t n, uint64_t* f_out, void* stream);

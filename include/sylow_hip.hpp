@@ -286,10 +286,15 @@ template <class T> struct PinnedAllocator {
 };
 
 // "are ALL of them valid?" as ONE boolean: the glued product of examples/verify_multiple_messages_same_signer.rs:41-60 (weights == nullptr)
-// or the sound small-exponent test with the caller's random weights (sylow_hip_bls_batch_verify_weighted).  One key per message, or one key.
+// or the sound small-exponent test with the caller's random weights (sylow_hip_bls_batch_verify_weighted).  One key per message, or one key;
+// c * n keys: n committees of c keys, term-major (key j belongs to message j mod n, sig[i] is committee i's aggregate signature; summed keys
+// presume proofs of possession); n / c keys, at least two: keys reused with that period (signature i is under key i mod pubkey.size()).
+inline bool aggregate_shape_ok(size_t n, size_t n_pk) {
+  return n == 0 || n_pk == 1 || n_pk == n || (n_pk > n && n_pk % n == 0) || (n_pk >= 2 && n_pk < n && n % n_pk == 0);
+}
 inline bool verify_all(const std::vector<G2Affine>& pubkey, const std::vector<std::vector<uint8_t>>& msgs, const std::vector<G1Affine>& sig,
                        const std::vector<Fp>* weights = nullptr, Gt* product = nullptr) {
-  if (sig.size() != msgs.size() || (pubkey.size() != msgs.size() && pubkey.size() != 1)) throw Error("verify_all: length mismatch");
+  if (sig.size() != msgs.size() || !aggregate_shape_ok(msgs.size(), pubkey.size())) throw Error("verify_all: length mismatch");
   if (weights && weights->size() != msgs.size()) throw Error("verify_all: one weight per signature");
   Messages m(msgs);
   auto dpk = to_device_soa(pubkey); auto dsig = to_device_soa(sig);
@@ -306,6 +311,12 @@ inline bool verify_all(const std::vector<G2Affine>& pubkey, const std::vector<st
   check(sylow_hip_memcpy_d2h(&one, done.as<void>(), 1, nullptr), "d2h"); check(sylow_hip_stream_sync(nullptr), "sync");
   if (product) *product = from_device_soa<Gt>(dgt, 1)[0];
   return one != 0;
+}
+// Many signers, ONE message (examples/threshold_signing.rs:92-121): e(sig, G2gen) e(-H(msg), sum_j pubkeys[j]) == identity -- one hash, one G2
+// sum and two Miller loops whatever the number of keys.  `sig` is the signers' aggregate signature (sum() of the individual ones).
+inline bool verify_one_message(const std::vector<G2Affine>& pubkeys, const std::vector<uint8_t>& msg, const G1Affine& sig, Gt* product = nullptr) {
+  if (pubkeys.empty()) throw Error("verify_one_message: no public keys");
+  return verify_all(pubkeys, std::vector<std::vector<uint8_t>>{msg}, std::vector<G1Affine>{sig}, nullptr, product);
 }
 // sum_i p[i] as ONE point (the `+` fold of examples/verify_multiple_messages_same_signer.rs:41-60); *is_identity receives the flag of the result
 inline G1Affine sum(const std::vector<G1Affine>& p, bool* is_identity = nullptr, const std::vector<uint8_t>* p_inf = nullptr) {

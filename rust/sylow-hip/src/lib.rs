@@ -412,10 +412,13 @@ pub fn glued_pairing_all(dev: &Device, p: &[G1Affine], q: &[G2Affine], skip_iden
 /// Aggregate verification -- the batch shape of examples/verify_multiple_messages_same_signer.rs:41-60 and
 /// threshold_signing.rs:92-121: is the product of the 2n pairs (sig_i, G2gen), (-H(msg_i), pk_i) the identity?  The signatures are
 /// summed in G1 first (prod_i e(sig_i, G2gen) = e(sum_i sig_i, G2gen)); `pk` holds one key per message, or ONE key for the whole
-/// batch (then the hashes are summed as well).  Returns the Gt value of the product and the boolean.  `comm`: as for `all_valid`
-/// (every rank passes its shard of a batch spread over the GPUs of the node; null = this process alone).
+/// batch (then the hashes are summed as well).  Two more shapes, term-major: `c * n` keys are n committees of c keys (key j belongs to
+/// message `j % n`, `sig[i]` is committee i's aggregate signature; the keys are summed, which presumes proofs of possession), and
+/// `n / c` keys (at least two) are keys reused with that period (signature i is under key `i % pk.len()`).
+/// Returns the Gt value of the product and the boolean.  `comm`: as for `all_valid` (every rank passes its shard of a batch spread
+/// over the GPUs of the node, whole committees only; null = this process alone).
 pub fn aggregate_verify(dev: &Device, pk: &[G2Affine], msgs: &[&[u8]], sig: &[G1Affine], comm: *mut c_void) -> Result<(GtOut, bool), HipError> {
-    assert!(sig.len() == msgs.len() && (pk.len() == msgs.len() || pk.len() == 1));
+    assert!(sig.len() == msgs.len() && aggregate_shape_ok(msgs.len(), pk.len()));
     let n = msgs.len();
     let (dpk, dsig) = (upload_g2(dev, pk)?, upload_g1(dev, sig)?);
     let (d_msgs, d_off) = messages(dev, msgs)?;
@@ -427,6 +430,19 @@ pub fn aggregate_verify(dev: &Device, pk: &[G2Affine], msgs: &[&[u8]], sig: &[G1
     })?;
     let words = dev.download_aos::<48>(&gt, 1)?;
     Ok((gt_from_words(&words[0]), dev.download(&one)?[0] != 0))
+}
+
+/// The key-array lengths `aggregate_verify` takes for n (message, signature) rows: one key, one per row, committees, key reuse.
+pub fn aggregate_shape_ok(n: usize, n_pk: usize) -> bool {
+    n == 0 || n_pk == 1 || n_pk == n || (n_pk > n && n_pk % n == 0) || (n_pk >= 2 && n_pk < n && n % n_pk == 0)
+}
+
+/// Many signers, ONE message (examples/threshold_signing.rs:92-121, dkg.rs:146-175): is e(sig, G2gen) e(-H(msg), sum_j pk_j) the
+/// identity?  One hash, one G2 sum and two Miller loops whatever the number of keys.  `sig` is the signers' aggregate signature.
+/// Summing keys presumes proofs of possession.
+pub fn fast_aggregate_verify(dev: &Device, pk: &[G2Affine], msg: &[u8], sig: &G1Affine) -> Result<bool, HipError> {
+    assert!(!pk.is_empty());
+    Ok(aggregate_verify(dev, pk, &[msg], std::slice::from_ref(sig), std::ptr::null_mut())?.1)
 }
 
 /// A batch of cached `G2PreComputed` tables (pairing.rs:556) resident on the device, and the two loops that consume them:

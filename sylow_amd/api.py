@@ -429,8 +429,28 @@ def verify_same_signer(pubkey: G2Affine, msgs, sig: G1Affine) -> np.ndarray:
 
 def aggregate_verify(pubkey: G2Affine, msgs, sig: G1Affine) -> bool:
     """The batch check of examples/verify_multiple_messages_same_signer.rs:41-60 / threshold_signing.rs:92-121: the product of the
-    2n pairs (sig_i, G2gen), (-H(msg_i), pk_i) == Gt::identity(), as one boolean; `pubkey` holds one key per message or ONE key."""
-    _, ok = engine().bls_aggregate_verify(pubkey.xy, list(msgs), sig.xy, pubkey.infinity, sig.infinity)
+    2n pairs (sig_i, G2gen), (-H(msg_i), pk_i) == Gt::identity(), as one boolean; `pubkey` holds one key per message or ONE key.
+    Two more shapes of `pubkey`, rows term-major like aggregate(): c * n keys are n COMMITTEES of c keys (key j belongs to message
+    j mod n, sig_i is committee i's aggregate signature; the keys are summed, so they must come with proofs of possession), and n / c
+    keys (at least two) are keys REUSED with that period (signature i is under key i mod len(pubkey))."""
+    msgs = list(msgs)
+    if not engine().aggregate_shape_ok(len(msgs), len(pubkey)) or len(sig) != len(msgs):
+        raise ValueError(f"aggregate_verify: {len(pubkey)} keys and {len(sig)} signatures for {len(msgs)} messages")
+    _, ok = engine().bls_aggregate_verify(pubkey.xy, msgs, sig.xy, pubkey.infinity, sig.infinity)
+    return bool(ok)
+
+
+def fast_aggregate_verify(pubkeys: G2Affine, msg: bytes, sig: G1Affine) -> bool:
+    """Many signers, ONE message (examples/threshold_signing.rs:92-121, dkg.rs:146-175; every committee / validator-set check):
+    e(sig, G2gen) e(-H(msg), sum_j pk_j) == Gt::identity() -- one hash, one G2 sum and two Miller loops whatever the number of keys.
+    `sig` is the aggregate signature, or the signers' individual signatures (summed first).  Summing keys presumes proofs of
+    possession: without them a signer can choose a key that cancels the others' (rogue-key attack)."""
+    if len(pubkeys) == 0:
+        raise ValueError("fast_aggregate_verify: no public keys")
+    sig_xy, sig_inf = sig.xy, sig.infinity
+    if len(sig) != 1:
+        sig_xy, sig_inf = engine().g1_sum(sig_xy, sig_inf)
+    _, ok = engine().bls_aggregate_verify(pubkeys.xy, [bytes(msg)], sig_xy, pubkeys.infinity, sig_inf)
     return bool(ok)
 
 

@@ -222,6 +222,41 @@ __global__ void __launch_bounds__(BLOCK) k_g1_sum_tail(u64* acc, size_t n, size_
   store_fp(oxy, stride, col, 0, x); store_fp(oxy, stride, col, 4, y);
   oinf[col] = inf ? 1 : 0;
 }
+// Segmented form: out_s = sum_k P[k * n_seg + s], s < n_seg, k < m -- n_seg independent sums in the term-major layout of k_g1_lincomb (the
+// hashes of the messages signed under one key, when keys repeat with period n_seg).  The same stages of serial accumulation: lane
+// u = part * n_seg + s adds up terms part, part + parts, ... of segment s and leaves one projective partial at element u of acc (in place when
+// the input is acc: lane u alone reads element u, before it writes); parts = 1 is the last stage, which converts to affine.  One rule covers a
+// handful of long segments and many short ones (g1h::sum_segments), so there is no second kernel and no switch between two to tune.
+template <bool AFFINE_IN, bool AFFINE_OUT>
+__global__ void HEAVY_BOUNDS k_g1_seg_fold(const u64* in, const uint8_t* inf, size_t stride_in, size_t n_seg, size_t m, size_t parts,
+                                           u64* out, uint8_t* oinf, size_t stride_out) {
+  const size_t u = TID;
+  if (u >= n_seg * parts) return;
+  const size_t part = u / n_seg, seg = u - part * n_seg;
+  G1W res = proj_zero<OpsF29>();
+#pragma unroll 1
+  for (size_t k = part; k < m; k += parts) {
+    const size_t i = k * n_seg + seg;
+    G1W q;
+    if (AFFINE_IN) {
+      const bool z = inf && inf[i];                     // a flagged point is (0 : 1 : 0) whatever its coordinate words hold
+      q.x = OpsF29::select(f29_from_fp_reduced(load_fp(in, stride_in, i, 0)), OpsF29::zero(), z);
+      q.y = OpsF29::select(f29_from_fp_reduced(load_fp(in, stride_in, i, 4)), OpsF29::one(), z);
+      q.z = OpsF29::select(OpsF29::one(), OpsF29::zero(), z);
+    } else {
+      q = g1w_load_proj(in, stride_in, i);
+    }
+    res = proj_add_lazy<OpsF29>(res, q);
+  }
+  if (AFFINE_OUT) {
+    Fp x, y; bool rinf;
+    g1_to_affine(x, y, rinf, G1P{f29_to_fp(res.x), f29_to_fp(res.y), f29_to_fp(res.z)});
+    store_fp(out, stride_out, seg, 0, x); store_fp(out, stride_out, seg, 4, y);
+    oinf[seg] = rinf ? 1 : 0;
+  } else {
+    g1w_store_proj(out, stride_out, u, res);
+  }
+}
 
 // ------------------------------------------------------------------ hash / BLS kernels ----------
 // k_hash_to_g1 lives in hash.hip (a unit of its own: compiled for four wavefronts per SIMD)
@@ -372,6 +407,35 @@ int32_t sum_tree_strided(uint64_t* acc, size_t acc_stride, size_t m, uint64_t* o
     m = L;
   }
   k_g1_sum_tail<<<1, BLOCK, 0, (hipStream_t)stream>>>(acc, acc_stride, m, out_xy, out_inf, stride, col, negate); LAUNCHED();
+}
+// Segmented sum (k_g1_seg_fold): a stage cuts every segment into `parts` slices of at least SUM_FOLD terms while that fills no more than one
+// round of the GPU (2^17 lanes resident); many segments: parts = 1 at once, one lane per segment
+constexpr size_t SEG_ROUND = 131072;
+static size_t seg_parts(size_t n_seg, size_t m) {
+  const size_t by_work = fold_lanes(m), by_room = SEG_ROUND / n_seg;
+  const size_t p = by_work < by_room ? by_work : by_room;
+  return p < 1 ? 1 : p;
+}
+size_t sum_segments_scratch_words(size_t n_seg, size_t c) {
+  const size_t p = n_seg ? seg_parts(n_seg, c) : 1;
+  return p > 1 ? 12 * n_seg * p : 0;
+}
+int32_t sum_segments(const uint64_t* p_xy, const uint8_t* p_inf, size_t n_seg, size_t c, uint64_t* acc, uint64_t* out_xy, uint8_t* out_inf, void* stream) {
+  if (!n_seg) return SYLOW_HIP_OK;
+  const size_t stride_acc = n_seg * seg_parts(n_seg, c);
+  const uint64_t* in = p_xy;
+  size_t m = c, stride_in = n_seg * c;
+  bool affine = true;
+  for (;;) {
+    const size_t parts = seg_parts(n_seg, m);
+    if (parts <= 1) break;
+    if (affine) k_g1_seg_fold<true, false><<<GRID(n_seg * parts)>>>(in, p_inf, stride_in, n_seg, m, parts, acc, nullptr, stride_acc);
+    else k_g1_seg_fold<false, false><<<GRID(n_seg * parts)>>>(in, nullptr, stride_in, n_seg, m, parts, acc, nullptr, stride_acc);
+    in = acc; stride_in = stride_acc; m = parts; affine = false;      // parts <= ceil(m / SUM_FOLD) < m: the loop ends
+  }
+  if (affine) k_g1_seg_fold<true, true><<<GRID(n_seg)>>>(in, p_inf, stride_in, n_seg, m, 1, out_xy, out_inf, n_seg);
+  else k_g1_seg_fold<false, true><<<GRID(n_seg)>>>(in, nullptr, stride_in, n_seg, m, 1, out_xy, out_inf, n_seg);
+  LAUNCHED();
 }
 }  // namespace g1h
 

@@ -108,6 +108,10 @@ int32_t sum(const uint64_t* p_xy, const uint8_t* p_inf, size_t n, uint64_t* acc,
 int32_t sum_tree(uint64_t* acc, size_t n, uint64_t* out_xy, uint8_t* out_inf, size_t stride, size_t col, int negate, void* stream);
 // the same for the first m elements of an acc whose SoA stride is acc_stride
 int32_t sum_tree_strided(uint64_t* acc, size_t acc_stride, size_t m, uint64_t* out_xy, uint8_t* out_inf, size_t stride, size_t col, int negate, void* stream);
+// n_seg independent sums of c points each, term-major (term k of segment s at index k * n_seg + s) -> affine SoA [8][n_seg] + flags;
+// acc: scratch of sum_segments_scratch_words(n_seg, c) words (0 when one stage does it)
+size_t sum_segments_scratch_words(size_t n_seg, size_t c);
+int32_t sum_segments(const uint64_t* p_xy, const uint8_t* p_inf, size_t n_seg, size_t c, uint64_t* acc, uint64_t* out_xy, uint8_t* out_inf, void* stream);
 }  // namespace g1h
 namespace plkh {        // lane-pair units
 // selectors of plk_pairing.hip's Fp12 kernel (sylow_hip_fp12_hook_batch, and the Fp12 entry points of tower.hip)
@@ -127,6 +131,10 @@ int32_t build_lines29(const uint64_t* q_xy, size_t n, size_t idx, bn254::i32* ta
 size_t line_table_bytes();                                                                             // plk_verify.hip
 size_t g2_comb_bytes();                                                                                // plk_group.hip
 int32_t build_g2_comb(bn254::i32* table, void* stream);                                                // plk_group.hip
+// plk_group.hip: the G2 twin of g1h::sum_segments -- n_seg sums of c points each, term-major -> affine SoA [16][n_seg] + flags (the public keys
+// of n_seg committees); acc: scratch of g2_sum_scratch_words(n_seg, c) words
+size_t g2_sum_scratch_words(size_t n_seg, size_t c);
+int32_t g2_sum(const uint64_t* q_xy, const uint8_t* q_inf, size_t n_seg, size_t c, uint64_t* acc, uint64_t* out_xy, uint8_t* out_inf, void* stream);
 // plk_multi.hip: small batches on one wavefront per element, and the eight-lane routes of sign_wide.hip (small_routes_on: SYLOW_HIP_OPT_WIDE_TAIL != 0)
 bool small_routes_on();
 size_t wide_batch_max();           // 0 when the small-batch routes are off

@@ -364,6 +364,38 @@ __global__ void HEAVY_BOUNDS k_g2_normalize(const u64* pxyz, u64* oxy, uint8_t* 
   const G2Q p{w2_from_s2(load_s2(pxyz, n, i, 0, odd)), w2_from_s2(load_s2(pxyz, n, i, 8, odd)), w2_from_s2(load_s2(pxyz, n, i, 16, odd))};
   store_g2q_affine(oxy, oinf, n, i, odd, p);
 }
+// ------------------------------------------------------------------ segmented sums of G2 points ------------------------------
+// out_s = sum_k Q[k * n_seg + s], s < n_seg, k < m: n_seg independent sums of m points each in the term-major layout of
+// sylow_hip_g1_lincomb_batch (the public keys of n_seg committees: prod_j e(-H(m), pk_j) = e(-H(m), sum_j pk_j), dkg.rs:309-314 folds
+// keys the same way).  The model is the G1 sum of g1.hip: stages of SERIAL accumulation, accumulator in registers, complete formulas
+// (a doubling, an identity or a cancelling pair inside a sum needs no special case).  Lane pair u = part * n_seg + s adds up terms
+// part, part + parts, ... of segment s -- a wavefront reads 32 consecutive elements at every step whether that is one huge segment
+// or many small ones -- and leaves ONE projective partial at element u of acc [24][stride] (in place when the input is acc itself:
+// lane pair u is the only reader of element u and has read it before it writes).  `parts` = 1 is the last stage: one lane pair per
+// segment, one normalisation, affine words + flag into the array the Miller loop reads.
+// On E' (OpsW2), not on the isomorphic twist: with affine input the map costs two Fp scalings per point for ONE addition, and the
+// instruction count of the loop body decides it.
+constexpr size_t G2_SUM_FOLD = 16;          // terms per lane pair and stage, as SUM_FOLD of g1.hip
+BN_DEV void store_g2q_proj(u64* a, size_t stride, size_t i, int odd, const G2Q& r) {
+  store_s2(a, stride, i, 0, odd, w2_to_s2(r.x)); store_s2(a, stride, i, 8, odd, w2_to_s2(r.y)); store_s2(a, stride, i, 16, odd, w2_to_s2(r.z));
+}
+template <bool AFFINE_IN, bool AFFINE_OUT>
+__global__ void HEAVY_BOUNDS k_g2_seg_fold(const u64* in, const uint8_t* inf, size_t stride_in, size_t n_seg, size_t m, size_t parts,
+                                           u64* out, uint8_t* oinf, size_t stride_out) {
+  const size_t t = TID, u = pair_index(t);
+  const int odd = pair_role(t);
+  if (u >= n_seg * parts) return;
+  const size_t part = u / n_seg, seg = u - part * n_seg;
+  G2Q res = proj_zero<OpsW2>();
+#pragma unroll 1
+  for (size_t k = part; k < m; k += parts) {
+    const size_t i = k * n_seg + seg;
+    const G2Q q = AFFINE_IN ? load_g2q(in, inf, stride_in, i, odd) : load_g2q_proj(in, stride_in, i, odd);
+    res = proj_add_lazy<OpsW2>(res, q);           // inlined in the loop: no point travels through the stack frame
+  }
+  if (AFFINE_OUT) store_g2q_affine(out, oinf, stride_out, seg, odd, res);
+  else store_g2q_proj(out, stride_out, u, odd, res);
+}
 // G2Affine::endomorphism (g2.rs:140-152): psi(x, y) = (eps0 conj x, eps1 conj y), psi(identity) = identity; status reports the
 // on-curve re-check the reference performs on the result (it panics there; here NOT_ON_CURVE)
 __global__ void __launch_bounds__(BLOCK) k_g2_psi(const u64* qxy, const uint8_t* qinf, u64* oxy, uint8_t* oinf, uint8_t* status, size_t n) {
@@ -698,6 +730,36 @@ namespace plkh {
 size_t g2_comb_bytes() { return plk::COMB_WORDS * sizeof(bn254::i32); }
 int32_t build_g2_comb(bn254::i32* table, void* stream) {
   plk::k_g2_comb_table<<<GRID(2 * (size_t)plk::COMB_WIN * plk::COMB_ENT)>>>(table); LAUNCHED();
+}
+// Segmented G2 sum (k_g2_seg_fold).  Two regimes from one rule: a stage cuts every segment into `parts` slices of at least G2_SUM_FOLD terms
+// for as long as that fills no more than one round of the GPU (2^16 lane pairs resident); with n_seg of that order or more parts = 1 at once and
+// every lane pair walks its own segment; with ONE segment of 2^20 points the stages are 65536, 4096, 256, 16 and 1 lane pairs.
+constexpr size_t G2_SUM_ROUND = 65536;
+static size_t g2_sum_parts(size_t n_seg, size_t m) {
+  const size_t by_work = (m + plk::G2_SUM_FOLD - 1) / plk::G2_SUM_FOLD, by_room = G2_SUM_ROUND / n_seg;
+  const size_t p = by_work < by_room ? by_work : by_room;
+  return p < 1 ? 1 : p;
+}
+size_t g2_sum_scratch_words(size_t n_seg, size_t c) {
+  const size_t p = n_seg ? g2_sum_parts(n_seg, c) : 1;
+  return p > 1 ? 24 * n_seg * p : 0;
+}
+int32_t g2_sum(const uint64_t* q_xy, const uint8_t* q_inf, size_t n_seg, size_t c, uint64_t* acc, uint64_t* out_xy, uint8_t* out_inf, void* stream) {
+  if (!n_seg) return SYLOW_HIP_OK;
+  const size_t stride_acc = n_seg * g2_sum_parts(n_seg, c);
+  const uint64_t* in = q_xy;
+  size_t m = c, stride_in = n_seg * c;
+  bool affine = true;
+  for (;;) {
+    const size_t parts = g2_sum_parts(n_seg, m);
+    if (parts <= 1) break;
+    if (affine) plk::k_g2_seg_fold<true, false><<<GRID(2 * n_seg * parts)>>>(in, q_inf, stride_in, n_seg, m, parts, acc, nullptr, stride_acc);
+    else plk::k_g2_seg_fold<false, false><<<GRID(2 * n_seg * parts)>>>(in, nullptr, stride_in, n_seg, m, parts, acc, nullptr, stride_acc);
+    in = acc; stride_in = stride_acc; m = parts; affine = false;      // parts <= ceil(m / 16) < m: the loop ends
+  }
+  if (affine) plk::k_g2_seg_fold<true, true><<<GRID(2 * n_seg)>>>(in, q_inf, stride_in, n_seg, m, 1, out_xy, out_inf, n_seg);
+  else plk::k_g2_seg_fold<false, true><<<GRID(2 * n_seg)>>>(in, nullptr, stride_in, n_seg, m, 1, out_xy, out_inf, n_seg);
+  LAUNCHED();
 }
 int32_t evm_decode_pairs(const uint8_t* in, size_t n_pairs, uint64_t* pxy, uint8_t* pinf, uint64_t* qxy, uint8_t* qinf, uint8_t* pst, void* stream) {
   k_evm_decode_pairs<<<dim3((unsigned)((2 * n_pairs + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, (hipStream_t)stream>>>(in, n_pairs, pxy, pinf, qxy, qinf, pst);

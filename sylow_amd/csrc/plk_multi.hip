@@ -1175,7 +1175,11 @@ int32_t sylow_hip_pairing_product_partial_batch(const uint64_t* p_xy, const uint
 using host::Fork;
 static int32_t aggregate_partial(const uint64_t* pk_xy, const uint8_t* pk_inf, size_t n_pk, const uint8_t* msgs, const uint64_t* msg_offsets,
                                  const uint64_t* sig_xy, const uint8_t* sig_inf, const uint64_t* weights, size_t n, uint64_t* f_out, void* stream) {
-  ARGCHK(f_out && (n == 0 || (pk_xy && msgs && msg_offsets && sig_xy && (n_pk == 1 || n_pk == n))));
+  // n_pk = c n, c >= 2: COMMITTEES -- key j belongs to message j mod n (term-major, as sylow_hip_g1_lincomb_batch), sig_i is the committee's
+  // aggregate signature: prod_t e(-H_i, pk[t n + i]) = e(-H_i, sum_t pk[t n + i]), n Miller loops whatever c is.  n = c n_pk, n_pk >= 2: KEY
+  // REUSE -- signature i is under key i mod n_pk: prod_t e(-H[t n_pk + j], pk_j) = e(-sum_t H[t n_pk + j], pk_j), n_pk Miller loops.
+  const bool committees = n != 0 && n_pk > n && n_pk % n == 0, key_reuse = n_pk >= 2 && n > n_pk && n % n_pk == 0;
+  ARGCHK(f_out && (n == 0 || (pk_xy && msgs && msg_offsets && sig_xy && (n_pk == 1 || n_pk == n || committees || key_reuse))));
   hipStream_t st = (hipStream_t)stream;
   if (n == 0) { plk::k_fp12_set_one<<<1, 64, 0, st>>>(f_out); LAUNCHED(); }
   const bool one_key = n_pk == 1 && n != 1;
@@ -1205,12 +1209,43 @@ static int32_t aggregate_partial(const uint64_t* pk_xy, const uint8_t* pk_inf, s
       rc = miller_product_tree(pb2, p2inf + 1, qb2, q2inf + 1, 1, 1, wb, &pb, sd);
     }
   }
+  // committees: the key sums depend on the keys only -- a segmented G2 sum on a side stream of its own beside the hashing (behind the
+  // signature half on `sd` its Miller loop and the one below would run one after the other)
+  host::Lease wx;                                           // the folded operands of the two shapes above, and the fold's scratch
+  u64* fxy = nullptr;
+  uint8_t* finf = nullptr;
+  Fork fork_keys;
+  if (rc == SYLOW_HIP_OK && committees) {
+    const size_t w_fold = plkh::g2_sum_scratch_words(n, n_pk / n);
+    hipStream_t sk = fork_keys.open(st, host::option(SYLOW_HIP_OPT_AGG_FORK) != 0);
+    rc = wx.acquire((16 * n + w_fold) * sizeof(u64) + n, sk);
+    if (rc == SYLOW_HIP_OK) {
+      fxy = (u64*)wx.p;
+      finf = (uint8_t*)(fxy + 16 * n + w_fold);
+      rc = plkh::g2_sum(pk_xy, pk_inf, n, n_pk / n, fxy + 16 * n, fxy, finf, sk);      // apk_i = sum_t pk[t n + i]
+    }
+  }
   // one key and no weights: only the SUM of the hashes is needed -- they go projective straight into the summation tree's array
   const bool hash_into_tree = one_key && !weights;
   if (rc == SYLOW_HIP_OK) rc = hash_into_tree ? g1h::hash_to_g1_proj(msgs, msg_offsets, acc2, n, stream)
                                               : g1h::hash_to_g1(msgs, msg_offsets, hxy, hinf, n, /*negate=*/one_key ? 0 : 1, stream);
   if (rc == SYLOW_HIP_OK && weights) rc = sylow_hip_g1_scalar_mul_batch(hxy, hinf, weights, hxy, hinf, n, stream);      // H_i <- w_i H_i (in place)
-  if (rc == SYLOW_HIP_OK && !one_key) {
+  if (rc == SYLOW_HIP_OK && committees) {
+    // prod_i e(-[w_i] H_i, apk_i): n pairs
+    rc = fork_keys.join(st);
+    if (wx.slot >= 0) wx.st = st;      // as wb below
+    if (rc == SYLOW_HIP_OK) rc = miller_product_tree(hxy, hinf, fxy, finf, n, 1, wa, &pa, stream);
+  } else if (rc == SYLOW_HIP_OK && key_reuse) {
+    // prod_j e(-sum_t [w] H[t n_pk + j], pk_j): n_pk pairs
+    const size_t w_fold = g1h::sum_segments_scratch_words(n_pk, n / n_pk);
+    rc = wx.acquire((8 * n_pk + w_fold) * sizeof(u64) + n_pk, st);
+    if (rc == SYLOW_HIP_OK) {
+      fxy = (u64*)wx.p;
+      finf = (uint8_t*)(fxy + 8 * n_pk + w_fold);
+      rc = g1h::sum_segments(hxy, hinf, n_pk, n / n_pk, fxy + 8 * n_pk, fxy, finf, stream);
+    }
+    if (rc == SYLOW_HIP_OK) rc = miller_product_tree(fxy, finf, pk_xy, pk_inf, n_pk, 1, wa, &pa, stream);
+  } else if (rc == SYLOW_HIP_OK && !one_key) {
     // prod_i e(-H_i, pk_i) over the batch
     rc = miller_product_tree(hxy, hinf, pk_xy, pk_inf, n, 1, wa, &pa, stream);
   } else if (rc == SYLOW_HIP_OK) {
@@ -1226,7 +1261,7 @@ static int32_t aggregate_partial(const uint64_t* pk_xy, const uint8_t* pk_inf, s
   if (rc == SYLOW_HIP_OK) rc = joined;
   if (rc == SYLOW_HIP_OK) plk::k_fp12_mul_pair<<<1, 64, 0, st>>>(pa, pb, f_out);
   if (wb.slot >= 0) wb.st = st;      // the caller's stream has joined the side stream and still reads the block: its release is ordered there
-  return host::finish(rc, wa, wb, ws);
+  return host::finish(rc, wa, wb, wx, ws);
 }
 int32_t sylow_hip_bls_aggregate_partial_batch(const uint64_t* pk_xy, const uint8_t* pk_inf, size_t n_pk, const uint8_t* msgs, const uint64_t* msg_offsets,
                                               const uint64_t* sig_xy, const uint8_t* sig_inf, size_t n, uint64_t* f_out, void* stream) {

@@ -783,12 +783,18 @@ class Engine:
         self._call(name, dpk.ptr, self._ptr(dpi), dm.ptr, doff.ptr, dsig.ptr, self._ptr(dsi), dok.ptr, n)
         return dok.download()
 
+    @staticmethod
+    def aggregate_shape_ok(n, n_pk):
+        """The key-array shapes the aggregate entry points take for n (message, signature) rows (include/sylow_hip.h): one key, one key per
+        row, committees (n_pk = c n: key j belongs to message j mod n) and key reuse (n = c n_pk, n_pk >= 2: row i is under key i mod n_pk)."""
+        return n == 0 or n_pk in (1, n) or (n_pk > n and n_pk % n == 0) or (2 <= n_pk < n and n % n_pk == 0)
+
     def bls_aggregate_verify(self, pk_xy, msgs, sig_xy, pk_inf=None, sig_inf=None, comm=None):
-        """One boolean for the whole batch: prod_i e(sig_i, G2gen) e(-H(msg_i), pk_i) == 1 (one key row = the same signer).
-        Returns (gt [48] words, is_one)."""
+        """One boolean for the whole batch: prod_i e(sig_i, G2gen) e(-H(msg_i), pk_i) == 1 (one key row = the same signer; c n key rows =
+        committees of c keys, sig_i their aggregate signature; n / c key rows = keys reused with that period).  Returns (gt [48] words, is_one)."""
         pk_xy, sig_xy = _aos(pk_xy, 16), _aos(sig_xy, 8)
         n, n_pk = len(msgs), pk_xy.shape[0]
-        assert sig_xy.shape[0] == n and (n_pk in (1, n) or n == 0)
+        assert sig_xy.shape[0] == n and self.aggregate_shape_ok(n, n_pk)
         dm, doff = self._msgs(msgs)
         dpk = self.to_device_soa(pk_xy, 16) if n_pk else None
         dsig = self.to_device_soa(sig_xy, 8) if n else None
@@ -802,13 +808,31 @@ class Engine:
         verification); weights [n, 4] Fp values drawn by the caller after the signatures are fixed.  Returns (Gt words, bool)."""
         pk_xy, sig_xy, weights = _aos(pk_xy, 16), _aos(sig_xy, 8), _aos(weights, 4)
         n, n_pk = sig_xy.shape[0], pk_xy.shape[0]
-        assert len(msgs) == n and weights.shape[0] == n and n_pk in (1, n)
+        assert len(msgs) == n and weights.shape[0] == n and n_pk >= 1 and self.aggregate_shape_ok(n, n_pk)
         dpk, dsig, dw = self.to_device_soa(pk_xy, 16), self.to_device_soa(sig_xy, 8), self.to_device_soa(weights, 4)
         dm, doff = self._msgs(msgs)
         dpi, dsi = self._flags(pk_inf, n_pk), self._flags(sig_inf, n)
         dgt, dis = self.empty((48, 1)), self.empty((1,), np.uint8)
         self._call("sylow_hip_bls_batch_verify_weighted", dpk.ptr, self._ptr(dpi), n_pk, dm.ptr, doff.ptr, dsig.ptr, self._ptr(dsi), dw.ptr, n, comm, dgt.ptr, dis.ptr)
         return self.from_device_soa(dgt), bool(dis.download()[0])
+
+    def bls_aggregate_partial(self, pk_xy, msgs, sig_xy, weights=None, pk_inf=None, sig_inf=None):
+        """One shard's raw Miller product of the (weighted) aggregate check, [1, 48] words: the input of fp12_product_final_exp."""
+        pk_xy, sig_xy = _aos(pk_xy, 16), _aos(sig_xy, 8)
+        n, n_pk = len(msgs), pk_xy.shape[0]
+        assert sig_xy.shape[0] == n and n_pk >= 1 and self.aggregate_shape_ok(n, n_pk)
+        dpk, dsig = self.to_device_soa(pk_xy, 16), self.to_device_soa(sig_xy, 8)
+        dm, doff = self._msgs(msgs)
+        dpi, dsi = self._flags(pk_inf, n_pk), self._flags(sig_inf, n)
+        df = self.empty((48, 1))
+        if weights is None:
+            self._call("sylow_hip_bls_aggregate_partial_batch", dpk.ptr, self._ptr(dpi), n_pk, dm.ptr, doff.ptr, dsig.ptr, self._ptr(dsi), n, df.ptr)
+        else:
+            weights = _aos(weights, 4)
+            assert weights.shape[0] == n
+            dw = self.to_device_soa(weights, 4)
+            self._call("sylow_hip_bls_weighted_partial_batch", dpk.ptr, self._ptr(dpi), n_pk, dm.ptr, doff.ptr, dsig.ptr, self._ptr(dsi), dw.ptr, n, df.ptr)
+        return self.from_device_soa(df)
 
     def bls_verify_same_signer(self, pk_xy, msgs, sig_xy, pk_inf=None, sig_inf=None):
         pk_xy, sig_xy = _aos(pk_xy, 16), _aos(sig_xy, 8)
