@@ -89,10 +89,11 @@ def run_pair(engine: Engine, inputs, pair_per_point_cost=BYZANTIUM_PAIR_PER_POIN
         counts = [len(inputs[i]) // PAIR_ELEMENT_LEN for i in live]
         off = np.concatenate([[0], np.cumsum(counts)]).astype(np.uint64)
         n_pairs = int(off[-1])
-        blob = np.frombuffer(b"".join(inputs[i] for i in live) or b"\x00", dtype=np.uint8)
-        d_in, d_off = engine.to_device(blob), engine.to_device(off)
+        # a batch of empty jobs only holds no pair: the entry point takes in = NULL then
+        d_in = engine.to_device(np.frombuffer(b"".join(inputs[i] for i in live), dtype=np.uint8)) if n_pairs else None
+        d_off = engine.to_device(off)
         d_res, d_st = engine.empty((len(live),), np.uint8), engine.empty((len(live),), np.uint8)
-        engine._call("sylow_hip_evm_ecpairing_batch", d_in.ptr, d_off.ptr, len(live), n_pairs, d_res.ptr, d_st.ptr)
+        engine._call("sylow_hip_evm_ecpairing_batch", engine._ptr(d_in), d_off.ptr, len(live), n_pairs, d_res.ptr, d_st.ptr)
         res, st = d_res.download(), d_st.download()
         for j, i in enumerate(live):
             out[i] = PrecompileError(_STATUS[int(st[j])]) if st[j] else int(res[j]).to_bytes(32, "big")

@@ -29,7 +29,7 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FILES = ["tests/test_gpu_pairing.py", "tests/test_gpu_hash_bls.py", "tests/test_gpu_multi_pairing.py", "tests/test_gpu_evm.py",
+FILES = ["tests/test_gpu_pairing.py", "tests/test_gpu_hash_bls.py", "tests/test_gpu_multi_pairing.py", "tests/test_gpu_evm.py", "tests/test_gpu_evm_batches.py",
          "tests/test_gpu_aggregate.py", "tests/test_gpu_lane_pair.py", "tests/test_gpu_precomputed.py", "tests/test_gpu_hash_chain.py", "tests/test_gpu_groups.py",
          "tests/test_gpu_fuzz_invariants.py", "tests/test_gpu_fr_threshold.py", "tests/test_gpu_input_contract.py"]
 ROUTES = [{"SYLOW_HIP_QUAD_MAX": "0"}, {"SYLOW_HIP_TAIL_SPLIT": "0"}, {"SYLOW_HIP_QUAD_MAX": "1048576", "SYLOW_HIP_WIDE_TAIL": "0"}, {"SYLOW_HIP_MULTI_TABLES": "0"}, {"SYLOW_HIP_MULTI_TABLES": "1"}, {"SYLOW_HIP_WIDE_TAIL": "0"}, {"SYLOW_HIP_AGG_FORK": "0"}, {"SYLOW_HIP_STAGGER": "0"},
