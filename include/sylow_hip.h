@@ -473,6 +473,48 @@ int32_t sylow_hip_bls_verify_fused_batch(const uint64_t* pk_xy, const uint8_t* p
 /* @shape pk_xy=u64[16*n] pk_inf=u8[n]? msgs=u8[*] msg_offsets=u64[n+1] sig_xy=u64[8*n] sig_inf=u8[n]? ok=u8[n] */
 int32_t sylow_hip_bls_verify_two_pairings_batch(const uint64_t* pk_xy, const uint8_t* pk_inf, const uint8_t* msgs, const uint64_t* msg_offsets,
                                                 const uint64_t* sig_xy, const uint8_t* sig_inf, uint8_t* ok, size_t n, void* stream);
+/* ---- a caller-chosen RFC 9380 expander and tag: Expander, XMDExpander<D>, XOFExpander<D> (src/lib.rs:71-84, src/hasher.rs) ---------
+ * expander: XMDExpander<Keccak256> (the suite of every entry point above), XMDExpander<Sha256> or XOFExpander<Shake128>, the two the
+ * reference pins with RFC 9380 literals (hasher.rs:345-472).  dst_host / dst_len: HOST pointer to the tag, NULL = the library tag
+ * (lib.rs:90); a tag longer than 255 bytes is shortened once per call as XMDExpander::new / XOFExpander::new do (hasher.rs:157-173,
+ * 274-290: H("H2C-OVERSIZE-DST-" || DST), for the XOF ceil(2 security_bits / 8) bytes of it).  security_bits: the expanders' k
+ * (128 for BN254).  Expander 0 with the same tag gives the bytes, field elements, points and flags of the entry points above, bit for
+ * bit.  The new expanders hash one message per lane at every batch size.
+ * Whole-call errors, the conditions of HashError::ExpandMessage (hasher.rs:211-216) and of i2osp's ranges: an unknown expander,
+ * len_in_bytes > 65535, XMD with ceil(len_in_bytes / 32) > 255 or 2 security_bits > 256, security_bits < 1, XOF with
+ * ceil(2 security_bits / 8) > 255, and len_in_bytes == 0 (there the reference's XMD indexes an empty vector and panics, its XOF returns
+ * no bytes: a divergence) return SYLOW_HIP_E_ARG, launch nothing and name the reason in sylow_hip_last_error(). */
+#define SYLOW_HIP_EXPANDER_XMD_KECCAK256 0
+#define SYLOW_HIP_EXPANDER_XMD_SHA256 1
+#define SYLOW_HIP_EXPANDER_XOF_SHAKE128 2
+/* Expander::expand_message(msg, len_in_bytes) (hasher.rs:201-250 XMD, 315-329 XOF): raw bytes, row i at out + i * len_in_bytes. */
+/* @shape msgs=u8[*] msg_offsets=u64[n+1] dst_host=u8[dst_len]? out=u8[len_in_bytes*n] */
+int32_t sylow_hip_expand_message_batch(int32_t expander, const uint8_t* msgs, const uint64_t* msg_offsets, const uint8_t* dst_host, size_t dst_len,
+                                       int32_t security_bits, size_t len_in_bytes, uint8_t* out, size_t n, void* stream);
+/* Expander::hash_to_field(msg, 2, 48) (hasher.rs:84-128) under the expander: out_u [8][n] = (u0, u1). */
+/* @shape msgs=u8[*] msg_offsets=u64[n+1] dst_host=u8[dst_len]? out_u=u64[8*n] */
+int32_t sylow_hip_hash_to_field_expander_batch(int32_t expander, const uint8_t* msgs, const uint64_t* msg_offsets, const uint8_t* dst_host, size_t dst_len,
+                                               int32_t security_bits, uint64_t* out_u, size_t n, void* stream);
+/* G1Projective::hash_to_curve(&expander, msg) (g1.rs:307-331), affine out. */
+/* @shape msgs=u8[*] msg_offsets=u64[n+1] dst_host=u8[dst_len]? out_xy=u64[8*n] out_inf=u8[n] */
+int32_t sylow_hip_hash_to_g1_expander_batch(int32_t expander, const uint8_t* msgs, const uint64_t* msg_offsets, const uint8_t* dst_host, size_t dst_len,
+                                            int32_t security_bits, uint64_t* out_xy, uint8_t* out_inf, size_t n, void* stream);
+/* sign_message(&expander, msg, sk) (g1.rs:355): sig_i = sk_i * H(msg_i) with H from the expander. */
+/* @shape dst_host=u8[dst_len]? sk=u64[4*n] msgs=u8[*] msg_offsets=u64[n+1] sig_xy=u64[8*n] sig_inf=u8[n] */
+int32_t sylow_hip_bls_sign_expander_batch(int32_t expander, const uint8_t* dst_host, size_t dst_len, int32_t security_bits, const uint64_t* sk,
+                                          const uint8_t* msgs, const uint64_t* msg_offsets, uint64_t* sig_xy, uint8_t* sig_inf, size_t n, void* stream);
+/* The boolean of verify (lib.rs:223-236) with H from the expander: sylow_hip_bls_verify_batch's evaluation, reading of identities and
+ * routes by batch size behind another hashing launch. */
+/* @shape dst_host=u8[dst_len]? pk_xy=u64[16*n] pk_inf=u8[n]? msgs=u8[*] msg_offsets=u64[n+1] sig_xy=u64[8*n] sig_inf=u8[n]? ok=u8[n] */
+int32_t sylow_hip_bls_verify_expander_batch(int32_t expander, const uint8_t* dst_host, size_t dst_len, int32_t security_bits,
+                                            const uint64_t* pk_xy, const uint8_t* pk_inf, const uint8_t* msgs, const uint64_t* msg_offsets,
+                                            const uint64_t* sig_xy, const uint8_t* sig_inf, uint8_t* ok, size_t n, void* stream);
+/* The same boolean on points H_i the caller hashed -- another hash-to-curve, or one hash checked against many signatures:
+ * ok_i = [ e(sig_i, G2gen) == e(H_i, pk_i) ], h_xy [8][n] affine (reduced like Fp::new), identity inputs as pairing() treats them:
+ * h_inf[i] = 1 (h_inf may be NULL) makes the right-hand pairing Gt::identity(), as an identity hash does above. */
+/* @shape pk_xy=u64[16*n] pk_inf=u8[n]? h_xy=u64[8*n] h_inf=u8[n]? sig_xy=u64[8*n] sig_inf=u8[n]? ok=u8[n] */
+int32_t sylow_hip_bls_verify_hashed_batch(const uint64_t* pk_xy, const uint8_t* pk_inf, const uint64_t* h_xy, const uint8_t* h_inf,
+                                          const uint64_t* sig_xy, const uint8_t* sig_inf, uint8_t* ok, size_t n, void* stream);
 /* ---- wire formats: G1Affine/G2Affine::{to,from}_be_bytes (g1.rs:151-280, g2.rs:319-433) -------------- */
 /* G1: 64 bytes x | y big-endian; G2: 128 bytes x.c1 | x.c0 | y.c1 | y.c0; bit 7 of byte 0 is the infinity flag and
  * the identity is written as (0, 1) + flag.  from_be_bytes masks the flag, then: a coordinate >= p, or a set flag

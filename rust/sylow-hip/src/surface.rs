@@ -412,6 +412,115 @@ pub fn hash_to_field_batch(dev: &Device, msgs: &[&[u8]], dst: Option<&[u8]>) -> 
     device::check(unsafe { ffi::sylow_hip_hash_to_field_batch(d_msgs.as_ptr(), d_off.as_ptr(), dst_ptr, dst_len, out.as_mut_ptr(), n, dev.stream) })?;
     Ok(dev.download_aos::<8>(&out, n)?.iter().map(|w| [fp_from_words(&w[0..4]), fp_from_words(&w[4..8])]).collect())
 }
+/// The expanders the library hashes with (`SYLOW_HIP_EXPANDER_*`): sylow's `XMDExpander<Keccak256>`, `XMDExpander<Sha256>` and
+/// `XOFExpander<Shake128>` (lib.rs:71-84, hasher.rs:137-330), each with the caller's tag (`None` = sylow's DST) and security level k.
+#[derive(Clone, Copy, PartialEq, Eq, Debug)]
+pub enum Expander {
+    XmdKeccak256 = 0,
+    XmdSha256 = 1,
+    XofShake128 = 2,
+}
+/// An `Expander` bound to its tag and security level: what `XMDExpander::new(dst, k)` / `XOFExpander::new(dst, k)` hold.
+#[derive(Clone, Copy)]
+pub struct Suite<'a> {
+    pub expander: Expander,
+    pub dst: Option<&'a [u8]>,
+    pub security_bits: i32,
+}
+impl<'a> Suite<'a> {
+    pub fn new(expander: Expander, dst: Option<&'a [u8]>) -> Self {
+        Suite { expander, dst, security_bits: 128 }
+    }
+    fn dst_arg(&self) -> (*const u8, usize) {
+        self.dst.map_or((ptr::null(), 0), |d| (d.as_ptr(), d.len()))
+    }
+}
+/// `Expander::expand_message(msg, len_in_bytes)` (hasher.rs:201-250, 315-329): `len_in_bytes` bytes per message.  The conditions of
+/// `HashError::ExpandMessage` fail the whole call.
+pub fn expand_message_batch(dev: &Device, suite: &Suite, msgs: &[&[u8]], len_in_bytes: usize) -> Result<Vec<Vec<u8>>, HipError> {
+    let n = msgs.len();
+    let (d_msgs, d_off) = messages(dev, msgs)?;
+    let out = dev.alloc::<u8>(len_in_bytes * n)?;
+    let (dst_ptr, dst_len) = suite.dst_arg();
+    // SAFETY: n + 1 offsets into d_msgs; dst is a HOST pointer (read during the call); out holds len_in_bytes * n bytes.
+    device::check(unsafe {
+        ffi::sylow_hip_expand_message_batch(suite.expander as i32, d_msgs.as_ptr(), d_off.as_ptr(), dst_ptr, dst_len, suite.security_bits, len_in_bytes,
+                                            out.as_mut_ptr(), n, dev.stream)
+    })?;
+    let bytes = dev.download(&out)?;
+    Ok(if len_in_bytes == 0 { vec![Vec::new(); n] } else { bytes.chunks(len_in_bytes).map(|c| c.to_vec()).collect() })
+}
+/// `Expander::hash_to_field(msg, 2, 48)` (hasher.rs:84-128) under the suite: two Fp per message.
+pub fn hash_to_field_expander_batch(dev: &Device, suite: &Suite, msgs: &[&[u8]]) -> Result<Vec<[Fp; 2]>, HipError> {
+    let n = msgs.len();
+    let (d_msgs, d_off) = messages(dev, msgs)?;
+    let out = dev.alloc::<u64>(8 * n)?;
+    let (dst_ptr, dst_len) = suite.dst_arg();
+    // SAFETY: as expand_message_batch; out holds 8 * n words.
+    device::check(unsafe {
+        ffi::sylow_hip_hash_to_field_expander_batch(suite.expander as i32, d_msgs.as_ptr(), d_off.as_ptr(), dst_ptr, dst_len, suite.security_bits,
+                                                    out.as_mut_ptr(), n, dev.stream)
+    })?;
+    Ok(dev.download_aos::<8>(&out, n)?.iter().map(|w| [fp_from_words(&w[0..4]), fp_from_words(&w[4..8])]).collect())
+}
+/// `G1Projective::hash_to_curve(&expander, msg)` (g1.rs:307-331) under the suite.
+pub fn hash_to_curve_expander_batch(dev: &Device, suite: &Suite, msgs: &[&[u8]]) -> Result<Vec<G1Projective>, HipError> {
+    let n = msgs.len();
+    let (d_msgs, d_off) = messages(dev, msgs)?;
+    let out = DeviceG1 { xy: dev.alloc::<u64>(8 * n)?, inf: dev.alloc::<u8>(n)?, n };
+    let (dst_ptr, dst_len) = suite.dst_arg();
+    // SAFETY: as expand_message_batch; n outputs.
+    device::check(unsafe {
+        ffi::sylow_hip_hash_to_g1_expander_batch(suite.expander as i32, d_msgs.as_ptr(), d_off.as_ptr(), dst_ptr, dst_len, suite.security_bits,
+                                                 out.xy.as_mut_ptr(), out.inf.as_mut_ptr(), n, dev.stream)
+    })?;
+    download_g1(dev, &out)
+}
+/// `GroupTrait::sign_message(&expander, msg, private_key)` (g1.rs:355-366) under the suite.
+pub fn sign_message_expander_batch(dev: &Device, suite: &Suite, msgs: &[&[u8]], private_keys: &[Fp]) -> Result<Vec<G1Projective>, HipError> {
+    assert_eq!(private_keys.len(), msgs.len());
+    let n = msgs.len();
+    let words: Vec<[u64; 4]> = private_keys.iter().map(|k| k.value().to_words()).collect();
+    let d_sk = dev.upload_soa::<4>(&words)?;
+    let (d_msgs, d_off) = messages(dev, msgs)?;
+    let sig = DeviceG1 { xy: dev.alloc::<u64>(8 * n)?, inf: dev.alloc::<u8>(n)?, n };
+    let (dst_ptr, dst_len) = suite.dst_arg();
+    // SAFETY: sk 4 * n words, offsets n + 1 entries into d_msgs, outputs n elements; dst is a HOST pointer.
+    device::check(unsafe {
+        ffi::sylow_hip_bls_sign_expander_batch(suite.expander as i32, dst_ptr, dst_len, suite.security_bits, d_sk.as_ptr(), d_msgs.as_ptr(), d_off.as_ptr(),
+                                               sig.xy.as_mut_ptr(), sig.inf.as_mut_ptr(), n, dev.stream)
+    })?;
+    download_g1(dev, &sig)
+}
+/// `sylow::verify` (lib.rs:223-236) with H from the suite: ok[i] = [ e(sig[i], G2gen) == e(H(msgs[i]), pk[i]) ].
+pub fn verify_expander_batch(dev: &Device, suite: &Suite, pk: &[G2Affine], msgs: &[&[u8]], sig: &[G1Affine]) -> Result<Vec<bool>, HipError> {
+    assert!(pk.len() == msgs.len() && sig.len() == msgs.len());
+    let n = msgs.len();
+    let (dpk, dsig) = (upload_g2(dev, pk)?, upload_g1(dev, sig)?);
+    let (d_msgs, d_off) = messages(dev, msgs)?;
+    let ok = dev.alloc::<u8>(n)?;
+    let (dst_ptr, dst_len) = suite.dst_arg();
+    // SAFETY: n keys, n signatures, n + 1 offsets, n flags; dst is a HOST pointer.
+    device::check(unsafe {
+        ffi::sylow_hip_bls_verify_expander_batch(suite.expander as i32, dst_ptr, dst_len, suite.security_bits, dpk.xy.as_ptr(), dpk.inf.as_ptr(),
+                                                 d_msgs.as_ptr(), d_off.as_ptr(), dsig.xy.as_ptr(), dsig.inf.as_ptr(), ok.as_mut_ptr(), n, dev.stream)
+    })?;
+    Ok(dev.download(&ok)?.iter().map(|&f| f != 0).collect())
+}
+/// The same check on points the caller hashed (another hash-to-curve, or one hash against many signatures):
+/// ok[i] = [ e(sig[i], G2gen) == e(h[i], pk[i]) ].
+pub fn verify_hashed_batch(dev: &Device, pk: &[G2Affine], h: &[G1Affine], sig: &[G1Affine]) -> Result<Vec<bool>, HipError> {
+    assert!(pk.len() == h.len() && sig.len() == h.len());
+    let n = h.len();
+    let (dpk, dh, dsig) = (upload_g2(dev, pk)?, upload_g1(dev, h)?, upload_g1(dev, sig)?);
+    let ok = dev.alloc::<u8>(n)?;
+    // SAFETY: n keys, n hashes, n signatures, n flags.
+    device::check(unsafe {
+        ffi::sylow_hip_bls_verify_hashed_batch(dpk.xy.as_ptr(), dpk.inf.as_ptr(), dh.xy.as_ptr(), dh.inf.as_ptr(), dsig.xy.as_ptr(), dsig.inf.as_ptr(),
+                                               ok.as_mut_ptr(), n, dev.stream)
+    })?;
+    Ok(dev.download(&ok)?.iter().map(|&f| f != 0).collect())
+}
 /// `SvdW::unchecked_map_to_point` (svdw.rs:180-262): u -> (x, y) on E(Fp); `None` where the reference returns an error.
 pub fn svdw_map_batch(dev: &Device, u: &[Fp]) -> Result<Vec<Option<[Fp; 2]>>, HipError> {
     let n = u.len();

@@ -81,6 +81,12 @@ SIGNATURES = {
     "sylow_hip_bls_verify_batch": [c_u64p, c_u8p, c_u8p, c_u64p, c_u64p, c_u8p, c_u8p, c_sz, c_vp],
     "sylow_hip_bls_verify_two_pairings_batch": [c_u64p, c_u8p, c_u8p, c_u64p, c_u64p, c_u8p, c_u8p, c_sz, c_vp],
     "sylow_hip_bls_verify_fused_batch": [c_u64p, c_u8p, c_u8p, c_u64p, c_u64p, c_u8p, c_u8p, c_sz, c_vp],
+    "sylow_hip_expand_message_batch": [c_i32, c_u8p, c_u64p, ctypes.c_char_p, c_sz, c_i32, c_sz, c_u8p, c_sz, c_vp],
+    "sylow_hip_hash_to_field_expander_batch": [c_i32, c_u8p, c_u64p, ctypes.c_char_p, c_sz, c_i32, c_u64p, c_sz, c_vp],
+    "sylow_hip_hash_to_g1_expander_batch": [c_i32, c_u8p, c_u64p, ctypes.c_char_p, c_sz, c_i32, c_u64p, c_u8p, c_sz, c_vp],
+    "sylow_hip_bls_sign_expander_batch": [c_i32, ctypes.c_char_p, c_sz, c_i32, c_u64p, c_u8p, c_u64p, c_u64p, c_u8p, c_sz, c_vp],
+    "sylow_hip_bls_verify_expander_batch": [c_i32, ctypes.c_char_p, c_sz, c_i32, c_u64p, c_u8p, c_u8p, c_u64p, c_u64p, c_u8p, c_u8p, c_sz, c_vp],
+    "sylow_hip_bls_verify_hashed_batch": [c_u64p, c_u8p, c_u64p, c_u8p, c_u64p, c_u8p, c_u8p, c_sz, c_vp],
     "sylow_hip_evm_ecadd_batch": [c_u8p, c_u8p, c_u8p, c_sz, c_vp],
     "sylow_hip_evm_ecmul_batch": [c_u8p, c_u8p, c_u8p, c_sz, c_vp],
     "sylow_hip_evm_ecpairing_batch": [c_u8p, c_u64p, c_sz, c_sz, c_u8p, c_u8p, c_vp],

@@ -122,8 +122,11 @@ class G1Affine(_Points):
         return cls(np.repeat(_row([0, 1]), n, 0), np.ones(n, dtype=np.uint8))
 
     @classmethod
-    def hash_to_curve(cls, msgs, dst: bytes = DST):     # g1.rs:307-331 with XMDExpander<Keccak256>(dst, 128)
-        xy, inf = engine().hash_to_g1(list(msgs), dst)
+    def hash_to_curve(cls, msgs, dst: bytes = DST, expander=None):     # g1.rs:307-331; expander None: XMDExpander<Keccak256>(dst, 128)
+        if expander is not None:
+            xy, inf = engine().hash_to_g1(list(msgs), expander.dst, expander=expander.id, k=expander.k)
+        else:
+            xy, inf = engine().hash_to_g1(list(msgs), dst)
         return cls(xy, inf)
 
     def __mul__(self, k):                          # Mul<&Fp> (group.rs:639-667)
@@ -513,12 +516,57 @@ class KeyPair:
         return self.secret_key.shape[0]
 
 
-def sign(k, msgs) -> G1Affine:
-    """sign(&Fp, &[u8]) (lib.rs:179-187): H(msg) * k."""
-    xy, inf = engine().bls_sign(k, list(msgs))
+class _Expander:
+    """Expander (hasher.rs:54-129), a tag and a security level bound to one of the library's expanders (SYLOW_HIP_EXPANDER_*)."""
+    id = None
+
+    def __init__(self, dst: bytes, k: int = 128):
+        self.dst, self.k = bytes(dst), int(k)
+
+    def expand_message(self, msgs, n: int) -> np.ndarray:          # expand_message(msg, len_in_bytes): uint8 [len(msgs), n]
+        return engine().expand_message(list(msgs), n, self.id, self.dst, self.k)
+
+    def hash_to_field(self, msgs) -> np.ndarray:                   # hash_to_field(msg, 2, 48) (hasher.rs:84-128): [len(msgs), 8] = (u0, u1)
+        return engine().hash_to_field(list(msgs), self.dst, expander=self.id, k=self.k)
+
+
+class XMDExpander(_Expander):
+    """XMDExpander<D>::new(dst, k) (hasher.rs:137-173) with D = Keccak256 or Sha256."""
+
+    def __init__(self, hash: str, dst: bytes, k: int = 128):
+        if hash not in ("keccak256", "sha256"):
+            raise ValueError("XMDExpander: hash is 'keccak256' or 'sha256'")
+        super().__init__(dst, k)
+        self.id = Engine.EXPANDERS["xmd_" + hash]
+
+
+class XOFExpander(_Expander):
+    """XOFExpander<Shake128>::new(dst, k) (hasher.rs:259-290)."""
+
+    def __init__(self, hash: str, dst: bytes, k: int = 128):
+        if hash != "shake128":
+            raise ValueError("XOFExpander: hash is 'shake128'")
+        super().__init__(dst, k)
+        self.id = Engine.EXPANDERS["xof_shake128"]
+
+
+def sign(k, msgs, expander=None) -> G1Affine:
+    """sign(&Fp, &[u8]) (lib.rs:179-187): H(msg) * k; with an expander, sign_message(&expander, msg, k) (g1.rs:355)."""
+    if expander is not None:
+        xy, inf = engine().bls_sign(k, list(msgs), expander=expander.id, dst=expander.dst, k=expander.k)
+    else:
+        xy, inf = engine().bls_sign(k, list(msgs))
     return G1Affine(xy, inf)
 
 
-def verify(pubkey: G2Affine, msgs, sig: G1Affine) -> np.ndarray:
-    """verify(&G2Projective, &[u8], &G1Projective) (lib.rs:223-236): elementwise bool."""
+def verify(pubkey: G2Affine, msgs, sig: G1Affine, expander=None) -> np.ndarray:
+    """verify(&G2Projective, &[u8], &G1Projective) (lib.rs:223-236): elementwise bool; with an expander, H from that suite."""
+    if expander is not None:
+        return engine().bls_verify(pubkey.xy, list(msgs), sig.xy, pubkey.infinity, sig.infinity, expander=expander.id, dst=expander.dst,
+                                   k=expander.k).astype(bool)
     return engine().bls_verify(pubkey.xy, list(msgs), sig.xy, pubkey.infinity, sig.infinity).astype(bool)
+
+
+def verify_hashed(pubkey: G2Affine, h: G1Affine, sig: G1Affine) -> np.ndarray:
+    """verify on points the caller hashed (any hash-to-curve; one hash against many signatures): e(sig, G2gen) == e(h, pubkey)."""
+    return engine().bls_verify_hashed(pubkey.xy, h.xy, sig.xy, pubkey.infinity, h.infinity, sig.infinity).astype(bool)

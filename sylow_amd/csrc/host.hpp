@@ -102,6 +102,11 @@ int32_t evm_ecmul_wide(const uint8_t* in, uint8_t* out, uint8_t* status, size_t 
 // sign_wide.hip: the same on eight lanes per message (small batches)
 int32_t hash_to_g1_wide(const uint8_t* msgs, const uint64_t* msg_offsets, const DstPrime& dp, uint64_t* out_xy, uint8_t* out_inf, size_t n, int negate, void* stream);
 int32_t hash_to_g1_dst(const uint8_t* msgs, const uint64_t* msg_offsets, const DstPrime& dp, uint64_t* out_xy, uint8_t* out_inf, size_t n, int negate, void* stream);
+// expand.hip: the whole-call conditions of a caller-chosen expander (SYLOW_HIP_EXPANDER_*; E_ARG and the reason in sylow_hip_last_error), and
+// H(m_i) (or -H(m_i)) affine under it with the caller's tag (dst NULL = the library tag); expander 0 is hash_to_g1_dst
+int32_t expander_check(int32_t expander, int32_t security_bits, size_t len_in_bytes);
+int32_t hash_to_g1_expander(int32_t expander, const uint8_t* dst, size_t dst_len, int32_t security_bits, const uint8_t* msgs, const uint64_t* msg_offsets,
+                            uint64_t* out_xy, uint8_t* out_inf, size_t n, int negate, void* stream);
 // sum_i P_i (or its negative) -> column `col` of an affine SoA array of stride `stride`; acc: scratch of 12 n words
 int32_t sum(const uint64_t* p_xy, const uint8_t* p_inf, size_t n, uint64_t* acc, uint64_t* out_xy, uint8_t* out_inf, size_t stride, size_t col, int negate, void* stream);
 // the same from an acc [12][n] that already holds the n projective points

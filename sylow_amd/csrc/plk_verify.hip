@@ -139,6 +139,14 @@ __global__ void HEAVY_BOUNDS k_bls_verify_fused(const u64* pkxy, const uint8_t* 
   bls_verify_fused_body<PK_TABLE>(pkxy, pkinf, pk_table, hneg, hneg_inf, sigxy, siginf, gen_table, okout, n, m, st);
   probe_end(pb, st.clk);
 }
+// -H_i for caller-supplied affine points (sylow_hip_bls_verify_hashed_batch): one Fp negation per element, reduced like Fp::new on the way in
+__global__ void __launch_bounds__(BLOCK) k_g1_negate(const u64* hxy, const uint8_t* hinf, u64* oxy, uint8_t* oinf, size_t n) {
+  const size_t i = TID;
+  if (i >= n) return;
+  store_fp(oxy, n, i, 0, load_fp(hxy, n, i, 0));
+  store_fp(oxy, n, i, 4, fp_neg(load_fp(hxy, n, i, 4)));
+  oinf[i] = (hinf && hinf[i]) ? 1 : 0;
+}
 }  // namespace plk
 
 namespace plkh {
@@ -149,17 +157,18 @@ int32_t build_lines29(const uint64_t* q_xy, size_t n, size_t idx, bn254::i32* ta
 }  // namespace plkh
 
 // The fused check as two launches: -H(m_i) for the batch (hash.hip: k_hash_to_g1, one element per lane, four wavefronts per SIMD, 64 bytes
-// per element through a leased block), then the pairing kernel reading it.
-template <bool PK_TABLE>
-static int32_t launch_fused(const uint64_t* pk_xy, const uint8_t* pk_inf, const bn254::i32* pk_table, const uint8_t* msgs, const uint64_t* msg_offsets,
-                            const DstPrime& dp, const uint64_t* sig_xy, const uint8_t* sig_inf, const bn254::i32* gen, uint8_t* ok, size_t n, void* stream) {
+// per element through a leased block), then the pairing kernel reading it.  hash(h, h_inf, negate) is the hashing step: the library suite
+// (hash_library), a caller-chosen expander and tag, or the negation of points the caller hashed (sylow_hip_bls_verify_hashed_batch).
+template <bool PK_TABLE, class Hash>
+static int32_t launch_fused(const uint64_t* pk_xy, const uint8_t* pk_inf, const bn254::i32* pk_table, Hash&& hash,
+                            const uint64_t* sig_xy, const uint8_t* sig_inf, const bn254::i32* gen, uint8_t* ok, size_t n, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   host::Lease ws;
   int32_t rc = ws.acquire(8 * n * sizeof(u64) + n, st);
   if (rc != SYLOW_HIP_OK) return rc;
   u64* hneg = (u64*)ws.p;
   uint8_t* hinf = (uint8_t*)(hneg + 8 * n);
-  rc = g1h::hash_to_g1(msgs, msg_offsets, hneg, hinf, n, /*negate=*/1, stream);
+  rc = hash(hneg, hinf, /*negate=*/1);
   if (rc == SYLOW_HIP_OK && n <= plkh::quad_batch_max())        // mid-size batches: a lane quad per element (plk_quad.hip)
     rc = plkh::verify_fused_quad(PK_TABLE ? 1 : 0, pk_xy, pk_inf, pk_table, hneg, hinf, sig_xy, sig_inf, gen, ok, n, n, stream);
   else if (rc == SYLOW_HIP_OK)
@@ -177,52 +186,58 @@ static int32_t launch_fused(const uint64_t* pk_xy, const uint8_t* pk_inf, const 
 }
 // Small batches of the per-signature checks: H(m_i) (or -H(m_i)) into a leased block, then check(h, h_inf, scratch): one of plk_multi.hip's
 // one-wavefront-per-element routines, `words` words of scratch per element
-template <class Check>
-static int32_t verify_small(const uint8_t* msgs, const uint64_t* msg_offsets, size_t n, size_t words, int negate, void* stream, Check&& check) {
+template <class Hash, class Check>
+static int32_t verify_small(Hash&& hash, size_t n, size_t words, int negate, void* stream, Check&& check) {
   host::Lease ws;
   int32_t rc = ws.acquire((8 + words) * n * sizeof(u64) + n, (hipStream_t)stream);
   if (rc != SYLOW_HIP_OK) return rc;
   u64* h = (u64*)ws.p;
   u64* scratch = h + 8 * n;
   uint8_t* hinf = (uint8_t*)(scratch + words * n);
-  rc = g1h::hash_to_g1(msgs, msg_offsets, h, hinf, n, negate, stream);
+  rc = hash(h, hinf, negate);
   if (rc == SYLOW_HIP_OK) rc = check(h, hinf, scratch);
   return host::finish(rc, ws);
 }
 
-extern "C" {
+// today's hashing step: XMDExpander<Keccak256> under the library tag
+static auto hash_library(const uint8_t* msgs, const uint64_t* msg_offsets, size_t n, void* stream) {
+  return [=](u64* h, uint8_t* hinf, int negate) { return g1h::hash_to_g1(msgs, msg_offsets, h, hinf, n, negate, stream); };
+}
+
 // verify (lib.rs:223-236): pairing(sig, G2gen) == pairing(H(msg), pk).  The default entry point answers with ONE final
 // exponentiation: FE(a) == FE(b) <=> FE(a conj(b)) == 1 (FE is a homomorphism onto unitary elements, FE(conj b) = FE(b)^-1), and
 // conj(miller(H, pk)) = miller(-H, pk) line by line (negating P negates exactly the line's odd-in-w coefficient) -- for every
 // input, in the subgroup or not.  The literal two-pairing evaluation stays available as *_two_pairings_batch.
-static int32_t verify_one_final_exp(const uint64_t* pk_xy, const uint8_t* pk_inf, const uint8_t* msgs, const uint64_t* msg_offsets,
+template <class Hash>
+static int32_t verify_one_final_exp(const uint64_t* pk_xy, const uint8_t* pk_inf, Hash&& hash,
                                     const uint64_t* sig_xy, const uint8_t* sig_inf, uint8_t* ok, size_t n, void* stream) {
-  ARGCHK(pk_xy && msgs && msg_offsets && sig_xy && ok); if (!n) return SYLOW_HIP_OK;
   // a few verifications are pure latency on one lane pair each (6.8 ms): the same product e(sig, G2gen) e(-H, pk) with the same reading of
   // identities on one wavefront per Miller loop and per final exponentiation (3 ms)
   if (n <= plkh::wide_verify_max())    // small batches: -H(m_i), then a wavefront per Miller loop and per final exponentiation
-    return verify_small(msgs, msg_offsets, n, 96, /*negate=*/1, stream, [&](const u64* hneg, const uint8_t* hinf, u64* scratch) {
+    return verify_small(hash, n, 96, /*negate=*/1, stream, [&](const u64* hneg, const uint8_t* hinf, u64* scratch) {
       return plkh::verify_wide_batch(pk_xy, pk_inf, hneg, hinf, sig_xy, sig_inf, scratch, ok, n, stream);
     });
-  DstPrime dp; host::dst_arg(dp, nullptr, 0);
   const bn254::i32* gen = nullptr;
   int32_t rc = host::gen_lines29(&gen, (hipStream_t)stream);
   if (rc != SYLOW_HIP_OK) return rc;
-  return launch_fused<false>(pk_xy, pk_inf, nullptr, msgs, msg_offsets, dp, sig_xy, sig_inf, gen, ok, n, stream);
+  return launch_fused<false>(pk_xy, pk_inf, nullptr, hash, sig_xy, sig_inf, gen, ok, n, stream);
 }
+extern "C" {
 int32_t sylow_hip_bls_verify_batch(const uint64_t* pk_xy, const uint8_t* pk_inf, const uint8_t* msgs, const uint64_t* msg_offsets,
                                    const uint64_t* sig_xy, const uint8_t* sig_inf, uint8_t* ok, size_t n, void* stream) {
-  return verify_one_final_exp(pk_xy, pk_inf, msgs, msg_offsets, sig_xy, sig_inf, ok, n, stream);
+  ARGCHK(pk_xy && msgs && msg_offsets && sig_xy && ok); if (!n) return SYLOW_HIP_OK;
+  return verify_one_final_exp(pk_xy, pk_inf, hash_library(msgs, msg_offsets, n, stream), sig_xy, sig_inf, ok, n, stream);
 }
 int32_t sylow_hip_bls_verify_fused_batch(const uint64_t* pk_xy, const uint8_t* pk_inf, const uint8_t* msgs, const uint64_t* msg_offsets,
                                          const uint64_t* sig_xy, const uint8_t* sig_inf, uint8_t* ok, size_t n, void* stream) {
-  return verify_one_final_exp(pk_xy, pk_inf, msgs, msg_offsets, sig_xy, sig_inf, ok, n, stream);
+  ARGCHK(pk_xy && msgs && msg_offsets && sig_xy && ok); if (!n) return SYLOW_HIP_OK;
+  return verify_one_final_exp(pk_xy, pk_inf, hash_library(msgs, msg_offsets, n, stream), sig_xy, sig_inf, ok, n, stream);
 }
 int32_t sylow_hip_bls_verify_two_pairings_batch(const uint64_t* pk_xy, const uint8_t* pk_inf, const uint8_t* msgs, const uint64_t* msg_offsets,
                                                 const uint64_t* sig_xy, const uint8_t* sig_inf, uint8_t* ok, size_t n, void* stream) {
   ARGCHK(pk_xy && msgs && msg_offsets && sig_xy && ok); if (!n) return SYLOW_HIP_OK;
   if (n <= plkh::wide_verify_max())    // small batches: H(m_i), a wavefront per one or two Miller loops / final exponentiations, Gt values compared
-    return verify_small(msgs, msg_offsets, n, 192, /*negate=*/0, stream, [&](const u64* h, const uint8_t* hinf, u64* scratch) {
+    return verify_small(hash_library(msgs, msg_offsets, n, stream), n, 192, /*negate=*/0, stream, [&](const u64* h, const uint8_t* hinf, u64* scratch) {
       return plkh::verify_two_pairings_wide_batch(pk_xy, pk_inf, h, hinf, sig_xy, sig_inf, scratch, ok, n, stream);
     });
   DstPrime dp; host::dst_arg(dp, nullptr, 0);
@@ -236,10 +251,9 @@ int32_t sylow_hip_bls_verify_same_signer_batch(const uint64_t* pk_xy, const uint
   ARGCHK(pk_xy && msgs && msg_offsets && sig_xy && ok); if (!n) return SYLOW_HIP_OK;
   hipStream_t st = (hipStream_t)stream;
   if (n <= plkh::wide_verify_max())    // small batches: the one-wavefront route of bls_verify_batch with the one key read by every pair
-    return verify_small(msgs, msg_offsets, n, 96, /*negate=*/1, stream, [&](const u64* hneg, const uint8_t* hinf, u64* scratch) {
+    return verify_small(hash_library(msgs, msg_offsets, n, stream), n, 96, /*negate=*/1, stream, [&](const u64* hneg, const uint8_t* hinf, u64* scratch) {
       return plkh::verify_wide_batch(pk_xy, pk_inf, hneg, hinf, sig_xy, sig_inf, scratch, ok, n, stream, /*one_key=*/1);
     });
-  DstPrime dp; host::dst_arg(dp, nullptr, 0);
   const bn254::i32* gen = nullptr;
   int32_t rc = host::gen_lines29(&gen, st);
   if (rc != SYLOW_HIP_OK) return rc;
@@ -247,7 +261,7 @@ int32_t sylow_hip_bls_verify_same_signer_batch(const uint64_t* pk_xy, const uint
   if ((rc = ws.acquire(plk::LINE_TABLE_WORDS * sizeof(bn254::i32), st)) != SYLOW_HIP_OK) return rc;
   bn254::i32* table = (bn254::i32*)ws.p;
   plk::k_g2_lines29<<<1, plk::LINES_BLOCK, 0, st>>>(pk_xy, 1, 0, table);     // the key is a 1-element SoA array
-  return host::finish(launch_fused<true>(pk_xy, pk_inf, table, msgs, msg_offsets, dp, sig_xy, sig_inf, gen, ok, n, stream), ws);
+  return host::finish(launch_fused<true>(pk_xy, pk_inf, table, hash_library(msgs, msg_offsets, n, stream), sig_xy, sig_inf, gen, ok, n, stream), ws);
 }
 // The same check against a line table the host cached for the key (sylow_hip_g2_line_table: `G2PreComputed` cached per pk,
 // examples/verify_multiple_messages_same_signer.rs:41-60): no G2 arithmetic at all, nothing rebuilt per call.
@@ -259,10 +273,28 @@ int32_t sylow_hip_g2_line_table(const uint64_t* q_xy, size_t n, size_t idx, int3
 int32_t sylow_hip_bls_verify_line_table_batch(const int32_t* pk_table, const uint8_t* pk_inf, const uint8_t* msgs, const uint64_t* msg_offsets,
                                               const uint64_t* sig_xy, const uint8_t* sig_inf, uint8_t* ok, size_t n, void* stream) {
   ARGCHK(pk_table && msgs && msg_offsets && sig_xy && ok); if (!n) return SYLOW_HIP_OK;
-  DstPrime dp; host::dst_arg(dp, nullptr, 0);
   const bn254::i32* gen = nullptr;
   int32_t rc = host::gen_lines29(&gen, (hipStream_t)stream);
   if (rc != SYLOW_HIP_OK) return rc;
-  return launch_fused<true>(nullptr, pk_inf, pk_table, msgs, msg_offsets, dp, sig_xy, sig_inf, gen, ok, n, stream);
+  return launch_fused<true>(nullptr, pk_inf, pk_table, hash_library(msgs, msg_offsets, n, stream), sig_xy, sig_inf, gen, ok, n, stream);
+}
+// verify (lib.rs:223-236) with H from a caller-chosen expander and tag: the hashing launch changes, the routes by size and the pairing kernels do not
+int32_t sylow_hip_bls_verify_expander_batch(int32_t expander, const uint8_t* dst_host, size_t dst_len, int32_t security_bits,
+                                            const uint64_t* pk_xy, const uint8_t* pk_inf, const uint8_t* msgs, const uint64_t* msg_offsets,
+                                            const uint64_t* sig_xy, const uint8_t* sig_inf, uint8_t* ok, size_t n, void* stream) {
+  const int32_t rc = g1h::expander_check(expander, security_bits, 96);
+  if (rc != SYLOW_HIP_OK) return rc;
+  ARGCHK(pk_xy && msgs && msg_offsets && sig_xy && ok); if (!n) return SYLOW_HIP_OK;
+  return verify_one_final_exp(pk_xy, pk_inf, [=](u64* h, uint8_t* hinf, int negate) {
+    return g1h::hash_to_g1_expander(expander, dst_host, dst_len, security_bits, msgs, msg_offsets, h, hinf, n, negate, stream);
+  }, sig_xy, sig_inf, ok, n, stream);
+}
+// the same check on H(m_i) the caller computed (another hash-to-curve; hash once, verify many times): -H_i into the leased block, then the same routes
+int32_t sylow_hip_bls_verify_hashed_batch(const uint64_t* pk_xy, const uint8_t* pk_inf, const uint64_t* h_xy, const uint8_t* h_inf,
+                                          const uint64_t* sig_xy, const uint8_t* sig_inf, uint8_t* ok, size_t n, void* stream) {
+  ARGCHK(pk_xy && h_xy && sig_xy && ok); if (!n) return SYLOW_HIP_OK;
+  return verify_one_final_exp(pk_xy, pk_inf, [=](u64* h, uint8_t* hinf, int) {      // every route of this check asks for -H
+    plk::k_g1_negate<<<GRID(n)>>>(h_xy, h_inf, h, hinf, n); LAUNCHED();
+  }, sig_xy, sig_inf, ok, n, stream);
 }
 }  // extern "C"

@@ -726,32 +726,68 @@ class Engine:
         self._call("sylow_hip_fp_compute_naf_batch", dk.ptr, dp.ptr, dm.ptr, n)
         return self.from_device_soa(dp), self.from_device_soa(dm)
 
-    def hash_to_field(self, msgs, dst: bytes | None = None):
+    EXPANDERS = {"xmd_keccak256": 0, "xmd_sha256": 1, "xof_shake128": 2}     # SYLOW_HIP_EXPANDER_*
+
+    @classmethod
+    def _expander_id(cls, expander):
+        return cls.EXPANDERS[expander] if isinstance(expander, str) else int(expander)
+
+    def expand_message(self, msgs, length: int, expander=0, dst: bytes | None = None, k: int = 128):
+        """Expander::expand_message under an RFC 9380 expander (a name of EXPANDERS or its id): uint8 [n, length]."""
+        n = len(msgs)
+        dm, doff = self._msgs(msgs)
+        do = self.empty((n, max(length, 0)), np.uint8)
+        self._call("sylow_hip_expand_message_batch", self._expander_id(expander), dm.ptr, doff.ptr, dst, len(dst) if dst else 0, k, length, do.ptr, n)
+        return do.download()
+
+    def hash_to_field(self, msgs, dst: bytes | None = None, expander=None, k: int = 128):
         n = len(msgs)
         dm, doff = self._msgs(msgs)
         do = self.empty((8, n))
-        self._call("sylow_hip_hash_to_field_batch", dm.ptr, doff.ptr, dst, len(dst) if dst else 0, do.ptr, n)
+        if expander is None:
+            self._call("sylow_hip_hash_to_field_batch", dm.ptr, doff.ptr, dst, len(dst) if dst else 0, do.ptr, n)
+        else:
+            self._call("sylow_hip_hash_to_field_expander_batch", self._expander_id(expander), dm.ptr, doff.ptr, dst, len(dst) if dst else 0, k, do.ptr, n)
         return self.from_device_soa(do)
 
-    def hash_to_g1(self, msgs, dst: bytes | None = None):
+    def hash_to_g1(self, msgs, dst: bytes | None = None, expander=None, k: int = 128):
         n = len(msgs)
         dm, doff = self._msgs(msgs)
         do, doi = self.empty((8, n)), self.empty((n,), np.uint8)
-        self._call("sylow_hip_hash_to_g1_batch", dm.ptr, doff.ptr, dst, len(dst) if dst else 0, do.ptr, doi.ptr, n)
+        if expander is None:
+            self._call("sylow_hip_hash_to_g1_batch", dm.ptr, doff.ptr, dst, len(dst) if dst else 0, do.ptr, doi.ptr, n)
+        else:
+            self._call("sylow_hip_hash_to_g1_expander_batch", self._expander_id(expander), dm.ptr, doff.ptr, dst, len(dst) if dst else 0, k, do.ptr, doi.ptr, n)
         return self.from_device_soa(do), doi.download()
 
-    def bls_sign(self, sk, msgs):
+    def bls_sign(self, sk, msgs, expander=None, dst: bytes | None = None, k: int = 128):
         sk = _aos(sk, 4)
         n = len(msgs)
         dm, doff = self._msgs(msgs)
         dsk = self.to_device_soa(sk, 4)
         do, doi = self.empty((8, n)), self.empty((n,), np.uint8)
-        self._call("sylow_hip_bls_sign_batch", dsk.ptr, dm.ptr, doff.ptr, do.ptr, doi.ptr, n)
+        if expander is None and dst is None:
+            self._call("sylow_hip_bls_sign_batch", dsk.ptr, dm.ptr, doff.ptr, do.ptr, doi.ptr, n)
+        else:
+            self._call("sylow_hip_bls_sign_expander_batch", self._expander_id(expander or 0), dst, len(dst) if dst else 0, k, dsk.ptr, dm.ptr, doff.ptr,
+                       do.ptr, doi.ptr, n)
         return self.from_device_soa(do), doi.download()
 
-    def bls_verify(self, pk_xy, msgs, sig_xy, pk_inf=None, sig_inf=None, fused=False, two_pairings=False, pipelined=True, chunk=0):
+    def bls_verify_hashed(self, pk_xy, h_xy, sig_xy, pk_inf=None, h_inf=None, sig_inf=None):
+        """verify (lib.rs:223-236) on points H_i the caller hashed: ok_i = [ e(sig_i, G2gen) == e(H_i, pk_i) ]."""
+        pk_xy, h_xy, sig_xy = _aos(pk_xy, 16), _aos(h_xy, 8), _aos(sig_xy, 8)
+        n = h_xy.shape[0]
+        dpk, dh, dsig = self.to_device_soa(pk_xy, 16), self.to_device_soa(h_xy, 8), self.to_device_soa(sig_xy, 8)
+        dpi, dhi, dsi = self._flags(pk_inf, n), self._flags(h_inf, n), self._flags(sig_inf, n)
+        dok = self.empty((n,), np.uint8)
+        self._call("sylow_hip_bls_verify_hashed_batch", dpk.ptr, self._ptr(dpi), dh.ptr, self._ptr(dhi), dsig.ptr, self._ptr(dsi), dok.ptr, n)
+        return dok.download()
+
+    def bls_verify(self, pk_xy, msgs, sig_xy, pk_inf=None, sig_inf=None, fused=False, two_pairings=False, pipelined=True, chunk=0,
+                   expander=None, dst: bytes | None = None, k: int = 128):
         """verify (lib.rs:223-236).  Default and `fused`: one final exponentiation per element; `two_pairings`: the literal form.
         The default form runs through the chunked host pipeline (sylow_hip_bls_verify_host) unless `pipelined=False`.
+        `expander` / `dst`: H from another RFC 9380 suite (sylow_hip_bls_verify_expander_batch: one launch sequence, no host pipeline).
         `msgs`: a list of bytes, or a (blob uint8 array, offsets uint64 [n + 1]) pair."""
         pk_xy, sig_xy = _aos(pk_xy, 16), _aos(sig_xy, 8)
         if isinstance(msgs, tuple):
@@ -760,7 +796,10 @@ class Engine:
         else:
             n = len(msgs)
             blob, off = None, None
-        if pipelined and not two_pairings and not fused:
+        by_expander = expander is not None or dst is not None
+        if by_expander and (fused or two_pairings):
+            raise ValueError("bls_verify: expander / dst go with the default evaluation only")
+        if pipelined and not two_pairings and not fused and not by_expander:
             if blob is None:
                 blob = np.frombuffer(b"".join(msgs) or b"\0", dtype=np.uint8)
                 off = np.zeros(n + 1, dtype=np.uint64)
@@ -779,6 +818,10 @@ class Engine:
         dpk, dsig = self.to_device_soa(pk_xy, 16), self.to_device_soa(sig_xy, 8)
         dpi, dsi = self._flags(pk_inf, n), self._flags(sig_inf, n)
         dok = self.empty((n,), np.uint8)
+        if by_expander:
+            self._call("sylow_hip_bls_verify_expander_batch", self._expander_id(expander or 0), dst, len(dst) if dst else 0, k,
+                       dpk.ptr, self._ptr(dpi), dm.ptr, doff.ptr, dsig.ptr, self._ptr(dsi), dok.ptr, n)
+            return dok.download()
         name = "sylow_hip_bls_verify_two_pairings_batch" if two_pairings else "sylow_hip_bls_verify_fused_batch" if fused else "sylow_hip_bls_verify_batch"
         self._call(name, dpk.ptr, self._ptr(dpi), dm.ptr, doff.ptr, dsig.ptr, self._ptr(dsi), dok.ptr, n)
         return dok.download()

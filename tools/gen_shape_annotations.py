@@ -94,6 +94,12 @@ S["bls_sign_batch"] = "sk=u64[4*n] " + MSG + " sig_xy=u64[8*n] sig_inf=u8[n]"
 VER = "pk_xy=u64[16*n] pk_inf=u8[n]? " + MSG + " sig_xy=u64[8*n] sig_inf=u8[n]? ok=u8[n]"
 for v in ("bls_verify_batch", "bls_verify_fused_batch", "bls_verify_two_pairings_batch"):
     S[v] = VER
+S["expand_message_batch"] = MSG + " dst_host=u8[dst_len]? out=u8[len_in_bytes*n]"
+S["hash_to_field_expander_batch"] = MSG + " dst_host=u8[dst_len]? out_u=u64[8*n]"
+S["hash_to_g1_expander_batch"] = MSG + " dst_host=u8[dst_len]? out_xy=u64[8*n] out_inf=u8[n]"
+S["bls_sign_expander_batch"] = "dst_host=u8[dst_len]? sk=u64[4*n] " + MSG + " sig_xy=u64[8*n] sig_inf=u8[n]"
+S["bls_verify_expander_batch"] = "dst_host=u8[dst_len]? " + VER
+S["bls_verify_hashed_batch"] = "pk_xy=u64[16*n] pk_inf=u8[n]? h_xy=u64[8*n] h_inf=u8[n]? sig_xy=u64[8*n] sig_inf=u8[n]? ok=u8[n]"
 S["bls_verify_same_signer_batch"] = "pk_xy=u64[16] pk_inf=u8[1]? " + MSG + " sig_xy=u64[8*n] sig_inf=u8[n]? ok=u8[n]"
 S["g2_line_table"] = "q_xy=u64[16*n]? table=i32[*]"
 S["bls_verify_line_table_batch"] = "pk_table=i32[*] pk_inf=u8[1]? " + MSG + " sig_xy=u64[8*n] sig_inf=u8[n]? ok=u8[n]"
