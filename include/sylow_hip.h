@@ -355,6 +355,39 @@ int32_t sylow_hip_g2_normalize_batch(const uint64_t* p_xyz, uint64_t* out_xy, ui
  * out_xy [8][1] + out_inf [1] out; n = 0 gives the identity.  Serial per-lane accumulation in stages (g1.hip), complete formulas. */
 /* @shape p_xy=u64[8*n] p_inf=u8[n]? out_xy=u64[8] out_inf=u8[1] */
 int32_t sylow_hip_g1_sum_batch(const uint64_t* p_xy, const uint8_t* p_inf, size_t n, uint64_t* out_xy, uint8_t* out_inf, void* stream);
+/* ---- G2: many points into one (g2_msm.hpp, compiled with plk_group.hip).  Public keys are G2 points (lib.rs, examples/dkg.rs:37-49): dkg.rs:309-314 folds keys with `+`,
+ * a threshold group key is sum_i lambda_i pk_i, a rogue-key-safe aggregate key is sum_i t_i pk_i, and the G2 half of a KZG or Groth16 verifier
+ * is a G2 multi-scalar multiplication.  All four calls are stream-ordered with no host synchronisation, and points are taken as given: no
+ * on-curve check, no subgroup check.
+ * THE SCALAR RULE is that of sylow_hip_g2_scalar_mul_batch, not that of the G1 calls above: k is an Fp value, k >= p is reduced like Fp::new,
+ * and the product is EXACT ON THE WHOLE TWIST -- there is no reduction mod r anywhere (a twist point need not have order r), and there is no
+ * "subgroup" variant. */
+/* sum_i Q_i as ONE G2 point: q_xy [16][n] affine + optional flags in, out_xy [16][1] + out_inf [1] out; n = 0 gives the identity (0, 1, inf).
+ * The segmented lane-pair sum of the committee verifier with one segment, complete formulas. */
+/* @shape q_xy=u64[16*n] q_inf=u8[n]? out_xy=u64[16] out_inf=u8[1] */
+int32_t sylow_hip_g2_sum_batch(const uint64_t* q_xy, const uint8_t* q_inf, size_t n, uint64_t* out_xy, uint8_t* out_inf, void* stream);
+/* n_jobs independent sums sum_i k_{j,i} * Q_{j,i} of n_terms terms each, term-major exactly like sylow_hip_g1_lincomb_batch (element (job j,
+ * term i) at index i*n_jobs + j): p_xy [16][n_jobs*n_terms], k [4][n_jobs*n_terms], out [16][n_jobs] affine + flags.  n_terms = 0 yields
+ * identities.  A scalar multiplication per lane pair, then the segmented sum. */
+/* @shape p_xy=u64[16*n_jobs*n_terms] p_inf=u8[n_jobs*n_terms]? k=u64[4*n_jobs*n_terms] out_xy=u64[16*n_jobs] out_inf=u8[n_jobs] */
+int32_t sylow_hip_g2_lincomb_batch(const uint64_t* p_xy, const uint8_t* p_inf, const uint64_t* k, uint64_t* out_xy, uint8_t* out_inf,
+                                   size_t n_jobs, size_t n_terms, void* stream);
+/* sum_i k_i * Q_i as ONE G2 point, bucket method on lane pairs: p_xy [16][n] affine + optional flags, k [4][n], out [16][1] affine +
+ * out_inf [1].  n = 0 gives the identity.  Output bit-identical to sylow_hip_g2_lincomb_batch(..., n_jobs = 1, n_terms = n) on every route
+ * (both are the canonical affine words of the same group element).  Scratch: about 160 + 14.8 W bytes per point and 448 bytes per bucket
+ * (W windows of 2^(c-1) buckets); under sylow_hip_set_scratch_limit the points go through in chunks that fit, every chunk adding into the
+ * same buckets. */
+/* @shape p_xy=u64[16*n] p_inf=u8[n]? k=u64[4*n] out_xy=u64[16] out_inf=u8[1] */
+int32_t sylow_hip_g2_msm(const uint64_t* p_xy, const uint8_t* p_inf, const uint64_t* k, size_t n,
+                         uint64_t* out_xy, uint8_t* out_inf, void* stream);
+/* The same with the plan given explicitly; a value < 0 is the default sylow_hip_g2_msm uses.  window: the width c (4..16, else
+ * SYLOW_HIP_E_ARG), default as for sylow_hip_g1_msm_tuned below n = 2^16 and 15 from there on (measured).  min_n: the smallest n sent to the
+ * bucket route, default 2^16 = 65536 (measured);
+ * below it, or under a scratch limit too small for one chunk, sylow_hip_g2_scalar_mul_batch and the segmented sum (0: the bucket route for
+ * every n >= 1).  The output does not depend on either. */
+/* @shape p_xy=u64[16*n] p_inf=u8[n]? k=u64[4*n] out_xy=u64[16] out_inf=u8[1] */
+int32_t sylow_hip_g2_msm_tuned(const uint64_t* p_xy, const uint8_t* p_inf, const uint64_t* k, size_t n, int32_t window, int64_t min_n,
+                               uint64_t* out_xy, uint8_t* out_inf, void* stream);
 /* G1Affine::new (g1.rs:111-132): status[i] = OK when y^2 == x^3 + 3 (or the identity flag is set), NOT_ON_CURVE otherwise */
 /* @shape p_xy=u64[8*n] p_inf=u8[n]? status=u8[n] */
 int32_t sylow_hip_g1_on_curve_batch(const uint64_t* p_xy, const uint8_t* p_inf, uint8_t* status, size_t n, void* stream);

@@ -225,6 +225,38 @@ inline G1Affine msm(const std::vector<G1Affine>& p, const std::vector<Fp>& k, bo
   if (infinity) *infinity = flag != 0;
   return r;
 }
+// The G2 twins (public keys), under names of their own so that msm({}, {}) stays unambiguous: k is an Fp value and the products are exact on the whole twist, as sylow_hip_g2_scalar_mul_batch.
+inline std::vector<G2Affine> g2_aggregate(const std::vector<G2Affine>& p, const std::vector<Fp>& k, size_t n_jobs, size_t n_terms) {
+  if (p.size() != n_jobs * n_terms || k.size() != p.size()) throw Error("aggregate: shape mismatch");
+  auto dp = to_device_soa(p); auto dk = to_device_soa(k);
+  DeviceBuffer dout(n_jobs * sizeof(G2Affine) + 8), dinf(n_jobs + 8);
+  check(sylow_hip_g2_lincomb_batch(dp.as<uint64_t>(), nullptr, dk.as<uint64_t>(), dout.as<uint64_t>(), dinf.as<uint8_t>(), n_jobs, n_terms, nullptr), "sylow_hip_g2_lincomb_batch");
+  return from_device_soa<G2Affine>(dout, n_jobs);
+}
+// sum_i k[i] * Q[i] as one G2 point by the bucket method (sylow_hip_g2_msm_tuned); same point as g2_aggregate(p, k, 1, p.size())
+inline G2Affine g2_msm(const std::vector<G2Affine>& p, const std::vector<Fp>& k, bool* infinity = nullptr, int32_t window = -1, int64_t min_n = -1) {
+  if (k.size() != p.size()) throw Error("msm: shape mismatch");
+  auto dp = to_device_soa(p); auto dk = to_device_soa(k);
+  DeviceBuffer dout(sizeof(G2Affine) + 8), dinf(8);
+  check(sylow_hip_g2_msm_tuned(dp.as<uint64_t>(), nullptr, dk.as<uint64_t>(), p.size(), window, min_n, dout.as<uint64_t>(), dinf.as<uint8_t>(), nullptr),
+        "sylow_hip_g2_msm_tuned");
+  uint8_t flag = 0;
+  check(sylow_hip_memcpy_d2h(&flag, dinf.as<void>(), 1, nullptr), "d2h");
+  const G2Affine r = from_device_soa<G2Affine>(dout, 1)[0];       // synchronises the stream
+  if (infinity) *infinity = flag != 0;
+  return r;
+}
+// sum_i Q[i] as one G2 point (sylow_hip_g2_sum_batch): the `+` fold over public keys
+inline G2Affine g2_sum(const std::vector<G2Affine>& q, bool* infinity = nullptr) {
+  auto dq = to_device_soa(q);
+  DeviceBuffer dout(sizeof(G2Affine) + 8), dinf(8);
+  check(sylow_hip_g2_sum_batch(dq.as<uint64_t>(), nullptr, q.size(), dout.as<uint64_t>(), dinf.as<uint8_t>(), nullptr), "sylow_hip_g2_sum_batch");
+  uint8_t flag = 0;
+  check(sylow_hip_memcpy_d2h(&flag, dinf.as<void>(), 1, nullptr), "d2h");
+  const G2Affine r = from_device_soa<G2Affine>(dout, 1)[0];       // synchronises the stream
+  if (infinity) *infinity = flag != 0;
+  return r;
+}
 struct Messages {                                    // concatenated bytes + offsets on the device
   DeviceBuffer bytes, offsets; size_t n;
   explicit Messages(const std::vector<std::vector<uint8_t>>& msgs) : bytes(total(msgs) + 8), offsets((msgs.size() + 1) * 8), n(msgs.size()) {

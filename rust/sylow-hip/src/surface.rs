@@ -932,6 +932,52 @@ pub fn g1_sum(dev: &Device, p: &DeviceG1) -> Result<G1Projective, HipError> {
     Ok(download_g1(dev, &out)?.remove(0))
 }
 
+/// sum_i q[i] as one G2 point (`sylow_hip_g2_sum_batch`): the `+` fold of examples/dkg.rs:309-314 over a resident batch of public keys.
+pub fn g2_sum(dev: &Device, q: &DeviceG2) -> Result<DeviceG2, HipError> {
+    let out = DeviceG2 { xy: dev.alloc::<u64>(16)?, inf: dev.alloc::<u8>(1)?, n: 1 };
+    // SAFETY: q holds q.n points and flags; out one point and one flag.
+    device::check(unsafe { ffi::sylow_hip_g2_sum_batch(q.xy.as_ptr(), q.inf.as_ptr(), q.n, out.xy.as_mut_ptr(), out.inf.as_mut_ptr(), dev.stream) })?;
+    Ok(out)
+}
+/// n_jobs weighted sums sum_i k[j][i] * q[j][i] in G2 (`sylow_hip_g2_lincomb_batch`: a threshold group key sum_i lambda_i pk_i), term-major
+/// input: element (job j, term i) at index i * n_jobs + j.  Scalars are Fp values and the products are exact on the whole twist.
+pub fn g2_lincomb(dev: &Device, q: &DeviceG2, k: &[Fp], n_jobs: usize, n_terms: usize) -> Result<DeviceG2, HipError> {
+    assert!(q.n == n_jobs * n_terms && k.len() == q.n);
+    let dk = dev.upload_soa::<4>(&fp_words(k))?;
+    let out = DeviceG2 { xy: dev.alloc::<u64>(16 * n_jobs)?, inf: dev.alloc::<u8>(n_jobs)?, n: n_jobs };
+    // SAFETY: n_jobs * n_terms points and scalars, n_jobs outputs.
+    device::check(unsafe {
+        ffi::sylow_hip_g2_lincomb_batch(q.xy.as_ptr(), q.inf.as_ptr(), dk.as_ptr(), out.xy.as_mut_ptr(), out.inf.as_mut_ptr(), n_jobs, n_terms, dev.stream)
+    })?;
+    Ok(out)
+}
+/// sum_i k[i] * q[i] as one G2 point by the bucket method (`sylow_hip_g2_msm`: a rogue-key-safe aggregate key sum_i t_i pk_i, the G2 half of
+/// a KZG verifier); the same point as `g2_lincomb(dev, q, k, 1, q.n)`.
+pub fn g2_msm(dev: &Device, q: &DeviceG2, k: &[Fp]) -> Result<DeviceG2, HipError> {
+    assert!(k.len() == q.n);
+    let n = q.n;
+    let dk = dev.upload_soa::<4>(&fp_words(k))?;
+    let out = DeviceG2 { xy: dev.alloc::<u64>(16)?, inf: dev.alloc::<u8>(1)?, n: 1 };
+    // SAFETY: n points and scalars (possibly empty), one output point.
+    device::check(unsafe {
+        ffi::sylow_hip_g2_msm(q.xy.as_ptr(), q.inf.as_ptr(), dk.as_ptr(), n, out.xy.as_mut_ptr(), out.inf.as_mut_ptr(), dev.stream)
+    })?;
+    Ok(out)
+}
+/// `g2_msm` with the plan pinned (`sylow_hip_g2_msm_tuned`): window width 4..16 and the smallest n on the bucket route; < 0 = the
+/// defaults.  The point does not depend on either.
+pub fn g2_msm_tuned(dev: &Device, q: &DeviceG2, k: &[Fp], window: i32, min_n: i64) -> Result<DeviceG2, HipError> {
+    assert!(k.len() == q.n);
+    let n = q.n;
+    let dk = dev.upload_soa::<4>(&fp_words(k))?;
+    let out = DeviceG2 { xy: dev.alloc::<u64>(16)?, inf: dev.alloc::<u8>(1)?, n: 1 };
+    // SAFETY: n points and scalars (possibly empty), one output point.
+    device::check(unsafe {
+        ffi::sylow_hip_g2_msm_tuned(q.xy.as_ptr(), q.inf.as_ptr(), dk.as_ptr(), n, window, min_n, out.xy.as_mut_ptr(), out.inf.as_mut_ptr(), dev.stream)
+    })?;
+    Ok(out)
+}
+
 /// Upper bound for the line tables of the multi-pair routes (`sylow_hip_set_scratch_limit`; 0 = the default of 12 GB): the one scratch
 /// user whose size is not proportional to its input.  Process-wide; results do not depend on it.
 pub fn set_scratch_limit(bytes: usize) -> Result<(), device::Error> {

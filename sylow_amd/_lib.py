@@ -151,6 +151,10 @@ SIGNATURES = {
     "sylow_hip_g1_sum_batch": [c_u64p, c_u8p, c_sz, c_u64p, c_u8p, c_vp],
     "sylow_hip_g1_msm": [c_u64p, c_u8p, c_u64p, c_sz, c_u64p, c_u8p, c_vp],
     "sylow_hip_g1_msm_tuned": [c_u64p, c_u8p, c_u64p, c_sz, c_i32, ctypes.c_int64, c_u64p, c_u8p, c_vp],
+    "sylow_hip_g2_sum_batch": [c_u64p, c_u8p, c_sz, c_u64p, c_u8p, c_vp],
+    "sylow_hip_g2_lincomb_batch": [c_u64p, c_u8p, c_u64p, c_u64p, c_u8p, c_sz, c_sz, c_vp],
+    "sylow_hip_g2_msm": [c_u64p, c_u8p, c_u64p, c_sz, c_u64p, c_u8p, c_vp],
+    "sylow_hip_g2_msm_tuned": [c_u64p, c_u8p, c_u64p, c_sz, c_i32, ctypes.c_int64, c_u64p, c_u8p, c_vp],
     "sylow_hip_pairing_host": [c_u64p, c_u8p, c_u64p, c_u8p, c_u64p, c_sz, c_sz],
     "sylow_hip_bls_verify_host": [c_u64p, c_u8p, c_u8p, c_u64p, c_u64p, c_u8p, c_u8p, c_sz, c_sz],
     "sylow_hip_pairing_host_bytes": [c_u8p, c_u8p, c_u64p, c_u8p, c_u8p, c_sz, c_sz],

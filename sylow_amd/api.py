@@ -364,21 +364,39 @@ class Fr:
         return cls(_random_scalars(n, seed))
 
 
-def aggregate(points: "G1Affine", weights: "Fr", n_jobs: int, n_terms: int) -> "G1Affine":
+def aggregate(points, weights: "Fr", n_jobs: int, n_terms: int):
     """sum_i weights[j,i] * points[j,i] per job (examples/threshold_signing.rs:124-143); rows are term-major
-    (row i*n_jobs + j is term i of job j)."""
+    (row i*n_jobs + j is term i of job j).  G1Affine in, G1Affine out; G2Affine in (public keys: a threshold group key
+    sum_i lambda_i pk_i), G2Affine out."""
+    if isinstance(points, G2Affine):
+        xy, inf = engine().g2_lincomb(points.xy, weights.v, n_jobs, n_terms, points.infinity)
+        return G2Affine(xy, inf)
     xy, inf = engine().g1_lincomb(points.xy, weights.v, n_jobs, n_terms, points.infinity)
     return G1Affine(xy, inf)
 
 
-def msm(points: "G1Affine", scalars) -> "G1Affine":
+def msm(points, scalars):
     """sum_i scalars[i] * points[i] as one point (bucket method on the GPU): KZG-style commitments, random linear combinations,
     weighted aggregation over a whole batch.  scalars: Fr, or [n, 4] Fp words (values >= p are reduced like Fp::new).  Same
-    point as aggregate(points, scalars, 1, n)."""
+    point as aggregate(points, scalars, 1, n).  G1Affine in, G1Affine out; G2Affine in (a rogue-key-safe aggregate key
+    sum_i t_i pk_i, the G2 half of a KZG verifier), G2Affine out."""
     v = scalars.v if isinstance(scalars, Fr) else np.ascontiguousarray(scalars, dtype=np.uint64).reshape(-1, 4)
     if len(points) != v.shape[0]:
         raise ValueError(f"msm: {len(points)} points but {v.shape[0]} scalars")
+    if isinstance(points, G2Affine):
+        xy, inf = engine().g2_msm(points.xy, v, points.infinity)
+        return G2Affine(xy, inf)
     xy, inf = engine().g1_msm(points.xy, v, points.infinity)
+    return G1Affine(xy, inf)
+
+
+def point_sum(points):
+    """sum_i points[i] as one point of the same type (the `+` fold of examples/dkg.rs:309-314 over keys, of
+    examples/verify_multiple_messages_same_signer.rs:41-60 over signatures)."""
+    if isinstance(points, G2Affine):
+        xy, inf = engine().g2_sum(points.xy, points.infinity)
+        return G2Affine(xy, inf)
+    xy, inf = engine().g1_sum(points.xy, points.infinity)
     return G1Affine(xy, inf)
 
 

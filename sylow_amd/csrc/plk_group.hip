@@ -840,3 +840,5 @@ int32_t sylow_hip_g2_double_batch(const uint64_t* a_xy, const uint8_t* a_inf, ui
   plk::k_g2_double<<<GRID(2 * n)>>>(a_xy, a_inf, out_xy, out_inf, n); LAUNCHED();
 }
 }  // extern "C"
+
+#include "g2_msm.hpp"      // sylow_hip_g2_sum_batch, _lincomb_batch, _msm, _msm_tuned: built on the group law and the segmented sum above

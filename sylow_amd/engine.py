@@ -496,6 +496,46 @@ class Engine:
             self._call("sylow_hip_g1_msm_tuned", self._ptr(dp), self._ptr(dpi), self._ptr(dk), n, int(window), int(min_n), do.ptr, doi.ptr)
         return self.from_device_soa(do), doi.download()
 
+    def g2_sum(self, q_xy, q_inf=None):
+        """sum_i Q_i as one G2 point (the `+` fold over public keys of examples/dkg.rs:309-314): ([1, 16] affine words, [1] flag)."""
+        q_xy = _aos(q_xy, 16)
+        n = q_xy.shape[0]
+        dq = self.to_device_soa(q_xy, 16) if n else None
+        dqi = self._flags(q_inf, n) if n else None
+        do, doi = self.empty((16, 1)), self.empty((1,), np.uint8)
+        self._call("sylow_hip_g2_sum_batch", self._ptr(dq), self._ptr(dqi), n, do.ptr, doi.ptr)
+        return self.from_device_soa(do), doi.download()
+
+    def g2_lincomb(self, p_xy, k, n_jobs, n_terms, p_inf=None):
+        """sum_i k[j,i] * Q[j,i] in G2; inputs term-major: row i*n_jobs + j is term i of job j.  k >= p is reduced like Fp::new and the
+        products are exact on the whole twist (no reduction mod r)."""
+        p_xy, k = _aos(p_xy, 16), _aos(k, 4)
+        n = n_jobs * n_terms
+        assert p_xy.shape[0] == n and k.shape[0] == n
+        dp = self.to_device_soa(p_xy, 16) if n else None
+        dk = self.to_device_soa(k, 4) if n else None
+        di = self._flags(p_inf, n) if n else None
+        do, doi = self.empty((16, n_jobs)), self.empty((n_jobs,), np.uint8)
+        self._call("sylow_hip_g2_lincomb_batch", self._ptr(dp), self._ptr(di), self._ptr(dk), do.ptr, doi.ptr, n_jobs, n_terms)
+        return self.from_device_soa(do), doi.download()
+
+    def g2_msm(self, p_xy, k, p_inf=None, window=-1, min_n=-1):
+        """sum_i k_i * Q_i as one G2 point by the bucket method (sylow_hip_g2_msm): ([1, 16] affine words, [1] flag), bit-identical to
+        g2_lincomb(p_xy, k, 1, n).  k: [n, 4] Fp words (k >= p is reduced like Fp::new; exact on the whole twist).  window / min_n >= 0
+        pin the plan (sylow_hip_g2_msm_tuned: window width 4..16, smallest n on the bucket route); < 0 = the defaults."""
+        p_xy, k = _aos(p_xy, 16), _aos(k, 4)
+        n = p_xy.shape[0]
+        assert k.shape[0] == n
+        dp = self.to_device_soa(p_xy, 16) if n else None
+        dk = self.to_device_soa(k, 4) if n else None
+        dpi = self._flags(p_inf, n) if n else None
+        do, doi = self.empty((16, 1)), self.empty((1,), np.uint8)
+        if window < 0 and min_n < 0:
+            self._call("sylow_hip_g2_msm", self._ptr(dp), self._ptr(dpi), self._ptr(dk), n, do.ptr, doi.ptr)
+        else:
+            self._call("sylow_hip_g2_msm_tuned", self._ptr(dp), self._ptr(dpi), self._ptr(dk), n, int(window), int(min_n), do.ptr, doi.ptr)
+        return self.from_device_soa(do), doi.download()
+
     def pairing(self, p_xy, q_xy, p_inf=None, q_inf=None, pipelined=True, chunk=0, out=None):
         """pairing() (pairing.rs:870-893) on host arrays: [n, 8] / [n, 16] words in, [n, 48] Gt words out.  Default: the chunked,
         double-buffered host pipeline (sylow_hip_pairing_host: the copies of chunk k - 1 / k + 1 run beside the kernels of chunk k);

@@ -70,6 +70,9 @@ S["g2_scalar_mul_subgroup_batch"] = S["g2_scalar_mul_batch"]
 S["g1_lincomb_batch"] = "p_xy=u64[8*n_jobs*n_terms] p_inf=u8[n_jobs*n_terms]? k=u64[4*n_jobs*n_terms] out_xy=u64[8*n_jobs] out_inf=u8[n_jobs]"
 S["g1_msm"] = S["g1_msm_tuned"] = "p_xy=u64[8*n] p_inf=u8[n]? k=u64[4*n] out_xy=u64[8] out_inf=u8[1]"
 S["g1_sum_batch"] = "p_xy=u64[8*n] p_inf=u8[n]? out_xy=u64[8] out_inf=u8[1]"
+S["g2_lincomb_batch"] = "p_xy=u64[16*n_jobs*n_terms] p_inf=u8[n_jobs*n_terms]? k=u64[4*n_jobs*n_terms] out_xy=u64[16*n_jobs] out_inf=u8[n_jobs]"
+S["g2_msm"] = S["g2_msm_tuned"] = "p_xy=u64[16*n] p_inf=u8[n]? k=u64[4*n] out_xy=u64[16] out_inf=u8[1]"
+S["g2_sum_batch"] = "q_xy=u64[16*n] q_inf=u8[n]? out_xy=u64[16] out_inf=u8[1]"
 S["g1_on_curve_batch"] = "p_xy=u64[8*n] p_inf=u8[n]? status=u8[n]"
 S["g2_psi_batch"] = "q_xy=u64[16*n] q_inf=u8[n]? out_xy=u64[16*n] out_inf=u8[n] status=u8[n]"
 S["g2_subgroup_check_batch"] = "q_xy=u64[16*n] q_inf=u8[n]? status=u8[n]"

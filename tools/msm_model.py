@@ -1,6 +1,8 @@
 """Model of the host-side recoding and planning of sylow_hip_g1_msm (sylow_amd/csrc/msm.hip): the signed c-bit digits of a scalar, the
 window / bucket counts, the chunk plan under a scratch budget and the scratch-byte formula.  Every formula here mirrors the C++ one by one;
-tests/test_msm_model.py pins them, and tests/test_gpu_msm.py uses scratch_bytes to force chunking.
+tests/test_msm_model.py pins them, and tests/test_gpu_msm.py uses scratch_bytes to force chunking.  The g2_* functions are the same model
+for sylow_hip_g2_msm (sylow_amd/csrc/g2_msm.hpp): the digits are those of k mod p itself (a twist point need not have order r), and a bucket
+and a prepared point are twice as wide (lane pairs); tests/test_g2_msm_model.py pins them.
 
     python tools/msm_model.py            # prints the plan for n = 2^12 .. 2^24"""
 import json
@@ -109,6 +111,65 @@ def plan(n: int, c: int, budget: int = DEFAULT_BUDGET):
                 hi = mid - 1
         nc = lo
     return nc, scratch_bytes(c, nc)
+
+
+# ---- G2 (g2_msm.hpp): the same scalar side without the mod-r step, the same plan with lane-pair sizes ----
+G2_DEFAULT_MIN = 1 << 16
+G2_WIDE_FROM, G2_WIDE_C = 1 << 16, 15   # from this n on the default window is G2_WIDE_C (measured: DESIGN.md §4.3)
+W54 = 54              # i32 words of a projective lane-pair point: 27 per lane
+G2_PT_WORDS = 40      # i32 words of a prepared affine point: per lane x, y, padding to 80 bytes
+
+
+def g2_reduce_scalar(k: int) -> int:
+    """k mod p and nothing else: Fp::new.  The product is exact on the whole twist, whose points need not have order r."""
+    return k % P
+
+
+def g2_default_window(n: int) -> int:
+    """the G1 rule below 2^16, c = 15 from there on (the sweep of c at 2^16 and 2^20 has it fastest at both)"""
+    return G2_WIDE_C if n >= G2_WIDE_FROM else default_window(n)
+
+
+def g2_recode(k: int, c: int) -> list:
+    """the signed c-bit digits of k mod p: k mod p < 2^254 and W c >= 255 leave no carry out of the top window"""
+    return recode(g2_reduce_scalar(k), c)
+
+
+def g2_fixed_bytes(c: int) -> int:
+    W, B = windows(c), buckets(c)
+    N, T = W * B, B // min(B, MSM_RUN)
+    tiles = -(-N // SCAN_TILE)
+    return (_align(N * 4) + _align(N * 8) + _align(N * 4) + _align(tiles * 8) + _align(8) + _align(N * W54 * 4) + _align(W * T * W54 * 4) +
+            _align(W * W54 * 4))
+
+
+def g2_chunk_bytes(c: int, nc: int) -> int:
+    W, N = windows(c), windows(c) * buckets(c)
+    return _align(nc * G2_PT_WORDS * 4) + _align(W * nc * 4) + _align(seg_bound(W, N, nc) * W54 * 4)
+
+
+def g2_scratch_bytes(c: int, nc: int) -> int:
+    """the one lease of a G2 call whose chunks hold nc points"""
+    return g2_fixed_bytes(c) + g2_chunk_bytes(c, nc)
+
+
+def g2_plan(n: int, c: int, budget: int = DEFAULT_BUDGET):
+    """(chunk size, lease bytes) of the G2 bucket route, or None when not even a chunk of min(n, 256) points fits (composed route)"""
+    W = windows(c)
+    nc = min(n, (1 << 31) // W)
+    floor_nc = min(n, 256)
+    if g2_scratch_bytes(c, floor_nc) > budget:
+        return None
+    if g2_scratch_bytes(c, nc) > budget:
+        lo, hi = floor_nc, nc
+        while lo < hi:
+            mid = lo + (hi - lo + 1) // 2
+            if g2_scratch_bytes(c, mid) <= budget:
+                lo = mid
+            else:
+                hi = mid - 1
+        nc = lo
+    return nc, g2_scratch_bytes(c, nc)
 
 
 if __name__ == "__main__":
