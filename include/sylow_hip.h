@@ -673,6 +673,59 @@ int32_t sylow_hip_bls_batch_verify_weighted(const uint64_t* pk_xy, const uint8_t
                                             const uint64_t* sig_xy, const uint8_t* sig_inf, const uint64_t* weights, size_t n, void* comm,
                                             uint64_t* gt_out, uint8_t* is_one, void* stream);
 
+/* ---- Groth16 on BN254 under ONE verifying key (groth16.hip, groth16_pair.hpp compiled with plk_multi.hip) -------------------------
+ * vk = (alpha in G1; beta, gamma, delta in G2; IC_0 .. IC_l in G1), a proof is (A in G1, B in G2, C in G1) with l = n_inputs public
+ * inputs x_1 .. x_l.  In the EVM / snarkjs form
+ *     vk_x = IC_0 + sum_j x_j IC_j,     ok = [ e(-A, B) e(alpha, beta) e(vk_x, gamma) e(C, delta) == 1 ].
+ * Conventions of the three calls:
+ *   vk arrays: device SoA arrays WITHOUT flag arrays -- vk_alpha [8][1], vk_beta / vk_gamma / vk_delta [16][1], vk_ic [8][n_inputs + 1].
+ *   proofs:    a_xy [8][n], b_xy [16][n], c_xy [8][n], each with an optional identity-flag array; inputs [4][n_inputs * n], INPUT-MAJOR:
+ *              input j of proof i at index j*n + i (the term-major rule of sylow_hip_g1_lincomb_batch).
+ *   words:     field words >= p are reduced like Fp::new, as everywhere.
+ *   scalars:   inputs and weights follow sylow_hip_evm_ecmul_batch -- ANY 256-bit word, taken mod r (every G1 point has order r, so for a
+ *              word < p this is also what sylow_hip_g1_lincomb_batch computes).  Solidity verifiers REJECT an input >= r: a host that wants
+ *              that rule checks the inputs with sylow_hip_fr_from_be_bytes_batch first.
+ *   identity:  EIP-197, as sylow_hip_evm_ecpairing_batch and skip_infinity = 1: a pair with a flagged identity on either side contributes 1,
+ *              and so does a vk_x that sums to the identity.
+ *   points:    taken as given, as in the MSM calls: no on-curve check, no subgroup check.  PRECONDITION: B, beta, gamma, delta in G2
+ *              proper (sylow_hip_g2_subgroup_check_batch / sylow_hip_g2_from_be_bytes_batch establish that).
+ *   calls:     stream-ordered, no host synchronisation; scratch leased per call.  n = 0 launches nothing that reads the arrays;
+ *              n_inputs = 0 is legal (vk_x = IC_0).  NULL where a pointer is required: SYLOW_HIP_E_ARG and no launch. */
+/* vk_x of every proof: out [8][n] affine + flags (the identity as (0, 1) + flag), bit-identical to sylow_hip_g1_lincomb_batch with
+ * n_jobs = n, n_terms = n_inputs + 1 on the bases replicated n times, scalar 1 for IC_0 and the inputs taken mod r.  The bases are shared:
+ * one small kernel builds a 16-entry window table per base per call, then one lane per proof runs Straus interleaving -- ONE chain of 252
+ * doublings and one complete addition per input and 4-bit window.  Equal bases and partial sums that hit the identity are legal. */
+/* @shape vk_ic=u64[8*(n_inputs+1)] inputs=u64[4*n_inputs*n]? out_xy=u64[8*n] out_inf=u8[n] */
+int32_t sylow_hip_groth16_vk_x_batch(const uint64_t* vk_ic, size_t n_inputs, const uint64_t* inputs, size_t n,
+                                     uint64_t* out_xy, uint8_t* out_inf, void* stream);
+/* ok [n]: the boolean above for every proof.  Routes: n <= 1024 with 4 n <= SYLOW_HIP_OPT_WIDE_MAX (default 6144), and any batch whose
+ * scratch limit is below 1024 proofs' line tables (19.5 KB each) or with SYLOW_HIP_OPT_MULTI_TABLES = 0, take the COMPOSED route: vk_x
+ * by the kernel above, then the four literal pairs per proof through sylow_hip_multi_pairing_batch.  Every other batch takes the TABLE route:
+ * per call the lines of gamma and delta are formed once and e(-alpha, beta) is ONE Miller loop whose value is multiplied into every
+ * job before its final exponentiation; per proof vk_x, the lines of B_i (in HBM, in slices under sylow_hip_set_scratch_limit exactly as
+ * sylow_hip_multi_pairing_batch slices), one shared-squaring loop over three lines per step, one final exponentiation, a compare.  The flags
+ * are the same on every route and under every limit. */
+/* @shape vk_alpha=u64[8] vk_beta=u64[16] vk_gamma=u64[16] vk_delta=u64[16] vk_ic=u64[8*(n_inputs+1)] a_xy=u64[8*n] a_inf=u8[n]? b_xy=u64[16*n] b_inf=u8[n]? c_xy=u64[8*n] c_inf=u8[n]? inputs=u64[4*n_inputs*n]? ok=u8[n] */
+int32_t sylow_hip_groth16_verify_batch(const uint64_t* vk_alpha, const uint64_t* vk_beta, const uint64_t* vk_gamma, const uint64_t* vk_delta,
+                                       const uint64_t* vk_ic, size_t n_inputs, const uint64_t* a_xy, const uint8_t* a_inf,
+                                       const uint64_t* b_xy, const uint8_t* b_inf, const uint64_t* c_xy, const uint8_t* c_inf,
+                                       const uint64_t* inputs, size_t n, uint8_t* ok, void* stream);
+/* The SOUND one-boolean form, the move of sylow_hip_bls_batch_verify_weighted: with weights r_i [4][n]
+ *     prod_i e(r_i A_i, B_i) e(-s alpha, beta) e(-sum_i r_i vk_x_i, gamma) e(-sum_i r_i C_i, delta) == 1,      s = sum_i r_i mod r,
+ *     sum_i r_i vk_x_i = s IC_0 + sum_j (sum_i r_i x_ij mod r) IC_j
+ * -- n scalar multiplications in G1, one n-pair Miller product, one multi-scalar multiplication over the C_i (sylow_hip_g1_msm, whatever
+ * route it picks), the Fr column sums s, s_j in one two-level reduction, n_inputs + 2 more scalar multiplications, three more pairs and ONE
+ * final exponentiation.  gt_out [48][1] is the Gt element, hence the words, of the reference's glued_pairing over the n + 3 literal pairs
+ * written above; is_one [1] its comparison with the identity; either may be NULL (not both).  A weight of 0 removes a proof from the test;
+ * n = 0 gives the identity.  The caller draws the weights AFTER the proofs are fixed (e.g. 64 or 128 random bits each): if every proof is
+ * valid the result is the identity; if any is not, the test passes with probability at most 2^-(bits of the weights) over the caller's
+ * randomness, provided every G2 input is in the r-torsion (the precondition above). */
+/* @shape vk_alpha=u64[8] vk_beta=u64[16] vk_gamma=u64[16] vk_delta=u64[16] vk_ic=u64[8*(n_inputs+1)] a_xy=u64[8*n] a_inf=u8[n]? b_xy=u64[16*n] b_inf=u8[n]? c_xy=u64[8*n] c_inf=u8[n]? inputs=u64[4*n_inputs*n]? weights=u64[4*n] gt_out=u64[48]? is_one=u8[1]? */
+int32_t sylow_hip_groth16_batch_verify_weighted(const uint64_t* vk_alpha, const uint64_t* vk_beta, const uint64_t* vk_gamma, const uint64_t* vk_delta,
+                                                const uint64_t* vk_ic, size_t n_inputs, const uint64_t* a_xy, const uint8_t* a_inf,
+                                                const uint64_t* b_xy, const uint8_t* b_inf, const uint64_t* c_xy, const uint8_t* c_inf,
+                                                const uint64_t* inputs, const uint64_t* weights, size_t n, uint64_t* gt_out, uint8_t* is_one, void* stream);
+
 /* ---- test hooks (stable enough for the repo's own tests; not part of the drop-in surface) ------------------------------------
  * Granger-Scott cyclotomic square (pairing.rs:309-350) and the raw Fp12 selector: 0..7 one-element-per-lane tower ops (tower.hip), 8 / 9 product /
  * cyclotomic square on the carry-free core, 10 / 11 exp_by_neg_z (carry-free / saturated), 16..31 the lane-pair Fp12 layer: 16 product,

@@ -344,6 +344,82 @@ inline bool verify_all(const std::vector<G2Affine>& pubkey, const std::vector<st
   if (product) *product = from_device_soa<Gt>(dgt, 1)[0];
   return one != 0;
 }
+// Groth16 on BN254 under ONE verifying key (sylow_hip.h, "Groth16").  The key's points are never the identity, so it carries no flags.
+struct Groth16VerifyingKey {
+  G1Affine alpha;
+  G2Affine beta, gamma, delta;
+  std::vector<G1Affine> ic;                       // IC_0 .. IC_l
+  size_t n_inputs() const { return ic.size() - 1; }
+};
+namespace detail {
+// inputs[i][j] (proof-major on the host) -> the device's input-major [4][l * n]: input j of proof i at index j * n + i
+inline DeviceBuffer groth16_inputs(const std::vector<std::vector<Fp>>& inputs, size_t l) {
+  std::vector<Fp> flat(inputs.size() * l);
+  for (size_t i = 0; i < inputs.size(); ++i) {
+    if (inputs[i].size() != l) throw Error("groth16: every proof takes n_inputs public inputs");
+    for (size_t j = 0; j < l; ++j) flat[j * inputs.size() + i] = inputs[i][j];
+  }
+  return to_device_soa(flat);
+}
+}  // namespace detail
+// the device copies both Groth16 checks take
+struct Groth16Device {
+  DeviceBuffer alpha, beta, gamma, delta, ic, a, b, c, x;
+  size_t n, l;
+};
+inline Groth16Device groth16_upload(const char* who, const Groth16VerifyingKey& vk, const std::vector<G1Affine>& a, const std::vector<G2Affine>& b,
+                                    const std::vector<G1Affine>& c, const std::vector<std::vector<Fp>>& inputs) {
+  if (vk.ic.empty()) throw Error(std::string(who) + ": the key holds at least IC_0");
+  const size_t n = a.size(), l = vk.n_inputs();
+  if (b.size() != n || c.size() != n || inputs.size() != n) throw Error(std::string(who) + ": length mismatch");
+  return Groth16Device{to_device_soa(std::vector<G1Affine>{vk.alpha}), to_device_soa(std::vector<G2Affine>{vk.beta}), to_device_soa(std::vector<G2Affine>{vk.gamma}),
+                       to_device_soa(std::vector<G2Affine>{vk.delta}), to_device_soa(vk.ic), to_device_soa(a), to_device_soa(b), to_device_soa(c),
+                       detail::groth16_inputs(inputs, l), n, l};
+}
+// ok[i] = [ e(-A_i, B_i) e(alpha, beta) e(IC_0 + sum_j x_ij IC_j, gamma) e(C_i, delta) == 1 ]; inputs are any 256-bit words, taken mod r.
+// Points are taken as given: B and the key's G2 points must lie in G2 proper.
+inline std::vector<uint8_t> groth16_verify(const Groth16VerifyingKey& vk, const std::vector<G1Affine>& a, const std::vector<G2Affine>& b,
+                                           const std::vector<G1Affine>& c, const std::vector<std::vector<Fp>>& inputs) {
+  Groth16Device d = groth16_upload("groth16_verify", vk, a, b, c, inputs);
+  std::vector<uint8_t> ok(d.n);
+  DeviceBuffer dok(d.n + 8);
+  check(sylow_hip_groth16_verify_batch(d.alpha.as<uint64_t>(), d.beta.as<uint64_t>(), d.gamma.as<uint64_t>(), d.delta.as<uint64_t>(), d.ic.as<uint64_t>(), d.l,
+                                       d.a.as<uint64_t>(), nullptr, d.b.as<uint64_t>(), nullptr, d.c.as<uint64_t>(), nullptr, d.x.as<uint64_t>(), d.n, dok.as<uint8_t>(),
+                                       nullptr), "sylow_hip_groth16_verify_batch");
+  if (d.n) check(sylow_hip_memcpy_d2h(ok.data(), dok.as<void>(), d.n, nullptr), "d2h");
+  check(sylow_hip_stream_sync(nullptr), "sync");
+  return ok;
+}
+// "are ALL of them valid?" as ONE boolean, the sound small-exponent test (sylow_hip_groth16_batch_verify_weighted): one weight per proof, drawn
+// AFTER the proofs are fixed; a batch with an invalid proof passes with probability at most 2^-(bits of the weights).  Like verify_all.
+inline bool groth16_verify_all(const Groth16VerifyingKey& vk, const std::vector<G1Affine>& a, const std::vector<G2Affine>& b, const std::vector<G1Affine>& c,
+                               const std::vector<std::vector<Fp>>& inputs, const std::vector<Fp>& weights, Gt* product = nullptr) {
+  Groth16Device d = groth16_upload("groth16_verify_all", vk, a, b, c, inputs);
+  if (weights.size() != d.n) throw Error("groth16_verify_all: one weight per proof");
+  auto dw = to_device_soa(weights);
+  DeviceBuffer dgt(sizeof(Gt) + 8), done(8);
+  check(sylow_hip_groth16_batch_verify_weighted(d.alpha.as<uint64_t>(), d.beta.as<uint64_t>(), d.gamma.as<uint64_t>(), d.delta.as<uint64_t>(), d.ic.as<uint64_t>(), d.l,
+                                                d.a.as<uint64_t>(), nullptr, d.b.as<uint64_t>(), nullptr, d.c.as<uint64_t>(), nullptr, d.x.as<uint64_t>(), dw.as<uint64_t>(),
+                                                d.n, dgt.as<uint64_t>(), done.as<uint8_t>(), nullptr), "sylow_hip_groth16_batch_verify_weighted");
+  uint8_t one = 0;
+  check(sylow_hip_memcpy_d2h(&one, done.as<void>(), 1, nullptr), "d2h"); check(sylow_hip_stream_sync(nullptr), "sync");
+  if (product) *product = from_device_soa<Gt>(dgt, 1)[0];
+  return one != 0;
+}
+// vk_x_i = IC_0 + sum_j x_ij IC_j for every proof (sylow_hip_groth16_vk_x_batch); *infinity (if given) receives the identity flags
+inline std::vector<G1Affine> groth16_vk_x(const std::vector<G1Affine>& ic, const std::vector<std::vector<Fp>>& inputs, std::vector<uint8_t>* infinity = nullptr) {
+  if (ic.empty()) throw Error("groth16_vk_x: ic holds at least IC_0");
+  const size_t n = inputs.size(), l = ic.size() - 1;
+  auto dic = to_device_soa(ic);
+  auto dx = detail::groth16_inputs(inputs, l);
+  DeviceBuffer dout(n * sizeof(G1Affine) + 8), dinf(n + 8);
+  check(sylow_hip_groth16_vk_x_batch(dic.as<uint64_t>(), l, dx.as<uint64_t>(), n, dout.as<uint64_t>(), dinf.as<uint8_t>(), nullptr), "sylow_hip_groth16_vk_x_batch");
+  if (infinity) {
+    infinity->assign(n, 0);
+    if (n) check(sylow_hip_memcpy_d2h(infinity->data(), dinf.as<void>(), n, nullptr), "d2h");
+  }
+  return from_device_soa<G1Affine>(dout, n);
+}
 // Many signers, ONE message (examples/threshold_signing.rs:92-121): e(sig, G2gen) e(-H(msg), sum_j pubkeys[j]) == identity -- one hash, one G2
 // sum and two Miller loops whatever the number of keys.  `sig` is the signers' aggregate signature (sum() of the individual ones).
 inline bool verify_one_message(const std::vector<G2Affine>& pubkeys, const std::vector<uint8_t>& msg, const G1Affine& sig, Gt* product = nullptr) {

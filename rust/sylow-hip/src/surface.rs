@@ -770,6 +770,67 @@ pub fn weighted_partial(dev: &Device, pk: &DeviceG2, msgs: &[&[u8]], sig: &Devic
     })?;
     Ok(f)
 }
+/// A Groth16 verifying key on the device: alpha (one G1 point), beta / gamma / delta (one G2 point each) and ic = IC_0 .. IC_l.  The
+/// entry points take these arrays without flag arrays: a key's points are never the identity.
+pub struct Groth16Vk {
+    pub alpha: DeviceG1,
+    pub beta: DeviceG2,
+    pub gamma: DeviceG2,
+    pub delta: DeviceG2,
+    pub ic: DeviceG1,
+}
+impl Groth16Vk {
+    /// l, the number of public inputs: ic holds IC_0 .. IC_l, at least IC_0
+    pub fn n_inputs(&self) -> usize {
+        assert!(self.ic.n >= 1, "a Groth16 key holds at least IC_0");
+        self.ic.n - 1
+    }
+}
+/// vk_x_i = IC_0 + sum_j x_ij IC_j for n proofs (`sylow_hip_groth16_vk_x_batch`).  `inputs` is INPUT-MAJOR: input j of proof i at index
+/// j * n + i; any 256-bit words, taken mod r.
+pub fn groth16_vk_x(dev: &Device, ic: &DeviceG1, inputs: &[Fr], n: usize) -> Result<DeviceG1, HipError> {
+    assert!(ic.n >= 1, "ic holds at least IC_0");
+    let n_inputs = ic.n - 1;
+    assert!(inputs.len() == n_inputs * n);
+    let dx = dev.upload_soa::<4>(&fr_words(inputs))?;
+    let out = DeviceG1 { xy: dev.alloc::<u64>(8 * n)?, inf: dev.alloc::<u8>(n)?, n };
+    // SAFETY: n_inputs + 1 bases, n_inputs * n input words, n outputs.
+    device::check(unsafe { ffi::sylow_hip_groth16_vk_x_batch(ic.xy.as_ptr(), n_inputs, dx.as_ptr(), n, out.xy.as_mut_ptr(), out.inf.as_mut_ptr(), dev.stream) })?;
+    Ok(out)
+}
+/// ok[i] = [ e(-A_i, B_i) e(alpha, beta) e(vk_x_i, gamma) e(C_i, delta) == 1 ] for n proofs under one key (`sylow_hip_groth16_verify_batch`);
+/// identities follow EIP-197.  Precondition: B, beta, gamma, delta in G2 proper.  `inputs` input-major as for `groth16_vk_x`.
+pub fn groth16_verify(dev: &Device, vk: &Groth16Vk, a: &DeviceG1, b: &DeviceG2, c: &DeviceG1, inputs: &[Fr]) -> Result<Vec<bool>, HipError> {
+    let n = a.n;
+    assert!(vk.ic.n >= 1 && b.n == n && c.n == n && inputs.len() == vk.n_inputs() * n);
+    let dx = dev.upload_soa::<4>(&fr_words(inputs))?;
+    let ok = dev.alloc::<u8>(n)?;
+    // SAFETY: one point per vk array and n_inputs + 1 bases; n proofs with flags; n_inputs * n input words; n flags out.
+    device::check(unsafe {
+        ffi::sylow_hip_groth16_verify_batch(vk.alpha.xy.as_ptr(), vk.beta.xy.as_ptr(), vk.gamma.xy.as_ptr(), vk.delta.xy.as_ptr(), vk.ic.xy.as_ptr(), vk.n_inputs(),
+                                            a.xy.as_ptr(), a.inf.as_ptr(), b.xy.as_ptr(), b.inf.as_ptr(), c.xy.as_ptr(), c.inf.as_ptr(), dx.as_ptr(), n,
+                                            ok.as_mut_ptr(), dev.stream)
+    })?;
+    Ok(dev.download(&ok)?.into_iter().map(|v| v != 0).collect())
+}
+/// The SOUND one-boolean form for n Groth16 proofs (`sylow_hip_groth16_batch_verify_weighted`): `weights` drawn by the caller AFTER the
+/// proofs are fixed (any 256-bit words, taken mod r; 0 removes a proof).  True when every proof is valid; a batch with an invalid one
+/// passes with probability at most 2^-(bits of the weights), given G2 inputs in the r-torsion.
+pub fn groth16_batch_verify_weighted(dev: &Device, vk: &Groth16Vk, a: &DeviceG1, b: &DeviceG2, c: &DeviceG1, inputs: &[Fr], weights: &[Fr]) -> Result<(GtOut, bool), HipError> {
+    let n = a.n;
+    assert!(vk.ic.n >= 1 && b.n == n && c.n == n && weights.len() == n && inputs.len() == vk.n_inputs() * n);
+    let dx = dev.upload_soa::<4>(&fr_words(inputs))?;
+    let dw = dev.upload_soa::<4>(&fr_words(weights))?;
+    let (gt, one) = (dev.alloc::<u64>(48)?, dev.alloc::<u8>(1)?);
+    // SAFETY: as groth16_verify, 4 * n weight words; gt 48 words; one 1 byte.
+    device::check(unsafe {
+        ffi::sylow_hip_groth16_batch_verify_weighted(vk.alpha.xy.as_ptr(), vk.beta.xy.as_ptr(), vk.gamma.xy.as_ptr(), vk.delta.xy.as_ptr(), vk.ic.xy.as_ptr(),
+                                                     vk.n_inputs(), a.xy.as_ptr(), a.inf.as_ptr(), b.xy.as_ptr(), b.inf.as_ptr(), c.xy.as_ptr(), c.inf.as_ptr(),
+                                                     dx.as_ptr(), dw.as_ptr(), n, gt.as_mut_ptr(), one.as_mut_ptr(), dev.stream)
+    })?;
+    let words = dev.download_aos::<48>(&gt, 1)?;
+    Ok((gt_from_words(&words[0]), dev.download(&one)?[0] != 0))
+}
 /// AND of a device-resident flag vector (one rank; `all_valid` in lib.rs adds the reduce over ranks).
 pub fn flags_all(dev: &Device, flags: &DeviceBuf<u8>) -> Result<bool, HipError> {
     let out = dev.alloc::<i32>(1)?;

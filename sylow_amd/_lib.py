@@ -149,6 +149,10 @@ SIGNATURES = {
     "sylow_hip_clock_probe": [c_u64p],
     "sylow_hip_wall_clock_khz": [ctypes.POINTER(c_i32)],
     "sylow_hip_g1_sum_batch": [c_u64p, c_u8p, c_sz, c_u64p, c_u8p, c_vp],
+    "sylow_hip_groth16_vk_x_batch": [c_u64p, c_sz, c_u64p, c_sz, c_u64p, c_u8p, c_vp],
+    "sylow_hip_groth16_verify_batch": [c_u64p, c_u64p, c_u64p, c_u64p, c_u64p, c_sz, c_u64p, c_u8p, c_u64p, c_u8p, c_u64p, c_u8p, c_u64p, c_sz, c_u8p, c_vp],
+    "sylow_hip_groth16_batch_verify_weighted": [c_u64p, c_u64p, c_u64p, c_u64p, c_u64p, c_sz, c_u64p, c_u8p, c_u64p, c_u8p, c_u64p, c_u8p, c_u64p, c_u64p, c_sz,
+                                                c_u64p, c_u8p, c_vp],
     "sylow_hip_g1_msm": [c_u64p, c_u8p, c_u64p, c_sz, c_u64p, c_u8p, c_vp],
     "sylow_hip_g1_msm_tuned": [c_u64p, c_u8p, c_u64p, c_sz, c_i32, ctypes.c_int64, c_u64p, c_u8p, c_vp],
     "sylow_hip_g2_sum_batch": [c_u64p, c_u8p, c_sz, c_u64p, c_u8p, c_vp],

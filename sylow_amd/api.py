@@ -516,6 +516,35 @@ def batch_verify(pubkey: G2Affine, msgs, sig: G1Affine, weight_bits: int = 128, 
     return ok
 
 
+class Groth16VerifyingKey:
+    """A Groth16 verifying key on BN254: alpha (one G1 point), beta / gamma / delta (one G2 point each) and ic (the l + 1 G1 points
+    IC_0 .. IC_l).  A plain holder: nothing is cached on the device between calls."""
+
+    def __init__(self, alpha: G1Affine, beta: G2Affine, gamma: G2Affine, delta: G2Affine, ic: G1Affine):
+        if not (len(alpha) == len(beta) == len(gamma) == len(delta) == 1 and len(ic) >= 1):
+            raise ValueError("Groth16VerifyingKey: alpha, beta, gamma, delta are single points and ic holds at least IC_0")
+        if alpha.infinity.any() or beta.infinity.any() or gamma.infinity.any() or delta.infinity.any() or ic.infinity.any():
+            raise ValueError("Groth16VerifyingKey: the key's points cannot be the identity")
+        self.alpha, self.beta, self.gamma, self.delta, self.ic = alpha, beta, gamma, delta, ic
+
+    @property
+    def n_inputs(self) -> int:
+        return len(self.ic) - 1
+
+    def arrays(self):
+        return self.alpha.xy, self.beta.xy, self.gamma.xy, self.delta.xy, self.ic.xy
+
+
+def groth16_verify(vk: Groth16VerifyingKey, a: G1Affine, b: G2Affine, c: G1Affine, inputs) -> np.ndarray:
+    """ok[i] = [ e(-A_i, B_i) e(alpha, beta) e(IC_0 + sum_j x_ij IC_j, gamma) e(C_i, delta) == 1 ] for n proofs under one key; inputs
+    [n, l, 4] words (or [n, l] Python ints), taken mod r.  Points are taken as given: B must lie in G2 proper (G2Affine.from_be_bytes and
+    the subgroup check establish that), and a host that wants the Solidity rule rejects inputs >= r beforehand."""
+    x = np.asarray(inputs)
+    if x.dtype == object or x.ndim == 2:
+        x = fp([int(v) for v in np.asarray(inputs, dtype=object).reshape(-1)]).reshape(len(a), vk.n_inputs, 4)
+    return engine().groth16_verify(vk.arrays(), a.xy, b.xy, c.xy, x, a.infinity, b.infinity, c.infinity).astype(bool)
+
+
 class KeyPair:
     """KeyPair (lib.rs:105-137), a batch of them: secret_key = Fp::new(Fr::rand().value()) -- a scalar below r held as an Fp --
     and public_key = G2Projective::generator() * secret_key."""

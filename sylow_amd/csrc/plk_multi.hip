@@ -1327,3 +1327,6 @@ int32_t sylow_hip_evm_ecpairing_batch(const uint8_t* in, const uint64_t* pair_of
   return host::finish(rc, lease);
 }
 }  // extern "C"
+
+// batched Groth16 verification: the pairing side (uses this unit's line tables, slicing and product tree)
+#include "groth16_pair.hpp"

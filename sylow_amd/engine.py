@@ -899,6 +899,65 @@ class Engine:
         self._call("sylow_hip_bls_batch_verify_weighted", dpk.ptr, self._ptr(dpi), n_pk, dm.ptr, doff.ptr, dsig.ptr, self._ptr(dsi), dw.ptr, n, comm, dgt.ptr, dis.ptr)
         return self.from_device_soa(dgt), bool(dis.download()[0])
 
+    # ---- Groth16 under one verifying key.  vk = (alpha [1, 8], beta / gamma / delta [1, 16], ic [l + 1, 8]); inputs [n, l, 4]: any 256-bit
+    # words, taken mod r ----
+    def _groth16_vk(self, vk):
+        alpha, beta, gamma, delta, ic = vk
+        ic = _aos(ic, 8)
+        assert ic.shape[0] >= 1
+        return (self.to_device_soa(_aos(alpha, 8), 8), self.to_device_soa(_aos(beta, 16), 16), self.to_device_soa(_aos(gamma, 16), 16),
+                self.to_device_soa(_aos(delta, 16), 16), self.to_device_soa(ic, 8), ic.shape[0] - 1)
+
+    def _groth16_inputs(self, inputs, n, n_inputs):
+        """[n, l, 4] (proof-major on the host) -> the device's input-major [4][l * n]"""
+        inputs = np.ascontiguousarray(inputs, dtype=np.uint64).reshape(n, n_inputs, 4)
+        if n == 0 or n_inputs == 0:
+            return None
+        return self.to_device_soa(np.ascontiguousarray(inputs.transpose(1, 0, 2)).reshape(n_inputs * n, 4), 4)
+
+    def groth16_vk_x(self, ic, inputs):
+        """vk_x_i = IC_0 + sum_j x_ij IC_j for every proof (sylow_hip_groth16_vk_x_batch): ([n, 8] affine words, [n] flags)."""
+        ic = _aos(ic, 8)
+        n_inputs = ic.shape[0] - 1
+        n = np.asarray(inputs).shape[0]
+        dic, dx = self.to_device_soa(ic, 8), self._groth16_inputs(inputs, n, n_inputs)
+        do, doi = self.empty((8, max(n, 1))), self.empty((max(n, 1),), np.uint8)
+        self._call("sylow_hip_groth16_vk_x_batch", dic.ptr, n_inputs, self._ptr(dx), n, do.ptr, doi.ptr)
+        return self.from_device_soa(do)[:n], doi.download()[:n]
+
+    def _groth16_proofs(self, a_xy, b_xy, c_xy, a_inf, b_inf, c_inf):
+        a_xy, b_xy, c_xy = _aos(a_xy, 8), _aos(b_xy, 16), _aos(c_xy, 8)
+        n = a_xy.shape[0]
+        assert b_xy.shape[0] == n and c_xy.shape[0] == n
+        up = lambda x, w: self.to_device_soa(x, w) if n else None
+        fl = lambda x: self._flags(x, n) if n else None
+        return n, up(a_xy, 8), fl(a_inf), up(b_xy, 16), fl(b_inf), up(c_xy, 8), fl(c_inf)
+
+    def groth16_verify(self, vk, a_xy, b_xy, c_xy, inputs, a_inf=None, b_inf=None, c_inf=None):
+        """e(-A_i, B_i) e(alpha, beta) e(vk_x_i, gamma) e(C_i, delta) == 1 for every proof under one verifying key
+        (sylow_hip_groth16_verify_batch): [n] uint8.  Identities follow EIP-197; B, beta, gamma, delta must be in G2 proper."""
+        dal, dbe, dga, dde, dic, n_inputs = self._groth16_vk(vk)
+        n, da, dai, db, dbi, dc, dci = self._groth16_proofs(a_xy, b_xy, c_xy, a_inf, b_inf, c_inf)
+        dx = self._groth16_inputs(inputs, n, n_inputs)
+        dok = self.empty((max(n, 1),), np.uint8)
+        self._call("sylow_hip_groth16_verify_batch", dal.ptr, dbe.ptr, dga.ptr, dde.ptr, dic.ptr, n_inputs, self._ptr(da), self._ptr(dai), self._ptr(db),
+                   self._ptr(dbi), self._ptr(dc), self._ptr(dci), self._ptr(dx), n, dok.ptr)
+        return dok.download()[:n]
+
+    def groth16_batch_verify_weighted(self, vk, a_xy, b_xy, c_xy, inputs, weights, a_inf=None, b_inf=None, c_inf=None):
+        """The small-exponent batch test of n Groth16 proofs as ONE Gt (sylow_hip_groth16_batch_verify_weighted); weights [n, 4] drawn by the
+        caller after the proofs are fixed (any 256-bit words, taken mod r; 0 removes a proof).  Returns (Gt words [1, 48], bool)."""
+        dal, dbe, dga, dde, dic, n_inputs = self._groth16_vk(vk)
+        n, da, dai, db, dbi, dc, dci = self._groth16_proofs(a_xy, b_xy, c_xy, a_inf, b_inf, c_inf)
+        dx = self._groth16_inputs(inputs, n, n_inputs)
+        weights = _aos(weights, 4)
+        assert weights.shape[0] == n
+        dw = self.to_device_soa(weights, 4) if n else None
+        dgt, dis = self.empty((48, 1)), self.empty((1,), np.uint8)
+        self._call("sylow_hip_groth16_batch_verify_weighted", dal.ptr, dbe.ptr, dga.ptr, dde.ptr, dic.ptr, n_inputs, self._ptr(da), self._ptr(dai), self._ptr(db),
+                   self._ptr(dbi), self._ptr(dc), self._ptr(dci), self._ptr(dx), self._ptr(dw), n, dgt.ptr, dis.ptr)
+        return self.from_device_soa(dgt), bool(dis.download()[0])
+
     def bls_aggregate_partial(self, pk_xy, msgs, sig_xy, weights=None, pk_inf=None, sig_inf=None):
         """One shard's raw Miller product of the (weighted) aggregate check, [1, 48] words: the input of fp12_product_final_exp."""
         pk_xy, sig_xy = _aos(pk_xy, 16), _aos(sig_xy, 8)

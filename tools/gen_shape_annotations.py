@@ -119,6 +119,11 @@ S["bls_aggregate_partial_batch"] = AGG + " f_out=u64[48]"
 S["bls_aggregate_verify_batch"] = AGG + " comm=void[*]? gt_out=u64[48]? is_one=u8[1]?"
 S["bls_weighted_partial_batch"] = AGG + " weights=u64[4*n] f_out=u64[48]"
 S["bls_batch_verify_weighted"] = AGG + " weights=u64[4*n] comm=void[*]? gt_out=u64[48]? is_one=u8[1]?"
+G16_VK = "vk_alpha=u64[8] vk_beta=u64[16] vk_gamma=u64[16] vk_delta=u64[16] vk_ic=u64[8*(n_inputs+1)]"
+G16_PROOFS = "a_xy=u64[8*n] a_inf=u8[n]? b_xy=u64[16*n] b_inf=u8[n]? c_xy=u64[8*n] c_inf=u8[n]? inputs=u64[4*n_inputs*n]?"
+S["groth16_vk_x_batch"] = "vk_ic=u64[8*(n_inputs+1)] inputs=u64[4*n_inputs*n]? out_xy=u64[8*n] out_inf=u8[n]"
+S["groth16_verify_batch"] = G16_VK + " " + G16_PROOFS + " ok=u8[n]"
+S["groth16_batch_verify_weighted"] = G16_VK + " " + G16_PROOFS + " weights=u64[4*n] gt_out=u64[48]? is_one=u8[1]?"
 S["pairing_host"] = "p_aos=u64[8*n] p_inf=u8[n]? q_aos=u64[16*n] q_inf=u8[n]? gt_aos=u64[48*n]"
 S["bls_verify_host"] = "pk_aos=u64[16*n] pk_inf=u8[n]? msgs=u8[*]? msg_offsets=u64[n+1] sig_aos=u64[8*n] sig_inf=u8[n]? ok=u8[n]"
 S["pairing_host_bytes"] = "p_be=u8[64*n] q_be=u8[128*n] gt_aos=u64[48*n] status_p=u8[n] status_q=u8[n]"
