@@ -726,6 +726,58 @@ int32_t sylow_hip_groth16_batch_verify_weighted(const uint64_t* vk_alpha, const 
                                                 const uint64_t* b_xy, const uint8_t* b_inf, const uint64_t* c_xy, const uint8_t* c_inf,
                                                 const uint64_t* inputs, const uint64_t* weights, size_t n, uint64_t* gt_out, uint8_t* is_one, void* stream);
 
+/* ---- KZG openings on BN254 under ONE SRS (kzg.hip; the per-opening check runs plk_verify.hip's same-signer kernels) -------------------
+ * The SRS as the caller holds it: the G1 generator (1, 2), the library's G2 generator, and tau_g2 = tau G2gen.  An opening is
+ * (C, z, y, pi) and claims f(z) = y for the polynomial committed in C:
+ *     F = C - y G1gen + z pi,     ok = [ e(F, G2gen) e(-pi, tau_g2) == 1 ].
+ * Conventions of the four calls (those of the Groth16 block above):
+ *   arrays:    device SoA arrays -- c_xy [8][n], pi_xy [8][n], z [4][n], y [4][n]; c_inf / pi_inf are optional identity-flag arrays.
+ *   tau_g2:    tau_g2_xy [16][1], WITHOUT a flag array.
+ *   words:     field words >= p are reduced like Fp::new, as everywhere.
+ *   scalars:   z, y and weights follow sylow_hip_evm_ecmul_batch and the Groth16 inputs -- ANY 256-bit word, taken mod r.
+ *   identity:  pairing() / EIP-197: a pair with an identity on either side contributes 1.  A flagged C is the commitment to the zero
+ *              polynomial and is legal; a flagged pi is the proof for a constant polynomial, and the row is then valid iff C = y G1gen; an F
+ *              that sums to the identity while pi is not the identity is an INVALID row.  A flagged point adds nothing, whatever its
+ *              coordinate words hold.
+ *   points:    taken as given: no on-curve check, no subgroup check.  PRECONDITION: tau_g2 in G2 proper, and not the identity.
+ *   calls:     stream-ordered, no host synchronisation; scratch leased per call.  n = 0 launches nothing that reads the arrays.  NULL
+ *              where a pointer is required: SYLOW_HIP_E_ARG, no launch, nothing written. */
+/* F_i for every opening: out [8][n] affine + flags (the identity as (0, 1) + flag), bit-identical to the composition
+ * sylow_hip_g1_generator_mul_batch(y mod r), sylow_hip_g1_scalar_mul_batch(pi, z mod r), sylow_hip_g1_add_batch, sylow_hip_g1_sub_batch -- both
+ * are the canonical affine words of one group element.  ONE launch, one opening per lane, one accumulator: the GLV window walk of z pi, then
+ * 32 complete additions against the per-device fixed-base table of the G1 generator for y, then C; one normalisation.  Every addition is
+ * complete: C = +-z pi, C = y G1gen, pi = +-G1gen and scalars = 0 mod r are legal. */
+/* @shape c_xy=u64[8*n] c_inf=u8[n]? z=u64[4*n] y=u64[4*n] pi_xy=u64[8*n] pi_inf=u8[n]? out_xy=u64[8*n] out_inf=u8[n] */
+int32_t sylow_hip_kzg_fold_batch(const uint64_t* c_xy, const uint8_t* c_inf, const uint64_t* z, const uint64_t* y,
+                                 const uint64_t* pi_xy, const uint8_t* pi_inf, uint64_t* out_xy, uint8_t* out_inf, size_t n, void* stream);
+/* ok [n]: the boolean above for every opening, evaluated as the fold and then the same-signer BLS check with sig := F, -H := -pi and
+ * tau_g2 as the key: its line table is built once per call, no G2 arithmetic runs per opening.  Routes by batch size exactly as
+ * sylow_hip_bls_verify_same_signer_batch (one wavefront per Miller loop up to SYLOW_HIP_OPT_WIDE_VERIFY_MAX, lane quads up to
+ * SYLOW_HIP_OPT_QUAD_MAX, lane pairs above); the flags are the same on every route and equal sylow_hip_kzg_fold_batch +
+ * sylow_hip_bls_verify_hashed_batch with tau_g2 replicated n times. */
+/* @shape tau_g2_xy=u64[16] c_xy=u64[8*n] c_inf=u8[n]? z=u64[4*n] y=u64[4*n] pi_xy=u64[8*n] pi_inf=u8[n]? ok=u8[n] */
+int32_t sylow_hip_kzg_verify_batch(const uint64_t* tau_g2_xy, const uint64_t* c_xy, const uint8_t* c_inf, const uint64_t* z, const uint64_t* y,
+                                   const uint64_t* pi_xy, const uint8_t* pi_inf, uint8_t* ok, size_t n, void* stream);
+/* The same against a line table of tau_g2 the host cached with sylow_hip_g2_line_table (sylow_hip_g2_line_table_words() int32 words):
+ * nothing is rebuilt per call.  Like sylow_hip_bls_verify_line_table_batch it has no one-wavefront route (that route walks the point). */
+/* @shape tau_table=i32[*] c_xy=u64[8*n] c_inf=u8[n]? z=u64[4*n] y=u64[4*n] pi_xy=u64[8*n] pi_inf=u8[n]? ok=u8[n] */
+int32_t sylow_hip_kzg_verify_line_table_batch(const int32_t* tau_table, const uint64_t* c_xy, const uint8_t* c_inf, const uint64_t* z, const uint64_t* y,
+                                              const uint64_t* pi_xy, const uint8_t* pi_inf, uint8_t* ok, size_t n, void* stream);
+/* The SOUND one-boolean form, the move of sylow_hip_groth16_batch_verify_weighted: with weights r_i [4][n]
+ *     e( sum_i r_i C_i + sum_i (r_i z_i) pi_i - (sum_i r_i y_i) G1gen , G2gen ) e( -sum_i r_i pi_i , tau_g2 ) == 1
+ * -- one small kernel reduces r_i, r_i z_i and s = sum_i r_i y_i mod r (two levels) and concatenates the 2n bases and scalars; then one
+ * sylow_hip_g1_msm over the 2n terms and one over the pi_i (whatever route it picks), one generator product, and
+ * sylow_hip_pairing_product_batch over the two pairs with skip_infinity = 1: two Miller loops and ONE final exponentiation whatever n is.
+ * gt_out [48][1] is the Gt element, hence the words, of the reference's glued_pairing over the two literal pairs written above, identity
+ * pairs left out; is_one [1] its comparison with the identity; either may be NULL (not both).  A weight of 0 removes an opening from the
+ * test; n = 0 gives the identity.  The caller draws the weights AFTER the openings are fixed (e.g. 64 or 128 random bits each): if every
+ * opening is valid the result is the identity; if any is not, the test passes with probability at most 2^-(bits of the weights) over the
+ * caller's randomness, provided tau_g2 is in the r-torsion (the precondition above). */
+/* @shape tau_g2_xy=u64[16] c_xy=u64[8*n] c_inf=u8[n]? z=u64[4*n] y=u64[4*n] pi_xy=u64[8*n] pi_inf=u8[n]? weights=u64[4*n] gt_out=u64[48]? is_one=u8[1]? */
+int32_t sylow_hip_kzg_batch_verify_weighted(const uint64_t* tau_g2_xy, const uint64_t* c_xy, const uint8_t* c_inf, const uint64_t* z, const uint64_t* y,
+                                            const uint64_t* pi_xy, const uint8_t* pi_inf, const uint64_t* weights, size_t n,
+                                            uint64_t* gt_out, uint8_t* is_one, void* stream);
+
 /* ---- test hooks (stable enough for the repo's own tests; not part of the drop-in surface) ------------------------------------
  * Granger-Scott cyclotomic square (pairing.rs:309-350) and the raw Fp12 selector: 0..7 one-element-per-lane tower ops (tower.hip), 8 / 9 product /
  * cyclotomic square on the carry-free core, 10 / 11 exp_by_neg_z (carry-free / saturated), 16..31 the lane-pair Fp12 layer: 16 product,

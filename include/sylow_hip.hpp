@@ -420,6 +420,82 @@ inline std::vector<G1Affine> groth16_vk_x(const std::vector<G1Affine>& ic, const
   }
   return from_device_soa<G1Affine>(dout, n);
 }
+// KZG openings on BN254 under ONE SRS (sylow_hip.h, "KZG"): F = C - y G1gen + z pi, ok = [ e(F, G2gen) e(-pi, tau_g2) == 1 ].  z and y are any
+// 256-bit words, taken mod r (carried in the Fp container, as the Groth16 inputs).  Points are taken as given.
+struct KzgOpenings {
+  std::vector<G1Affine> c, pi;
+  std::vector<Fp> z, y;
+};
+namespace detail {
+struct KzgDevice {
+  DeviceBuffer c, z, y, pi;
+  size_t n;
+};
+inline KzgDevice kzg_upload(const char* who, const KzgOpenings& o) {
+  const size_t n = o.c.size();
+  if (o.pi.size() != n || o.z.size() != n || o.y.size() != n) throw Error(std::string(who) + ": length mismatch");
+  return KzgDevice{to_device_soa(o.c), to_device_soa(o.z), to_device_soa(o.y), to_device_soa(o.pi), n};
+}
+}  // namespace detail
+// F_i for every opening (sylow_hip_kzg_fold_batch); *infinity (if given) receives the identity flags
+inline std::vector<G1Affine> kzg_fold(const KzgOpenings& o, std::vector<uint8_t>* infinity = nullptr) {
+  detail::KzgDevice d = detail::kzg_upload("kzg_fold", o);
+  DeviceBuffer dout(d.n * sizeof(G1Affine) + 8), dinf(d.n + 8);
+  check(sylow_hip_kzg_fold_batch(d.c.as<uint64_t>(), nullptr, d.z.as<uint64_t>(), d.y.as<uint64_t>(), d.pi.as<uint64_t>(), nullptr, dout.as<uint64_t>(),
+                                 dinf.as<uint8_t>(), d.n, nullptr), "sylow_hip_kzg_fold_batch");
+  if (infinity) {
+    infinity->assign(d.n, 0);
+    if (d.n) check(sylow_hip_memcpy_d2h(infinity->data(), dinf.as<void>(), d.n, nullptr), "d2h");
+  }
+  return from_device_soa<G1Affine>(dout, d.n);
+}
+// The verifier's half of the SRS: tau_g2 = tau G2gen (G2 proper, not the identity) and its line table, built once and kept on the device.
+class KzgVerifier {
+ public:
+  explicit KzgVerifier(const G2Affine& tau_g2) : tau_(to_device_soa(std::vector<G2Affine>{tau_g2})), table_((size_t)sylow_hip_g2_line_table_words() * sizeof(int32_t) + 8) {
+    check(sylow_hip_g2_line_table(tau_.as<uint64_t>(), 1, 0, table_.as<int32_t>(), nullptr), "sylow_hip_g2_line_table");
+    check(sylow_hip_stream_sync(nullptr), "sync");
+  }
+  // ok[i] for every opening (sylow_hip_kzg_verify_line_table_batch against the cached table)
+  std::vector<uint8_t> verify(const KzgOpenings& o) const {
+    detail::KzgDevice d = detail::kzg_upload("KzgVerifier::verify", o);
+    std::vector<uint8_t> ok(d.n);
+    DeviceBuffer dok(d.n + 8);
+    check(sylow_hip_kzg_verify_line_table_batch(table_.as<int32_t>(), d.c.as<uint64_t>(), nullptr, d.z.as<uint64_t>(), d.y.as<uint64_t>(), d.pi.as<uint64_t>(), nullptr,
+                                                dok.as<uint8_t>(), d.n, nullptr), "sylow_hip_kzg_verify_line_table_batch");
+    if (d.n) check(sylow_hip_memcpy_d2h(ok.data(), dok.as<void>(), d.n, nullptr), "d2h");
+    check(sylow_hip_stream_sync(nullptr), "sync");
+    return ok;
+  }
+  // "are ALL of them valid?" as ONE boolean, the sound small-exponent test (sylow_hip_kzg_batch_verify_weighted): one weight per opening, drawn
+  // AFTER the openings are fixed; a batch with an invalid opening passes with probability at most 2^-(bits of the weights).  Like verify_all.
+  bool verify_all(const KzgOpenings& o, const std::vector<Fp>& weights, Gt* product = nullptr) const {
+    detail::KzgDevice d = detail::kzg_upload("KzgVerifier::verify_all", o);
+    if (weights.size() != d.n) throw Error("KzgVerifier::verify_all: one weight per opening");
+    auto dw = to_device_soa(weights);
+    DeviceBuffer dgt(sizeof(Gt) + 8), done(8);
+    check(sylow_hip_kzg_batch_verify_weighted(tau_.as<uint64_t>(), d.c.as<uint64_t>(), nullptr, d.z.as<uint64_t>(), d.y.as<uint64_t>(), d.pi.as<uint64_t>(), nullptr,
+                                              dw.as<uint64_t>(), d.n, dgt.as<uint64_t>(), done.as<uint8_t>(), nullptr), "sylow_hip_kzg_batch_verify_weighted");
+    uint8_t one = 0;
+    check(sylow_hip_memcpy_d2h(&one, done.as<void>(), 1, nullptr), "d2h"); check(sylow_hip_stream_sync(nullptr), "sync");
+    if (product) *product = from_device_soa<Gt>(dgt, 1)[0];
+    return one != 0;
+  }
+  // the same check with the table built inside the call (sylow_hip_kzg_verify_batch): what a one-shot caller without this holder would make
+  std::vector<uint8_t> verify_uncached(const KzgOpenings& o) const {
+    detail::KzgDevice d = detail::kzg_upload("KzgVerifier::verify_uncached", o);
+    std::vector<uint8_t> ok(d.n);
+    DeviceBuffer dok(d.n + 8);
+    check(sylow_hip_kzg_verify_batch(tau_.as<uint64_t>(), d.c.as<uint64_t>(), nullptr, d.z.as<uint64_t>(), d.y.as<uint64_t>(), d.pi.as<uint64_t>(), nullptr,
+                                     dok.as<uint8_t>(), d.n, nullptr), "sylow_hip_kzg_verify_batch");
+    if (d.n) check(sylow_hip_memcpy_d2h(ok.data(), dok.as<void>(), d.n, nullptr), "d2h");
+    check(sylow_hip_stream_sync(nullptr), "sync");
+    return ok;
+  }
+
+ private:
+  DeviceBuffer tau_, table_;
+};
 // Many signers, ONE message (examples/threshold_signing.rs:92-121): e(sig, G2gen) e(-H(msg), sum_j pubkeys[j]) == identity -- one hash, one G2
 // sum and two Miller loops whatever the number of keys.  `sig` is the signers' aggregate signature (sum() of the individual ones).
 inline bool verify_one_message(const std::vector<G2Affine>& pubkeys, const std::vector<uint8_t>& msg, const G1Affine& sig, Gt* product = nullptr) {

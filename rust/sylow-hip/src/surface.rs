@@ -831,6 +831,91 @@ pub fn groth16_batch_verify_weighted(dev: &Device, vk: &Groth16Vk, a: &DeviceG1,
     let words = dev.download_aos::<48>(&gt, 1)?;
     Ok((gt_from_words(&words[0]), dev.download(&one)?[0] != 0))
 }
+/// The verifier's half of a BN254 KZG SRS on the device: tau_g2 = tau G2gen (one point of G2 proper, never the identity, so the entry points
+/// take it without a flag array) and its line table, built once by `KzgSrs::new` and reused by every `kzg_verify`.
+pub struct KzgSrs {
+    pub tau_g2: DeviceG2,
+    table: DeviceBuf<i32>,
+}
+impl KzgSrs {
+    pub fn new(dev: &Device, tau_g2: DeviceG2) -> Result<Self, HipError> {
+        assert!(tau_g2.n == 1, "tau_g2 is a single point");
+        // SAFETY: no arguments.
+        let words = unsafe { ffi::sylow_hip_g2_line_table_words() } as usize;
+        let table = dev.alloc::<i32>(words)?;
+        // SAFETY: tau_g2 is a 1-element SoA array; table holds `words` int32.
+        device::check(unsafe { ffi::sylow_hip_g2_line_table(tau_g2.xy.as_ptr(), 1, 0, table.as_mut_ptr(), dev.stream) })?;
+        dev.sync()?;
+        Ok(KzgSrs { tau_g2, table })
+    }
+}
+/// n KZG openings (C_i, z_i, y_i, pi_i), each claiming f(z_i) = y_i for the polynomial committed in C_i.  z and y are any 256-bit words,
+/// taken mod r; a flagged C is the zero polynomial's commitment, a flagged pi the proof for a constant polynomial.
+pub struct KzgOpenings<'a> {
+    pub c: &'a DeviceG1,
+    pub z: &'a [Fr],
+    pub y: &'a [Fr],
+    pub pi: &'a DeviceG1,
+}
+impl KzgOpenings<'_> {
+    fn upload(&self, dev: &Device) -> Result<(usize, DeviceBuf<u64>, DeviceBuf<u64>), HipError> {
+        let n = self.c.n;
+        assert!(self.pi.n == n && self.z.len() == n && self.y.len() == n);
+        Ok((n, dev.upload_soa::<4>(&fr_words(self.z))?, dev.upload_soa::<4>(&fr_words(self.y))?))
+    }
+}
+/// F_i = C_i - y_i G1gen + z_i pi_i for every opening (`sylow_hip_kzg_fold_batch`): one launch, the identity as (0, 1) + flag.
+pub fn kzg_fold(dev: &Device, o: &KzgOpenings) -> Result<DeviceG1, HipError> {
+    let (n, dz, dy) = o.upload(dev)?;
+    let out = DeviceG1 { xy: dev.alloc::<u64>(8 * n)?, inf: dev.alloc::<u8>(n)?, n };
+    // SAFETY: n points with flags, 4 * n scalar words each, n outputs.
+    device::check(unsafe {
+        ffi::sylow_hip_kzg_fold_batch(o.c.xy.as_ptr(), o.c.inf.as_ptr(), dz.as_ptr(), dy.as_ptr(), o.pi.xy.as_ptr(), o.pi.inf.as_ptr(), out.xy.as_mut_ptr(),
+                                      out.inf.as_mut_ptr(), n, dev.stream)
+    })?;
+    Ok(out)
+}
+/// ok[i] = [ e(C_i - y_i G1gen + z_i pi_i, G2gen) e(-pi_i, tau_g2) == 1 ] against the SRS's cached line table
+/// (`sylow_hip_kzg_verify_line_table_batch`); identities follow EIP-197.
+pub fn kzg_verify(dev: &Device, srs: &KzgSrs, o: &KzgOpenings) -> Result<Vec<bool>, HipError> {
+    let (n, dz, dy) = o.upload(dev)?;
+    let ok = dev.alloc::<u8>(n)?;
+    // SAFETY: table built by KzgSrs::new on this device; n points with flags, 4 * n scalar words each, n flags out.
+    device::check(unsafe {
+        ffi::sylow_hip_kzg_verify_line_table_batch(srs.table.as_ptr(), o.c.xy.as_ptr(), o.c.inf.as_ptr(), dz.as_ptr(), dy.as_ptr(), o.pi.xy.as_ptr(), o.pi.inf.as_ptr(),
+                                                   ok.as_mut_ptr(), n, dev.stream)
+    })?;
+    Ok(dev.download(&ok)?.into_iter().map(|v| v != 0).collect())
+}
+/// The same with the line table of tau_g2 built inside the call (`sylow_hip_kzg_verify_batch`): for a key used once.
+pub fn kzg_verify_once(dev: &Device, tau_g2: &DeviceG2, o: &KzgOpenings) -> Result<Vec<bool>, HipError> {
+    assert!(tau_g2.n == 1);
+    let (n, dz, dy) = o.upload(dev)?;
+    let ok = dev.alloc::<u8>(n)?;
+    // SAFETY: one G2 point; n points with flags, 4 * n scalar words each, n flags out.
+    device::check(unsafe {
+        ffi::sylow_hip_kzg_verify_batch(tau_g2.xy.as_ptr(), o.c.xy.as_ptr(), o.c.inf.as_ptr(), dz.as_ptr(), dy.as_ptr(), o.pi.xy.as_ptr(), o.pi.inf.as_ptr(),
+                                        ok.as_mut_ptr(), n, dev.stream)
+    })?;
+    Ok(dev.download(&ok)?.into_iter().map(|v| v != 0).collect())
+}
+/// The SOUND one-boolean form for n KZG openings (`sylow_hip_kzg_batch_verify_weighted`): `weights` drawn by the caller AFTER the openings
+/// are fixed (any 256-bit words, taken mod r; 0 removes an opening).  True when every opening is valid; a batch with an invalid one passes
+/// with probability at most 2^-(bits of the weights), given tau_g2 in the r-torsion.
+pub fn kzg_batch_verify_weighted(dev: &Device, tau_g2: &DeviceG2, o: &KzgOpenings, weights: &[Fr]) -> Result<(GtOut, bool), HipError> {
+    assert!(tau_g2.n == 1);
+    let (n, dz, dy) = o.upload(dev)?;
+    assert!(weights.len() == n);
+    let dw = dev.upload_soa::<4>(&fr_words(weights))?;
+    let (gt, one) = (dev.alloc::<u64>(48)?, dev.alloc::<u8>(1)?);
+    // SAFETY: as kzg_verify_once, 4 * n weight words; gt 48 words; one 1 byte.
+    device::check(unsafe {
+        ffi::sylow_hip_kzg_batch_verify_weighted(tau_g2.xy.as_ptr(), o.c.xy.as_ptr(), o.c.inf.as_ptr(), dz.as_ptr(), dy.as_ptr(), o.pi.xy.as_ptr(), o.pi.inf.as_ptr(),
+                                                 dw.as_ptr(), n, gt.as_mut_ptr(), one.as_mut_ptr(), dev.stream)
+    })?;
+    let words = dev.download_aos::<48>(&gt, 1)?;
+    Ok((gt_from_words(&words[0]), dev.download(&one)?[0] != 0))
+}
 /// AND of a device-resident flag vector (one rank; `all_valid` in lib.rs adds the reduce over ranks).
 pub fn flags_all(dev: &Device, flags: &DeviceBuf<u8>) -> Result<bool, HipError> {
     let out = dev.alloc::<i32>(1)?;

@@ -545,6 +545,36 @@ def groth16_verify(vk: Groth16VerifyingKey, a: G1Affine, b: G2Affine, c: G1Affin
     return engine().groth16_verify(vk.arrays(), a.xy, b.xy, c.xy, x, a.infinity, b.infinity, c.infinity).astype(bool)
 
 
+class KzgVerifier:
+    """The verifier's half of a BN254 KZG SRS: tau_g2 = tau G2gen (one point of G2 proper, not the identity) and its line table, built on
+    first use and kept on the device.  An opening is (C, z, y, pi) and claims f(z) = y for the polynomial committed in C; `openings` below is
+    the tuple (c: G1Affine, z, y, pi: G1Affine) with z, y as [n, 4] words or Python ints -- any 256-bit values, taken mod r."""
+
+    def __init__(self, tau_g2: G2Affine):
+        if len(tau_g2) != 1 or tau_g2.infinity.any():
+            raise ValueError("KzgVerifier: tau_g2 is a single point of G2, not the identity")
+        self.tau_g2, self._table = tau_g2, None
+
+    @staticmethod
+    def _words(v):
+        a = np.asarray(v)
+        return fp([int(x) for x in np.asarray(v, dtype=object).reshape(-1)]) if a.dtype == object or a.ndim == 1 else a
+
+    def verify(self, openings) -> np.ndarray:
+        """ok[i] = [ e(C_i - y_i G1gen + z_i pi_i, G2gen) e(-pi_i, tau_g2) == 1 ]; identities follow EIP-197 (a flagged pi proves a constant
+        polynomial: the row is valid iff C = y G1gen).  Points are taken as given."""
+        c, z, y, pi = openings
+        if self._table is None:
+            self._table = engine().g2_line_table(self.tau_g2.xy)
+        return engine().kzg_verify_line_table(self._table, c.xy, self._words(z), self._words(y), pi.xy, c.infinity, pi.infinity).astype(bool)
+
+    def verify_weighted(self, openings, weights) -> bool:
+        """"are ALL of them valid?" as ONE boolean, the sound small-exponent test (sylow_hip_kzg_batch_verify_weighted): one weight per opening,
+        drawn AFTER the openings are fixed; a batch with an invalid opening passes with probability at most 2^-(bits of the weights)."""
+        c, z, y, pi = openings
+        return engine().kzg_batch_verify_weighted(self.tau_g2.xy, c.xy, self._words(z), self._words(y), pi.xy, self._words(weights), c.infinity, pi.infinity)[1]
+
+
 class KeyPair:
     """KeyPair (lib.rs:105-137), a batch of them: secret_key = Fp::new(Fr::rand().value()) -- a scalar below r held as an Fp --
     and public_key = G2Projective::generator() * secret_key."""

@@ -118,6 +118,10 @@ int32_t sum_tree_strided(uint64_t* acc, size_t acc_stride, size_t m, uint64_t* o
 size_t sum_segments_scratch_words(size_t n_seg, size_t c);
 int32_t sum_segments(const uint64_t* p_xy, const uint8_t* p_inf, size_t n_seg, size_t c, uint64_t* acc, uint64_t* out_xy, uint8_t* out_inf, void* stream);
 }  // namespace g1h
+namespace kzgh {        // kzg.hip: F_i = C_i - y_i G1gen + z_i pi_i (affine SoA + flags, stride n) and, when neg_xy is given, -pi_i beside it: one launch
+int32_t fold(const uint64_t* c_xy, const uint8_t* c_inf, const uint64_t* z, const uint64_t* y, const uint64_t* pi_xy, const uint8_t* pi_inf,
+             uint64_t* out_xy, uint8_t* out_inf, uint64_t* neg_xy, uint8_t* neg_inf, size_t n, void* stream);
+}  // namespace kzgh
 namespace plkh {        // lane-pair units
 // selectors of plk_pairing.hip's Fp12 kernel (sylow_hip_fp12_hook_batch, and the Fp12 entry points of tower.hip)
 enum { OPW_MUL = 16, OPW_SQR = 17, OPW_SPARSE = 18, OPW_CYCSQR = 19, OPW_FROB1 = 20, OPW_FROB2 = 21, OPW_FROB3 = 22, OPW_EXPZ = 23,

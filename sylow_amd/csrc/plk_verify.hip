@@ -278,6 +278,46 @@ int32_t sylow_hip_bls_verify_line_table_batch(const int32_t* pk_table, const uin
   if (rc != SYLOW_HIP_OK) return rc;
   return launch_fused<true>(nullptr, pk_inf, pk_table, hash_library(msgs, msg_offsets, n, stream), sig_xy, sig_inf, gen, ok, n, stream);
 }
+}  // extern "C"
+// KZG openings under one SRS (include/sylow_hip.h, "KZG"): e(F_i, G2gen) e(-pi_i, tau_g2) == 1 with F_i = C_i - y_i G1gen + z_i pi_i is the
+// same-signer check with sig := F, -H := -pi and tau_g2 as the key.  The "hashing step" is kzg.hip's fold, ONE launch that writes F into a
+// block leased here and -pi straight into the block the route leases for -H; the routes by size and the pairing kernels are the same-signer
+// call's.  tau_xy NULL: the caller's cached table, which -- like sylow_hip_bls_verify_line_table_batch -- has no one-wavefront route.
+static int32_t kzg_verify(const uint64_t* tau_xy, const bn254::i32* tau_table, const uint64_t* c_xy, const uint8_t* c_inf, const uint64_t* z, const uint64_t* y,
+                          const uint64_t* pi_xy, const uint8_t* pi_inf, uint8_t* ok, size_t n, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  host::Lease wf, wt;
+  int32_t rc = wf.acquire(8 * n * sizeof(u64) + n, st);
+  if (rc != SYLOW_HIP_OK) return rc;
+  u64* f_xy = (u64*)wf.p;
+  uint8_t* f_inf = (uint8_t*)(f_xy + 8 * n);
+  auto fold = [=](u64* h, uint8_t* hinf, int) { return kzgh::fold(c_xy, c_inf, z, y, pi_xy, pi_inf, f_xy, f_inf, h, hinf, n, stream); };
+  if (tau_xy && n <= plkh::wide_verify_max())
+    return host::finish(verify_small(fold, n, 96, /*negate=*/1, stream, [&](const u64* hneg, const uint8_t* hinf, u64* scratch) {
+      return plkh::verify_wide_batch(tau_xy, nullptr, hneg, hinf, f_xy, f_inf, scratch, ok, n, stream, /*one_key=*/1);
+    }), wf);
+  const bn254::i32* gen = nullptr;
+  if ((rc = host::gen_lines29(&gen, st)) != SYLOW_HIP_OK) return host::finish(rc, wf);
+  if (!tau_table) {
+    if ((rc = wt.acquire(plk::LINE_TABLE_WORDS * sizeof(bn254::i32), st)) != SYLOW_HIP_OK) return host::finish(rc, wf);
+    plk::k_g2_lines29<<<1, plk::LINES_BLOCK, 0, st>>>(tau_xy, 1, 0, (bn254::i32*)wt.p);     // tau_g2 is a 1-element SoA array
+    tau_table = (const bn254::i32*)wt.p;
+  }
+  return host::finish(launch_fused<true>(tau_xy, nullptr, tau_table, fold, f_xy, f_inf, gen, ok, n, stream), wf, wt);
+}
+extern "C" {
+int32_t sylow_hip_kzg_verify_batch(const uint64_t* tau_g2_xy, const uint64_t* c_xy, const uint8_t* c_inf, const uint64_t* z, const uint64_t* y,
+                                   const uint64_t* pi_xy, const uint8_t* pi_inf, uint8_t* ok, size_t n, void* stream) {
+  ARGCHK(ok && (n == 0 || (tau_g2_xy && c_xy && z && y && pi_xy))); if (!n) return SYLOW_HIP_OK;
+  return kzg_verify(tau_g2_xy, nullptr, c_xy, c_inf, z, y, pi_xy, pi_inf, ok, n, stream);
+}
+int32_t sylow_hip_kzg_verify_line_table_batch(const int32_t* tau_table, const uint64_t* c_xy, const uint8_t* c_inf, const uint64_t* z, const uint64_t* y,
+                                              const uint64_t* pi_xy, const uint8_t* pi_inf, uint8_t* ok, size_t n, void* stream) {
+  ARGCHK(ok && (n == 0 || (tau_table && c_xy && z && y && pi_xy))); if (!n) return SYLOW_HIP_OK;
+  return kzg_verify(nullptr, tau_table, c_xy, c_inf, z, y, pi_xy, pi_inf, ok, n, stream);
+}
+}  // extern "C"
+extern "C" {
 // verify (lib.rs:223-236) with H from a caller-chosen expander and tag: the hashing launch changes, the routes by size and the pairing kernels do not
 int32_t sylow_hip_bls_verify_expander_batch(int32_t expander, const uint8_t* dst_host, size_t dst_len, int32_t security_bits,
                                             const uint64_t* pk_xy, const uint8_t* pk_inf, const uint8_t* msgs, const uint64_t* msg_offsets,

@@ -958,6 +958,59 @@ class Engine:
                    self._ptr(dbi), self._ptr(dc), self._ptr(dci), self._ptr(dx), self._ptr(dw), n, dgt.ptr, dis.ptr)
         return self.from_device_soa(dgt), bool(dis.download()[0])
 
+    # ---- KZG openings under one SRS.  tau_g2 [1, 16]; an opening is (C [8], z [4], y [4], pi [8]); z, y and weights: any 256-bit words,
+    # taken mod r ----
+    def _kzg_openings(self, c_xy, z, y, pi_xy, c_inf, pi_inf):
+        c_xy, z, y, pi_xy = _aos(c_xy, 8), _aos(z, 4), _aos(y, 4), _aos(pi_xy, 8)
+        n = c_xy.shape[0]
+        assert z.shape[0] == n and y.shape[0] == n and pi_xy.shape[0] == n
+        up = lambda x, w: self.to_device_soa(x, w) if n else None
+        fl = lambda x: self._flags(x, n) if n else None
+        return n, (up(c_xy, 8), fl(c_inf), up(z, 4), up(y, 4), up(pi_xy, 8), fl(pi_inf))      # the caller holds them across its call
+
+    def kzg_fold(self, c_xy, z, y, pi_xy, c_inf=None, pi_inf=None):
+        """F_i = C_i - y_i G1gen + z_i pi_i for every opening (sylow_hip_kzg_fold_batch): ([n, 8] affine words, [n] flags)."""
+        n, d = self._kzg_openings(c_xy, z, y, pi_xy, c_inf, pi_inf)
+        args = [self._ptr(x) for x in d]
+        do, doi = self.empty((8, max(n, 1))), self.empty((max(n, 1),), np.uint8)
+        self._call("sylow_hip_kzg_fold_batch", *args, do.ptr, doi.ptr, n)
+        return self.from_device_soa(do)[:n], doi.download()[:n]
+
+    def kzg_verify(self, tau_g2, c_xy, z, y, pi_xy, c_inf=None, pi_inf=None):
+        """e(C_i - y_i G1gen + z_i pi_i, G2gen) e(-pi_i, tau_g2) == 1 for every opening under one SRS (sylow_hip_kzg_verify_batch): [n]
+        uint8.  Identities follow EIP-197; tau_g2 must be in G2 proper."""
+        tau_g2 = _aos(tau_g2, 16)
+        assert tau_g2.shape[0] == 1
+        dtau = self.to_device_soa(tau_g2, 16)
+        n, d = self._kzg_openings(c_xy, z, y, pi_xy, c_inf, pi_inf)
+        args = [self._ptr(x) for x in d]
+        dok = self.empty((max(n, 1),), np.uint8)
+        self._call("sylow_hip_kzg_verify_batch", dtau.ptr, *args, dok.ptr, n)
+        return dok.download()[:n]
+
+    def kzg_verify_line_table(self, table: DeviceArray, c_xy, z, y, pi_xy, c_inf=None, pi_inf=None):
+        """The same against a line table of tau_g2 cached with g2_line_table (sylow_hip_kzg_verify_line_table_batch)."""
+        n, d = self._kzg_openings(c_xy, z, y, pi_xy, c_inf, pi_inf)
+        args = [self._ptr(x) for x in d]
+        dok = self.empty((max(n, 1),), np.uint8)
+        self._call("sylow_hip_kzg_verify_line_table_batch", table.ptr, *args, dok.ptr, n)
+        return dok.download()[:n]
+
+    def kzg_batch_verify_weighted(self, tau_g2, c_xy, z, y, pi_xy, weights, c_inf=None, pi_inf=None):
+        """The small-exponent batch test of n KZG openings as ONE Gt (sylow_hip_kzg_batch_verify_weighted); weights [n, 4] drawn by the
+        caller after the openings are fixed (any 256-bit words, taken mod r; 0 removes an opening).  Returns (Gt words [1, 48], bool)."""
+        tau_g2 = _aos(tau_g2, 16)
+        assert tau_g2.shape[0] == 1
+        dtau = self.to_device_soa(tau_g2, 16)
+        n, d = self._kzg_openings(c_xy, z, y, pi_xy, c_inf, pi_inf)
+        args = [self._ptr(x) for x in d]
+        weights = _aos(weights, 4)
+        assert weights.shape[0] == n
+        dw = self.to_device_soa(weights, 4) if n else None
+        dgt, dis = self.empty((48, 1)), self.empty((1,), np.uint8)
+        self._call("sylow_hip_kzg_batch_verify_weighted", dtau.ptr, *args, self._ptr(dw), n, dgt.ptr, dis.ptr)
+        return self.from_device_soa(dgt), bool(dis.download()[0])
+
     def bls_aggregate_partial(self, pk_xy, msgs, sig_xy, weights=None, pk_inf=None, sig_inf=None):
         """One shard's raw Miller product of the (weighted) aggregate check, [1, 48] words: the input of fp12_product_final_exp."""
         pk_xy, sig_xy = _aos(pk_xy, 16), _aos(sig_xy, 8)

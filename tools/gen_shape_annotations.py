@@ -124,6 +124,11 @@ G16_PROOFS = "a_xy=u64[8*n] a_inf=u8[n]? b_xy=u64[16*n] b_inf=u8[n]? c_xy=u64[8*
 S["groth16_vk_x_batch"] = "vk_ic=u64[8*(n_inputs+1)] inputs=u64[4*n_inputs*n]? out_xy=u64[8*n] out_inf=u8[n]"
 S["groth16_verify_batch"] = G16_VK + " " + G16_PROOFS + " ok=u8[n]"
 S["groth16_batch_verify_weighted"] = G16_VK + " " + G16_PROOFS + " weights=u64[4*n] gt_out=u64[48]? is_one=u8[1]?"
+KZG = "c_xy=u64[8*n] c_inf=u8[n]? z=u64[4*n] y=u64[4*n] pi_xy=u64[8*n] pi_inf=u8[n]?"
+S["kzg_fold_batch"] = KZG + " out_xy=u64[8*n] out_inf=u8[n]"
+S["kzg_verify_batch"] = "tau_g2_xy=u64[16] " + KZG + " ok=u8[n]"
+S["kzg_verify_line_table_batch"] = "tau_table=i32[*] " + KZG + " ok=u8[n]"
+S["kzg_batch_verify_weighted"] = "tau_g2_xy=u64[16] " + KZG + " weights=u64[4*n] gt_out=u64[48]? is_one=u8[1]?"
 S["pairing_host"] = "p_aos=u64[8*n] p_inf=u8[n]? q_aos=u64[16*n] q_inf=u8[n]? gt_aos=u64[48*n]"
 S["bls_verify_host"] = "pk_aos=u64[16*n] pk_inf=u8[n]? msgs=u8[*]? msg_offsets=u64[n+1] sig_aos=u64[8*n] sig_inf=u8[n]? ok=u8[n]"
 S["pairing_host_bytes"] = "p_be=u8[64*n] q_be=u8[128*n] gt_aos=u64[48*n] status_p=u8[n] status_q=u8[n]"
