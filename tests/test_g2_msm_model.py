@@ -1,5 +1,5 @@
-"""CPU: the host-side recoding and planning of sylow_hip_g2_msm (the g2_* functions of tools/msm_model.py mirror sylow_amd/csrc/g2_msm.hpp and
-the MOD_R = false side of msm_scalar.hpp).  The one place where G2 is not a copy of G1: the digits are those of k mod p itself."""
+"""CPU: the host-side recoding and planning of sylow_hip_g2_msm (the g2_* functions of tools/msm_model.py mirror sylow_amd/csrc/msm_bucket.hpp under
+the lane-pair policy of g2_msm.hpp, MOD_R = false).  The one place where G2 is not a copy of G1: the digits are those of k mod p itself."""
 import os
 import random
 import re
@@ -82,14 +82,19 @@ def test_g2_plan_and_scratch_are_monotone_in_the_chunk_size():
 
 
 def test_the_model_mirrors_the_sources():
-    src = open(os.path.join(ROOT, "sylow_amd", "csrc", "g2_msm.hpp")).read()
-    num = lambda name, text: int(re.search(name + r" = (?:\(size_t\))?(\d+)", text).group(1))
-    assert num("W54", src) == M.W54 and num("PT2_WORDS", src) == M.G2_PT_WORDS
-    assert num("MSM_SEG", src) == M.MSM_SEG and num("MSM_RUN", src) == M.MSM_RUN
-    assert int(re.search(r"G2_MSM_DEFAULT_MIN = \(size_t\)1 << (\d+)", src).group(1)) == M.G2_DEFAULT_MIN.bit_length() - 1
-    assert num("G2_MSM_WIDE_C", src) == M.G2_WIDE_C and int(re.search(r"G2_MSM_WIDE_FROM = \(size_t\)1 << (\d+)", src).group(1)) == 16
+    csrc = os.path.join(ROOT, "sylow_amd", "csrc")
+    src, shared = open(os.path.join(csrc, "g2_msm.hpp")).read(), open(os.path.join(csrc, "msm_bucket.hpp")).read()
+    num = lambda name, text: int(re.search(r"\b" + name + r" = (?:\(size_t\))?(\d+)", text).group(1))
+    # a lane pair per point: a bucket is LANES * 27 words, a prepared point LANES * 20
+    assert num("LANES", src) == 2 and "PROJ_WORDS = PROJ_LANE_WORDS * G::LANES" in shared and "PT_WORDS = PT_LANE_WORDS * G::LANES" in shared
+    assert num("LANES", src) * num("PROJ_LANE_WORDS", shared) == M.W54 and num("LANES", src) * num("PT_LANE_WORDS", shared) == M.G2_PT_WORDS
+    assert num("MSM_SEG", shared) == M.MSM_SEG and num("MSM_RUN", shared) == M.MSM_RUN
+    assert int(re.search(r"\bDEFAULT_MIN = \(size_t\)1 << (\d+)", src).group(1)) == M.G2_DEFAULT_MIN.bit_length() - 1
+    assert num("WIDE_C", src) == M.G2_WIDE_C and int(re.search(r"\bWIDE_FROM = \(size_t\)1 << (\d+)", src).group(1)) == 16
+    assert "return n >= WIDE_FROM ? WIDE_C : msm::default_window(n);" in src
     assert [M.g2_default_window(1 << lg) for lg in (10, 12, 14, 15, 16, 17, 18, 20, 24)] == [8, 8, 10, 10, 15, 15, 15, 15, 15]
     assert M.g2_default_window((1 << 16) - 1) == M.default_window((1 << 16) - 1) == 10
-    assert "k_msm_hist<false>" in src and "k_msm_scatter<false>" in src          # the digits of k mod p: no mod-r step on the twist
-    g1 = open(os.path.join(ROOT, "sylow_amd", "csrc", "msm.hip")).read()
-    assert "k_msm_hist<true>" in g1 and "k_msm_scatter<true>" in g1
+    assert re.search(r"\bMOD_R = false;", src)                                    # the digits of k mod p: no mod-r step on the twist
+    assert "if (G::MOD_R) cond_sub_const" in shared and "msm_scalar<G>(k, ks, n, i);" in shared
+    g1 = open(os.path.join(csrc, "msm.hip")).read()
+    assert re.search(r"\bMOD_R = true;", g1) and "msm::tuned<msmh::G1Lane>" in g1 and "msm::tuned<plk::G2Pair>" in src

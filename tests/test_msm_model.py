@@ -1,4 +1,4 @@
-"""CPU: the host-side recoding and planning of sylow_hip_g1_msm (tools/msm_model.py mirrors sylow_amd/csrc/msm.hip)."""
+"""CPU: the host-side recoding and planning of sylow_hip_g1_msm (tools/msm_model.py mirrors sylow_amd/csrc/msm_bucket.hpp and the G1 policy of msm.hip)."""
 import os
 import random
 import re
@@ -65,10 +65,14 @@ def test_scratch_formula_and_plan():
 
 
 def test_model_constants_match_the_kernel_unit():
-    src = open(os.path.join(ROOT, "sylow_amd", "csrc", "msm.hip")).read()
-    const = dict(re.findall(r"constexpr (?:int|size_t) (\w+) = ([^,;]+)[,;]", src))
+    csrc = os.path.join(ROOT, "sylow_amd", "csrc")
+    const = dict(re.findall(r"constexpr (?:int|size_t|bool) (\w+) = ([^,;]+)[,;]", open(os.path.join(csrc, "msm_bucket.hpp")).read()))
     assert int(const["MSM_SEG"]) == M.MSM_SEG and int(const["MSM_RUN"]) == M.MSM_RUN
     assert int(const["MSM_C_MIN"]) == M.C_MIN and int(const["MSM_C_MAX"]) == M.C_MAX
     assert const["MSM_DEFAULT_BUDGET"].strip() == "(size_t)1 << 30" and M.DEFAULT_BUDGET == 1 << 30
-    assert const["MSM_DEFAULT_MIN"].strip() == "(size_t)1 << 18" and M.DEFAULT_MIN == 1 << 18
-    assert int(const["W27"]) == M.W27 and int(const["PT_WORDS"]) == M.PT_WORDS
+    # the G1 policy: one lane per point, so a bucket is LANES * 27 words and a prepared point LANES * 20; scalars reduced mod r
+    g1 = dict(re.findall(r"constexpr (?:int|size_t|bool) (\w+) = ([^,;]+)[,;]", open(os.path.join(csrc, "msm.hip")).read()))
+    assert g1["DEFAULT_MIN"].strip() == "(size_t)1 << 18" and M.DEFAULT_MIN == 1 << 18
+    assert int(g1["LANES"]) == 1 and g1["MOD_R"].strip() == "true"
+    assert int(g1["LANES"]) * int(const["PROJ_LANE_WORDS"]) == M.W27 and int(g1["LANES"]) * int(const["PT_LANE_WORDS"]) == M.PT_WORDS
+    assert "PROJ_WORDS = PROJ_LANE_WORDS * G::LANES" in open(os.path.join(csrc, "msm_bucket.hpp")).read()

@@ -1,8 +1,9 @@
-"""Model of the host-side recoding and planning of sylow_hip_g1_msm (sylow_amd/csrc/msm.hip): the signed c-bit digits of a scalar, the
-window / bucket counts, the chunk plan under a scratch budget and the scratch-byte formula.  Every formula here mirrors the C++ one by one;
-tests/test_msm_model.py pins them, and tests/test_gpu_msm.py uses scratch_bytes to force chunking.  The g2_* functions are the same model
-for sylow_hip_g2_msm (sylow_amd/csrc/g2_msm.hpp): the digits are those of k mod p itself (a twist point need not have order r), and a bucket
-and a prepared point are twice as wide (lane pairs); tests/test_g2_msm_model.py pins them.
+"""Model of the host-side recoding and planning of sylow_hip_g1_msm (sylow_amd/csrc/msm_bucket.hpp under the one-lane policy of msm.hip):
+the signed c-bit digits of a scalar, the window / bucket counts, the chunk plan under a scratch budget and the scratch-byte formula.  Every
+formula here mirrors the C++ one by one; tests/test_msm_model.py pins them, and tests/test_gpu_msm.py uses scratch_bytes to force chunking.
+The g2_* functions are the same model for sylow_hip_g2_msm (the same header under the lane-pair policy of g2_msm.hpp): the digits are those
+of k mod p itself (a twist point need not have order r), and a bucket and a prepared point are twice as wide (lane pairs);
+tests/test_g2_msm_model.py pins them.
 
     python tools/msm_model.py            # prints the plan for n = 2^12 .. 2^24"""
 import json
@@ -113,7 +114,7 @@ def plan(n: int, c: int, budget: int = DEFAULT_BUDGET):
     return nc, scratch_bytes(c, nc)
 
 
-# ---- G2 (g2_msm.hpp): the same scalar side without the mod-r step, the same plan with lane-pair sizes ----
+# ---- G2 (the lane-pair policy of g2_msm.hpp): the same scalar side without the mod-r step, the same plan with lane-pair sizes ----
 G2_DEFAULT_MIN = 1 << 16
 G2_WIDE_FROM, G2_WIDE_C = 1 << 16, 15   # from this n on the default window is G2_WIDE_C (measured: DESIGN.md §4.3)
 W54 = 54              # i32 words of a projective lane-pair point: 27 per lane
