@@ -8,12 +8,18 @@ the equation alone.
 Identities follow pairing() / EIP-197: a pair with an identity on either side contributes 1 (it is left out of the product).  z, y and
 weights are any 256-bit integers, taken mod r."""
 import copy
+import os
 import random
+import sys
+import types
 
 import numpy as np
 
 import groth16_model as G
 from groth16_model import C, ONE48, P, R, ints, limbs  # noqa: F401  (re-exported for the tests)
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
+import glv_model  # noqa: E402  (the limb-exact model of glv_decompose: the authority for choosing the crafted z)
 
 DEFECTS = ("y_plus_one", "z_plus_one", "pi_swapped", "c_negated", "c_identity_valid", "pi_identity_valid", "pi_identity_invalid", "f_identity")
 # what the boolean of a row carrying the defect must be
@@ -187,3 +193,125 @@ def weighted_product(inst, weights):
     p, q = model_weighted(inst, weights)
     keep = ~G.is_identity(p)
     return G.products([[(p[k], q[k]) for k in range(2) if keep[k]]])[0]
+
+
+# ---- crafted scalars for the two digit walks of the fold -------------------------------------------------------------------------
+# z pi: z mod r splits into two magnitudes (glv_model.decompose_device); each is walked as 33 signed nibbles, digit i = nibble i of
+# m + 0x88...8 (33 eights) minus 8.  y G1gen: y mod r as 32 signed bytes with a carry, digit d in [-128, 127], table entry |d| - 1.
+GLV_BIAS = int("8" * 33, 16)
+GLV_TOP = (1 << 128) - int("8" * 32, 16)                       # 0x77...78: the least magnitude whose window 32 is 1 (all other digits -8)
+GLV_SEVENS = int("7" * 32, 16)                                 # every digit 7, window 32 zero
+
+
+def glv_halves(z):
+    """((|k1|, k1 < 0), (|k2|, k2 < 0)) of z mod r, as the device computes them"""
+    return glv_model.decompose_device(int(z) % R)
+
+
+def glv_window_digits(m):
+    assert 0 <= m < 1 << 128
+    b = m + GLV_BIAS
+    return [((b >> (4 * i)) & 15) - 8 for i in range(33)]
+
+
+def comb_digits(y):
+    y, carry, out = int(y) % R, 0, []
+    for w in range(32):
+        d = ((y >> (8 * w)) & 255) + carry
+        carry = int(d >= 128)
+        out.append(d - (carry << 8))
+    assert carry == 0
+    return out
+
+
+_CRAFTED = []
+
+
+def crafted_fold_scalars():
+    """A fixed list of (tag, value) for z and for y: ns.z, ns.y.  The z are FOUND with the model (seeded searches, a few thousand
+    decompositions): a pair of chosen halves t1 + t2 lambda comes back as itself only when z lands where the model's rounding allows it, so
+    every candidate is decomposed and kept only if it shows the property of its tag.
+
+    What the model can and cannot reach (tests/test_kzg_model.py asserts the reachable part, and that the searches below found nothing of
+    the rest).  With c_i = floor(z g_i / 2^256) both halves are k1 = e1 a1 + e2 a2 and k2 = e1 b1 - e2 a1 with rounding deficits
+    e1 in [0, 1.09), e2 in [0, 1) (a1 ~ 2^63, a2 ~ b1 ~ 0x6f4d 2^112; e1 passes 1 because g_1 is cut to 66 bits and z / 2^256 < 0.19), so
+      * k1 >= 0 always, k1 = 0 only for z = 0, and k1 < a2 + 1.09 a1 < 0x77...78: window 32 of the k1 half is never 1, the k1 half is never
+        negative, and "k1 = 0, k2 != 0" does not exist;
+      * k2 is negative only when e1 < 2^-63, and then |k2| < a1 < 2^64: flip2 (n1 != n2) is reachable, but never together with window 32;
+      * k2 >= 0x77...78 needs e1 > 1.07: z in the top tenth of [0, r);
+      * k2 = 0x77...78 and k2 = 0x77...77 exactly are not reachable (z = t1 + k2 lambda moves by less than 2^127 with t1, and neither lands
+        in the top tenth): the list holds the nearest, one nibble above window 15 changed, 31 of 32 digits as asked."""
+    if _CRAFTED:
+        return _CRAFTED[0]
+    import evm_model
+    lam, z = glv_model.lam, []
+    k2_of = lambda v: glv_halves(v)[1]
+    rng = random.Random(0x61D)
+    while sum(t == "k2_top" for t, _ in z) < 6:                # window 32 of the k2 half (digit 31 is then -8)
+        v = R - 1 - rng.randrange(R >> 4)
+        if k2_of(v)[0] >= GLV_TOP:
+            z.append(("k2_top", v))
+    for tag, half, lo, hi in (("k1_digit31_7", 0, 7 << 124, 1 << 128), ("k2_digit31_7", 1, 7 << 124, GLV_TOP)):
+        found = 0
+        while found < 2:
+            v = R - 1 - rng.randrange(R >> 4)
+            if lo <= glv_halves(v)[half][0] < hi:
+                z.append((tag, v))
+                found += 1
+
+    def nearest(base, sign):                                   # base with ONE nibble (16..30) changed, as the k2 half
+        for j in range(16, 31):
+            for d in range(1, 16):
+                t2 = base + sign * d * 16 ** j
+                for t1 in (3 << 124, 0x64 << 120, 1 << 120):
+                    v = (t1 + t2 * lam) % R
+                    if k2_of(v) == (t2, False):
+                        return v
+    z.append(("k2_near_all_minus_8", nearest(GLV_TOP, 1)))
+    z.append(("k2_near_all_7", nearest(GLV_SEVENS, -1)))
+    z += [("k2_zero", v) for v in (1, 0xFFFFFFFFFFFFFFFF, (1 << 125) + 0x123456789ABCDEF)]
+    for j in (1, 2, 3, 5, 0xC0FFEE, 0xC0FFEF, (1 << 62) + 12345, (1 << 62) + 12346):      # z g_1 just above j 2^256: e1 ~ 0, k2 < 0
+        v = -((-j << 256) // glv_model.g1c)
+        if v < R and k2_of(v)[1]:
+            z.append(("k2_negative", v))
+    z += [("edge", v % R) for v in evm_model.glv_edge_scalars()]
+    below = lambda byte, top: top << 248 | int.from_bytes(bytes([byte]) * 31, "big")
+    y = [("all_80", below(0x80, 0x2F)), ("all_7f", below(0x7F, 0x2F)), ("all_ff", below(0xFF, 0x2F)), ("all_80_top_0", below(0x80, 0)),
+         ("alternating", int("30" + "7f80" * 15 + "80", 16)),     # >= r: the kernel reduces it
+         ("alternating_807f", int("2f" + "807f" * 15 + "80", 16)),
+         ("alternating_7f80", int("2f" + "7f80" * 15 + "80", 16)), ("r_minus_1", R - 1), ("top_digit_max", 0x30 << 248),
+         ("top_digit_max_by_carry", below(0xFF, 0x2F) - 0x7F)]
+    _CRAFTED.append(types.SimpleNamespace(z=z, y=y))
+    return _CRAFTED[0]
+
+
+def crafted_instance(seed=0xC4AF):
+    """Openings that pair every crafted z with a random y and every crafted y with a random z (the edge scalars once, the others twice), pi
+    cycling through random generator multiples, G1gen and -G1gen; the maker knows tau and makes about half of the rows valid openings
+    (C = y G1gen + (tau - z) pi), the others carry a random C.  No row is flagged.  -> (Instance, the maker's booleans)"""
+    cs, rng = crafted_fold_scalars(), random.Random(seed)
+    fr = lambda: rng.randrange(1, R)
+    zs, ys = [], []
+    for tag, v in cs.z:
+        for _ in range(1 if tag == "edge" else 2):
+            zs.append(v)
+            ys.append(fr())
+    for tag, v in cs.y:
+        for _ in range(2):
+            zs.append(fr())
+            ys.append(v)
+    tau, n = fr(), len(zs)
+    pi = [(fr(), 1, fr(), R - 1)[i % 4] for i in range(n)]
+    valid = np.array([(i // 4 + i) % 2 == 0 for i in range(n)], dtype=bool)
+    c = [(ys[i] + (tau - zs[i]) * pi[i]) % R if valid[i] else fr() for i in range(n)]
+    assert all(v != 0 for v in c)
+    return Instance(tau, c, zs, ys, pi), valid
+
+
+def collapse_weights(idx, weights, pool_n):
+    """A batch tiled from a pool (row i is pool row idx[i]) under weights r_i is, for the weighted test, the pool itself under the sums of
+    the weights that fall on each pool row: the two literal pairs are linear in r_i with C, z, y and pi fixed per pool row.  -> pool_n ints"""
+    out = [0] * pool_n
+    for i, w in zip(np.asarray(idx).tolist(), weights):
+        out[i] = (out[i] + int(w)) % R
+    return out
