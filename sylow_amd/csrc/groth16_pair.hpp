@@ -1,5 +1,6 @@
 // groth16_pair.hpp -- the pairing side of sylow_hip_groth16_verify_batch.  Compiled as the tail of plk_multi.hip: it reuses that unit's
-// line tables (k_pair_lines, line_get), its slicing under sylow_hip_set_scratch_limit, miller_product_tree and k_final_exp_jobs.
+// line tables (k_pair_lines, line_get), its sliced table lease (lease_table_slices: multi_plan.hpp's slice_jobs under
+// sylow_hip_set_scratch_limit), miller_product_tree and k_final_exp_jobs.  Which route a batch takes: multi_plan.hpp, groth16_tables.
 //
 // Proof i passes iff  e(A_i, B_i) e(-alpha, beta) e(-vk_x_i, gamma) e(-C_i, delta) == 1  (the EVM form with every pair negated).
 //   PER CALL:  the line table of gamma and delta -- k_pair_lines on the "point" P = (1, 1), i.e. the lines before their scaling by a G1
@@ -153,14 +154,13 @@ extern "C" int32_t sylow_hip_groth16_verify_batch(const uint64_t* vk_alpha, cons
   uint8_t* vkx_inf = (uint8_t*)(vkx + 8 * n);
   rc = sylow_hip_groth16_vk_x_batch(vk_ic, n_inputs, inputs, n, vkx, vkx_inf, stream);
   if (rc != SYLOW_HIP_OK) return host::finish(rc, wx);
-  const size_t per_job = table_bytes_per_job(1);
-  const bool tables = !single_job_route(n, 4 * n, 1) && multi_tables_mode() != 0 && per_job * (n < 1024 ? n : 1024) <= table_budget();
-  if (!tables) {
+  const mp::Knobs knobs = knobs_now();
+  if (!mp::groth16_tables(knobs, n)) {
     rc = groth16_verify_composed(vk_alpha, vk_beta, vk_gamma, vk_delta, a_xy, a_inf, b_xy, b_inf, c_xy, c_inf, vkx, vkx_inf, n, ok, stream);
     return host::finish(rc, wx);
   }
   // per call: operands, the gamma / delta line table, e(-alpha, beta)
-  constexpr size_t SHARED_BYTES = (size_t)plk::LT_LINES * 2 * plk::LT_CHUNKS * 2 * sizeof(plk::u32x4);
+  constexpr size_t SHARED_BYTES = mp::table_bytes_per_job(2);       // one job of two slots: gamma, delta
   host::Lease wv, wab, ws;
   rc = wv.acquire(SHARED_BYTES + (16 + 32 + 2 + 8 + 16) * sizeof(u64), st);
   if (rc != SYLOW_HIP_OK) return host::finish(rc, wx);
@@ -168,22 +168,13 @@ extern "C" int32_t sylow_hip_groth16_verify_batch(const uint64_t* vk_alpha, cons
   u64 *ones = (u64*)((uint8_t*)wv.p + SHARED_BYTES), *gd = ones + 16, *off2 = gd + 32, *nalpha = off2 + 2, *beta = nalpha + 8;
   plk::k_groth16_vk_setup<<<1, 64, 0, st>>>(vk_alpha, vk_beta, vk_gamma, vk_delta, ones, gd, off2, nalpha, beta);
   plk::k_pair_lines<true><<<1, 64, 0, st>>>(ones, nullptr, gd, nullptr, off2, 0, 1, 2, 2, 1, shared);
-  u64* fab = nullptr;
-  rc = miller_product_tree(nalpha, nullptr, beta, nullptr, 1, 1, wab, &fab, stream);
+  const u64* fab = nullptr;
+  rc = miller_product_tree(knobs, nalpha, nullptr, beta, nullptr, 1, 1, wab, &fab, stream);
   if (rc != SYLOW_HIP_OK) return host::finish(rc, wab, wv, wx);
-  // per proof, in slices of whole rounds under the table budget (multi_pairing_tables' rule with one slot per job)
-  constexpr size_t ROUND = 65536;
-  const size_t budget = table_budget(), rounds = budget / (per_job * ROUND);
-  size_t slice = rounds >= 1 ? rounds * ROUND : (budget / per_job) & ~(size_t)1023;
-  if (slice < 1024) slice = 1024;
-  size_t jb_max = n < slice ? n : slice;
-  const size_t w_off = ((n + 2) & ~(size_t)1) * sizeof(u64);
-  rc = ws.acquire(per_job * jb_max + 48 * jb_max * sizeof(u64) + w_off, st);
-  if (rc != SYLOW_HIP_OK && jb_max > ROUND) {
-    (void)hipGetLastError();
-    jb_max = ROUND;
-    rc = ws.acquire(per_job * jb_max + 48 * jb_max * sizeof(u64) + w_off, st);
-  }
+  // per proof, in slices under the table budget: one slot per job, and per slice its raw values; the proofs' offsets once
+  const size_t per_job = mp::table_bytes_per_job(1), w_off = ((n + 2) & ~(size_t)1) * sizeof(u64);
+  size_t jb_max = 0;
+  rc = lease_table_slices(ws, knobs.budget, per_job, n, [&](size_t jb) { return 48 * jb * sizeof(u64) + w_off; }, st, &jb_max);
   if (rc != SYLOW_HIP_OK) return host::finish(rc, wab, wv, wx);
   plk::u32x4* table = (plk::u32x4*)ws.p;
   u64 *raw = (u64*)((uint8_t*)ws.p + per_job * jb_max), *off = raw + 48 * jb_max;

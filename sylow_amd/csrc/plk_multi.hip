@@ -1,5 +1,6 @@
 // plk_multi.hip -- glued pairings on lane pairs: one product per job (ecPairing shape), raw glued Miller values, and the
 // batch-wide product (chunked Miller loops + a log-depth tree of Fp12 products + one final exponentiation).
+#include "multi_plan.hpp"
 #include "plk_common.hpp"
 
 #include <atomic>
@@ -11,8 +12,8 @@ namespace plk {
 // one accumulator, a lane pair whose job has fewer pairs multiplies by the unit line.  Pair states live in the stack frame
 // (they are touched once per loop iteration); the accumulator and the working point stay in registers.
 struct PairStateW { G2W r; W2 qx, qy; S2 qxs, qys; F29 px, py; bool qinf, live; };
-constexpr int KMAXW = 4;        // ecPairing / glued jobs (a few pairs each)
-constexpr int KPROD = 8;        // batch-wide product: more pairs per shared squaring
+using multi_plan::KMAXW;        // ecPairing / glued jobs (a few pairs each)
+using multi_plan::KPROD;        // batch-wide product: more pairs per shared squaring
 
 // the raw glued Miller value of this lane pair's job [next, hi), any number of pairs.
 // Out of line ON PURPOSE: the stack frame of a kernel is its own frame plus the deepest callee chain, so with the Miller part
@@ -267,8 +268,9 @@ __global__ void HEAVY_BOUNDS k_multi_pairing(const u64* pxy, const uint8_t* pinf
 // [line][slot][chunk][thread]: a wavefront writes / reads 1 KB contiguous per instruction.  19.5 KB per pair, written once and read
 // once: 0.5 - 1 TB/s while these issue-bound kernels run, HBM the path otherwise leaves idle.
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));      // a native vector: loads keep their address space
-constexpr int LT_CHUNKS = 7;
-constexpr int LT_LINES = 87;
+using multi_plan::LT_CHUNKS;
+using multi_plan::LT_LINES;
+static_assert(2 * sizeof(u32x4) == multi_plan::CHUNK_PAIR_BYTES, "a chunk is 16 bytes per lane");
 struct LineW { W2 l0, l4, l2; };
 BN_DEV void line_put(u32x4* at, size_t stride, const LineW& L) {
   const i32 w[28] = {L.l0.c.v[0], L.l0.c.v[1], L.l0.c.v[2], L.l0.c.v[3], L.l0.c.v[4], L.l0.c.v[5], L.l0.c.v[6], L.l0.c.v[7], L.l0.c.v[8],
@@ -825,10 +827,7 @@ __global__ void __launch_bounds__(BLOCK) k_evm_pair_finalize(const uint8_t* pst,
   result[j] = st ? 0 : is_one[j];
 }
 
-// Jobs of two or more pairs on average: lines to HBM, then the table-driven loop, then the final exponentiations (see k_pair_lines).
-// Job batches share one leased workspace, reused in stream order: 19.5 KB per slot and job, batches of whole GPU rounds (2^16 lane
-// pairs) up to TBL_BYTES.  SYLOW_HIP_OPT_MULTI_TABLES = 0 / 1 forces the in-register / the table route for every job size (A/B runs).
-static int multi_tables_mode() { return (int)host::option(SYLOW_HIP_OPT_MULTI_TABLES); }
+namespace mp = multi_plan;      // every routing and slicing decision below is taken there
 // Bytes the line tables of one call may take: the host's bound (sylow_hip_set_scratch_limit), or by default a quarter of the device memory
 // that was FREE when this device's first multi-pair call arrived, at most 12 GB (an empty MI355X: 12 GB, nine rounds of two-slot jobs; a GPU
 // that is shared and mostly full: proportionally less -- never a constant that ignores the other tenants).  hipMemGetInfo is asked once per
@@ -850,21 +849,9 @@ static size_t table_budget() {
   }
   return v;
 }
-// bytes of line tables one job of kt slots takes (k_pair_lines' layout)
-static size_t table_bytes_per_job(size_t kt) { return (size_t)plk::LT_LINES * kt * plk::LT_CHUNKS * 2 * sizeof(plk::u32x4); }
-static size_t table_slots(size_t n_jobs, size_t n_pairs) {       // slots per job: the batch average, rounded up, 1..8; longer jobs take the in-register tail
-  size_t kt = n_jobs ? (n_pairs + n_jobs - 1) / n_jobs : 1;
-  return kt < 1 ? 1 : kt > 8 ? 8 : kt;
-}
-// The table route slices a batch into blocks of at least 1024 jobs: a budget below 1024 jobs' tables (20 - 160 MB by the job size) cannot be
-// honoured by it, so such a batch takes the in-register schedule (no table at all) -- the bound a host sets is never silently exceeded.
-static bool use_tables(size_t n_jobs, size_t n_pairs) {
-  const int m = multi_tables_mode();
-  if (m == 0) return false;
-  if (m != 1 && n_pairs < 2 * n_jobs) return false;
-  if (!n_pairs) return false;
-  const size_t need = table_bytes_per_job(table_slots(n_jobs, n_pairs)) * (n_jobs < 1024 ? n_jobs : 1024);
-  return need <= table_budget();
+// the knobs in force, read once per entry-point call.  SYLOW_HIP_OPT_MULTI_TABLES = 0 / 1 forces the in-register / the table route (A/B runs)
+static mp::Knobs knobs_now() {
+  return mp::Knobs{(int)host::option(SYLOW_HIP_OPT_MULTI_TABLES), table_budget(), plkh::wide_batch_max(), plkh::small_routes_on()};
 }
 // SYLOW_HIP_OPT_WIDE_PACK = t: the small-batch kernels put two elements on a wavefront above t elements (0 = never, 1 = always: A/B runs and
 // tests/test_gpu_routes.py).  Default: the number of compute units -- one wavefront per CU is the fastest shape (1.72 ms per pairing up
@@ -967,51 +954,148 @@ int32_t verify_two_pairings_wide_batch(const uint64_t* pk_xy, const uint8_t* pk_
   LAUNCHED();
 }
 }  // namespace plkh
-static bool single_job_route(size_t n_jobs, size_t n_pairs, int32_t skip_infinity);
-static int32_t single_job_product(const uint64_t* p_xy, const uint8_t* p_inf, const uint64_t* q_xy, const uint8_t* q_inf, const uint64_t* pair_offsets,
-                                  size_t n_jobs, size_t n_pairs, uint64_t* gt_out, uint8_t* is_one, void* stream);
-static int32_t multi_pairing_tables(const uint64_t* p_xy, const uint8_t* p_inf, const uint64_t* q_xy, const uint8_t* q_inf, const uint64_t* pair_offsets,
-                                    size_t n_jobs, size_t n_pairs, int32_t skip_infinity, uint64_t* gt_out, uint8_t* is_one, int raw_miller, int iso, void* stream) {
-  // iso: the line tables may be built on the isomorphic curves (k_pair_lines<true>) -- whenever the value ends in a final exponentiation, here or
-  // in the caller; 0 only where the reference's raw Miller value itself is the result (glued_miller_loop_batch)
-  hipStream_t st = (hipStream_t)stream;
-  const size_t kt = table_slots(n_jobs, n_pairs);
-  constexpr size_t ROUND = 65536;
-  const size_t TBL_BYTES = table_budget();
-  const size_t per_job = table_bytes_per_job(kt);
-  const size_t rounds = TBL_BYTES / (per_job * ROUND);
-  // whole rounds of the GPU's 2^16 resident lane pairs while the budget allows; under a host-set limit below one round
-  // (sylow_hip_set_scratch_limit) as many jobs as fit, in blocks of 1024 -- phase B / C then run under-filled, the price of the bound
-  size_t slice = rounds >= 1 ? rounds * ROUND : (TBL_BYTES / per_job) & ~(size_t)1023;
-  if (slice < 1024) slice = 1024;
-  size_t jb_max = n_jobs < slice ? n_jobs : slice;
-  size_t w_raw = raw_miller ? 0 : 48 * jb_max * sizeof(u64);
-  host::Lease ws;
-  int32_t rc = ws.acquire(per_job * jb_max + w_raw, st);
-  if (rc != SYLOW_HIP_OK && jb_max > ROUND) {                  // a device short of memory: one round per batch
+// One batch of jobs on its way to a schedule: the pairs, the jobs' pair ranges (device), the outputs, and how a value ends.  raw_miller: the
+// glued Miller value itself, SoA stride n_jobs in gt_out.  iso: the line tables may be built on the isomorphic curves (k_pair_lines<true>) --
+// whenever the value ends in a final exponentiation, here or in the caller; 0 only where the reference's raw Miller value itself is the
+// result (glued_miller_loop_batch)
+struct JobBatch {
+  const u64* p_xy; const uint8_t* p_inf; const u64* q_xy; const uint8_t* q_inf; const u64* offsets;
+  size_t n_jobs, n_pairs;
+  int32_t skip_infinity;
+  u64* gt_out; uint8_t* is_one;
+  int raw_miller, iso;
+};
+static int32_t launch_jobs(mp::Route route, const mp::Knobs& knobs, const JobBatch& b, void* stream);
+// The workspace of a table route that runs n_jobs jobs in slices: per_job bytes of line tables and extra(jb) more bytes for a slice of jb jobs
+// (mp::slice_jobs under the budget).  A device short of memory gets one round per slice.  What a failure means is the caller's business.
+template <class Extra>
+static int32_t lease_table_slices(host::Lease& ws, size_t budget, size_t per_job, size_t n_jobs, Extra extra, hipStream_t st, size_t* jb_max) {
+  size_t jb = mp::slice_jobs(budget, per_job, n_jobs);
+  int32_t rc = ws.acquire(per_job * jb + extra(jb), st);
+  if (rc != SYLOW_HIP_OK && mp::slice_retry(jb)) {
     (void)hipGetLastError();
-    jb_max = ROUND;
-    w_raw = raw_miller ? 0 : 48 * jb_max * sizeof(u64);
-    rc = ws.acquire(per_job * jb_max + w_raw, st);
+    jb = mp::slice_retry(jb);
+    rc = ws.acquire(per_job * jb + extra(jb), st);
   }
-  if (rc != SYLOW_HIP_OK) {                                    // no room for a table at all: the in-register schedule needs no workspace
+  *jb_max = jb;
+  return rc;
+}
+// Jobs of two or more pairs on average: lines to HBM, then the table-driven loop, then the final exponentiations (see k_pair_lines).
+// Job slices share one leased workspace, reused in stream order: 19.5 KB per slot and job, plus a slice's raw values.
+static int32_t multi_pairing_tables(const mp::Knobs& knobs, const JobBatch& b, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  const size_t kt = mp::table_slots(b.n_jobs, b.n_pairs), per_job = mp::table_bytes_per_job(kt);
+  host::Lease ws;
+  size_t jb_max = 0;
+  int32_t rc = lease_table_slices(ws, knobs.budget, per_job, b.n_jobs, [&](size_t jb) { return b.raw_miller ? (size_t)0 : 48 * jb * sizeof(u64); }, st, &jb_max);
+  if (rc != SYLOW_HIP_OK) {                                    // no room for a table at all
     (void)hipGetLastError();
-    plk::k_multi_pairing<plk::KMAXW><<<GRID(2 * n_jobs)>>>(p_xy, p_inf, q_xy, q_inf, pair_offsets, n_jobs, n_pairs, skip_infinity, gt_out, is_one, raw_miller); LAUNCHED();
+    return launch_jobs(mp::table_fallback(), knobs, b, stream);
   }
   plk::u32x4* table = (plk::u32x4*)ws.p;
   u64* raw = (u64*)((uint8_t*)ws.p + per_job * jb_max);
-  for (size_t job0 = 0; job0 < n_jobs; job0 += jb_max) {
-    const size_t jb = n_jobs - job0 < jb_max ? n_jobs - job0 : jb_max;
-    if (!iso) plk::k_pair_lines<false><<<GRID(2 * kt * jb)>>>(p_xy, p_inf, q_xy, q_inf, pair_offsets, job0, jb, n_pairs, (int)kt, skip_infinity, table);
-    else plk::k_pair_lines<true><<<GRID(2 * kt * jb)>>>(p_xy, p_inf, q_xy, q_inf, pair_offsets, job0, jb, n_pairs, (int)kt, skip_infinity, table);
-    if (raw_miller) {
-      plk::k_glued_from_tables<<<GRID(2 * jb)>>>(table, p_xy, p_inf, q_xy, q_inf, pair_offsets, job0, jb, n_pairs, (int)kt, skip_infinity, gt_out, n_jobs, job0);
+  for (size_t job0 = 0; job0 < b.n_jobs; job0 += jb_max) {
+    const size_t jb = b.n_jobs - job0 < jb_max ? b.n_jobs - job0 : jb_max;
+    if (!b.iso) plk::k_pair_lines<false><<<GRID(2 * kt * jb)>>>(b.p_xy, b.p_inf, b.q_xy, b.q_inf, b.offsets, job0, jb, b.n_pairs, (int)kt, b.skip_infinity, table);
+    else plk::k_pair_lines<true><<<GRID(2 * kt * jb)>>>(b.p_xy, b.p_inf, b.q_xy, b.q_inf, b.offsets, job0, jb, b.n_pairs, (int)kt, b.skip_infinity, table);
+    if (b.raw_miller) {
+      plk::k_glued_from_tables<<<GRID(2 * jb)>>>(table, b.p_xy, b.p_inf, b.q_xy, b.q_inf, b.offsets, job0, jb, b.n_pairs, (int)kt, b.skip_infinity, b.gt_out, b.n_jobs, job0);
     } else {
-      plk::k_glued_from_tables<<<GRID(2 * jb)>>>(table, p_xy, p_inf, q_xy, q_inf, pair_offsets, job0, jb, n_pairs, (int)kt, skip_infinity, raw, jb, 0);
-      plk::k_final_exp_jobs<<<GRID(2 * jb)>>>(raw, jb, job0, jb, n_jobs, gt_out, is_one);
+      plk::k_glued_from_tables<<<GRID(2 * jb)>>>(table, b.p_xy, b.p_inf, b.q_xy, b.q_inf, b.offsets, job0, jb, b.n_pairs, (int)kt, b.skip_infinity, raw, jb, 0);
+      plk::k_final_exp_jobs<<<GRID(2 * jb)>>>(raw, jb, job0, jb, b.n_jobs, b.gt_out, b.is_one);
     }
   }
   return host::finish(SYLOW_HIP_OK, ws);
+}
+// One log-depth tree of Fp12 products over m >= 1 values (SoA stride m): ping-pong k_fp12_tree_level passes while m > BLOCK, then the rest
+// of the tree in one block (k_fp12_tree_tail: in place, the product into the other buffer).  overwrite: `in` is scratch of the caller's
+// and serves as the second ping-pong buffer (s1 is not used).  Otherwise `in` is never written: one out-of-place level first, whatever m
+// is, and the passes alternate between s0 (ceil(m / 2) values) and s1 (ceil(m / 4)).  Returns where the product landed, stride 1.
+static const u64* fp12_tree_reduce(const u64* in, size_t m, bool overwrite, u64* s0, u64* s1, void* stream) {
+  const u64* cur = in;
+  u64 *nxt = s0, *other = overwrite ? (u64*)in : s1;
+  bool own = overwrite;
+  while (m > 1 && (m > (size_t)BLOCK || !own)) {
+    const size_t h = (m + 1) / 2;
+    plk::k_fp12_tree_level<<<GRID(2 * h)>>>(cur, m, nxt, h);
+    cur = nxt; nxt = other; other = (u64*)cur;
+    m = h;
+    own = true;
+  }
+  if (m > 1) {
+    plk::k_fp12_tree_tail<<<1, BLOCK, 0, (hipStream_t)stream>>>((u64*)cur, m, m, nxt);
+    cur = nxt;
+  }
+  return cur;
+}
+// Chunked Miller loops + product tree: leaves ONE raw Miller product (SoA stride 1 = 48 contiguous words) in the leased workspace.
+// n_pairs > 0.  The caller releases the lease after enqueueing whatever consumes *result.
+static int32_t miller_product_tree(const mp::Knobs& knobs, const uint64_t* p_xy, const uint8_t* p_inf, const uint64_t* q_xy, const uint8_t* q_inf, size_t n_pairs,
+                                   int32_t skip_infinity, host::Lease& ws, const u64** result, void* stream, const u64* range = nullptr) {
+  hipStream_t st = (hipStream_t)stream;
+  const size_t chunk = mp::product_chunk(n_pairs), n_jobs = (n_pairs + chunk - 1) / chunk;
+  // workspace: chunk offsets + two ping-pong buffers of Fp12 values
+  const size_t n_off = (n_jobs + 2) & ~(size_t)1, n_a = 48 * n_jobs, n_b = 48 * ((n_jobs + 1) / 2);
+  int32_t rc = ws.acquire((n_off + n_a + n_b) * sizeof(u64), st);
+  if (rc != SYLOW_HIP_OK) return rc;
+  u64 *off = (u64*)ws.p, *bufa = off + n_off, *bufb = bufa + n_a;
+  const mp::Route route = mp::chunk_route(knobs, n_pairs, range != nullptr, skip_infinity != 0);
+  // ONE pair (the collapsed halves of the aggregate verifiers): pure latency on one lane pair -- the whole wavefront takes it
+  if (route == mp::Route::SINGLE_WIDE) {
+    plk::k_miller_single_wide<<<1, 64, 0, st>>>(p_xy, p_inf, q_xy, q_inf, 1, range, bufa);
+    *result = bufa;
+    return SYLOW_HIP_OK;
+  }
+  // FEW pairs (small aggregate verifications, short products): one pair per lane pair would be one Miller loop deep on lone wavefronts
+  // (2.5 ms) -- a wavefront per one or two pairs instead (0.6 ms), then the same product tree over the n_pairs values
+  if (route == mp::Route::WIDE_BATCH) {
+    launch_miller_wide(p_xy, p_inf, q_xy, q_inf, bufa, nullptr, nullptr, nullptr, nullptr, nullptr, n_pairs, st);
+  } else {
+    // chunks as jobs with raw values: lines to HBM + the table-driven loop, or the in-register schedule of KMAXW / KPROD slots
+    plk::k_chunk_offsets<<<GRID(n_jobs + 1)>>>(off, n_jobs, n_pairs, chunk, range);
+    rc = launch_jobs(route, knobs, JobBatch{p_xy, p_inf, q_xy, q_inf, off, n_jobs, n_pairs, skip_infinity, bufa, nullptr, 1, /*iso=*/1}, stream);
+    if (rc != SYLOW_HIP_OK) return rc;
+  }
+  *result = fp12_tree_reduce(bufa, n_jobs, /*overwrite=*/true, bufb, nullptr, stream);
+  return SYLOW_HIP_OK;
+}
+// FEW pairs: one wavefront per Miller loop (raw: 48 n_pairs words), then one wavefront per job for the product of its pairs
+// [offsets[j], offsets[j + 1]) (device) and the final exponentiation
+static void wide_jobs_product(const uint64_t* p_xy, const uint8_t* p_inf, const uint64_t* q_xy, const uint8_t* q_inf, size_t n_pairs, u64* raw,
+                              const u64* offsets, size_t n_jobs, uint64_t* gt_out, uint8_t* is_one, hipStream_t st) {
+  launch_miller_wide(p_xy, p_inf, q_xy, q_inf, raw, nullptr, nullptr, nullptr, nullptr, nullptr, n_pairs, st);
+  plk::k_final_exp_wide_jobs<<<dim3((unsigned)n_jobs), dim3(64), 0, st>>>(raw, n_pairs, offsets, n_jobs, gt_out, is_one);
+}
+// FEW jobs with few pairs (a single ecPairing call, a single Groth16-style check, a handful of them; mp::single_job_route): 1.1 + 1.3 ms of
+// latency whatever the job size, against a whole glued loop and a final exponentiation on one lane pair per job (one job of 4 pairs: 7.9 ms).
+static int32_t single_job_product(const mp::Knobs& knobs, const JobBatch& b, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  host::Lease ws;
+  if (b.n_jobs == 1 && b.n_pairs > 256) {           // one LONG job: a log-depth product tree instead of a chain of products on one wavefront
+    const u64* prod = nullptr;
+    int32_t rc = miller_product_tree(knobs, b.p_xy, b.p_inf, b.q_xy, b.q_inf, b.n_pairs, 1, ws, &prod, stream, b.offsets);
+    if (rc != SYLOW_HIP_OK) return rc;
+    plk::k_final_exp_flag<<<1, 64, 0, st>>>(prod, 1, b.gt_out, b.is_one, knobs.small_routes);
+    return host::finish(SYLOW_HIP_OK, ws);
+  }
+  int32_t rc = ws.acquire(48 * b.n_pairs * sizeof(u64), st);
+  if (rc != SYLOW_HIP_OK) return rc;
+  wide_jobs_product(b.p_xy, b.p_inf, b.q_xy, b.q_inf, b.n_pairs, (u64*)ws.p, b.offsets, b.n_jobs, b.gt_out, b.is_one, st);
+  return host::finish(SYLOW_HIP_OK, ws);
+}
+// The one place a planned route becomes launches.  In-register schedules: chunks of KMAX pairs share the squarings; any KMAX is correct for
+// any job size.  Batches that average at most two pairs per job (the BLS / ecPairing k = 2 shape) take the two-slot instantiation: its
+// pair states are a third of the stack frame
+static int32_t launch_jobs(mp::Route route, const mp::Knobs& knobs, const JobBatch& b, void* stream) {
+  if (route == mp::Route::ONE_WAVE_JOBS) return single_job_product(knobs, b, stream);
+  if (route == mp::Route::TABLES) return multi_pairing_tables(knobs, b, stream);
+  auto slots = [&](auto kmax) {
+    plk::k_multi_pairing<decltype(kmax)::value><<<GRID(2 * b.n_jobs)>>>(b.p_xy, b.p_inf, b.q_xy, b.q_inf, b.offsets, b.n_jobs, b.n_pairs, b.skip_infinity, b.gt_out, b.is_one, b.raw_miller);
+  };
+  if (route == mp::Route::SLOTS_2) slots(std::integral_constant<int, 2>{});
+  else if (route == mp::Route::SLOTS_KPROD) slots(std::integral_constant<int, mp::KPROD>{});
+  else slots(std::integral_constant<int, mp::KMAXW>{});
+  LAUNCHED();
 }
 
 extern "C" {
@@ -1019,12 +1103,9 @@ int32_t sylow_hip_multi_pairing_batch(const uint64_t* p_xy, const uint8_t* p_inf
                                       const uint64_t* pair_offsets, size_t n_jobs, size_t n_pairs, int32_t skip_infinity,
                                       uint64_t* gt_out, uint8_t* is_one, void* stream) {
   ARGCHK(pair_offsets && (gt_out || is_one) && (n_pairs == 0 || (p_xy && q_xy))); if (!n_jobs) return SYLOW_HIP_OK;
-  if (single_job_route(n_jobs, n_pairs, skip_infinity)) return single_job_product(p_xy, p_inf, q_xy, q_inf, pair_offsets, n_jobs, n_pairs, gt_out, is_one, stream);
-  if (use_tables(n_jobs, n_pairs)) return multi_pairing_tables(p_xy, p_inf, q_xy, q_inf, pair_offsets, n_jobs, n_pairs, skip_infinity, gt_out, is_one, 0, /*iso=*/1, stream);
-  // chunks of KMAX pairs share the squarings; any KMAX is correct for any job size.  Batches that average at most two pairs per
-  // job (the BLS / ecPairing k = 2 shape) take the two-slot instantiation: its pair states are a third of the stack frame
-  if (n_pairs <= 2 * n_jobs) { plk::k_multi_pairing<2><<<GRID(2 * n_jobs)>>>(p_xy, p_inf, q_xy, q_inf, pair_offsets, n_jobs, n_pairs, skip_infinity, gt_out, is_one, 0); LAUNCHED(); }
-  plk::k_multi_pairing<plk::KMAXW><<<GRID(2 * n_jobs)>>>(p_xy, p_inf, q_xy, q_inf, pair_offsets, n_jobs, n_pairs, skip_infinity, gt_out, is_one, 0); LAUNCHED();
+  const mp::Knobs knobs = knobs_now();
+  return launch_jobs(mp::job_route(knobs, n_jobs, n_pairs, skip_infinity != 0, /*raw_glued=*/false), knobs,
+                     JobBatch{p_xy, p_inf, q_xy, q_inf, pair_offsets, n_jobs, n_pairs, skip_infinity, gt_out, is_one, 0, /*iso=*/1}, stream);
 }
 int32_t sylow_hip_g2_precompute_batch(const uint64_t* q_xy, uint64_t* coeffs, size_t n, void* stream) {
   ARGCHK(q_xy && coeffs); if (!n) return SYLOW_HIP_OK;
@@ -1033,8 +1114,9 @@ int32_t sylow_hip_g2_precompute_batch(const uint64_t* q_xy, uint64_t* coeffs, si
 int32_t sylow_hip_glued_miller_loop_batch(const uint64_t* p_xy, const uint64_t* q_xy, const uint64_t* pair_offsets, size_t n_jobs, size_t n_pairs,
                                            uint64_t* f_out, void* stream) {
   ARGCHK(pair_offsets && f_out && (n_pairs == 0 || (p_xy && q_xy))); if (!n_jobs) return SYLOW_HIP_OK;
-  if (use_tables(n_jobs, n_pairs)) return multi_pairing_tables(p_xy, nullptr, q_xy, nullptr, pair_offsets, n_jobs, n_pairs, 0, f_out, nullptr, 1, /*iso=*/0, stream);
-  plk::k_multi_pairing<plk::KMAXW><<<GRID(2 * n_jobs)>>>(p_xy, nullptr, q_xy, nullptr, pair_offsets, n_jobs, n_pairs, 0, f_out, nullptr, 1); LAUNCHED();
+  const mp::Knobs knobs = knobs_now();
+  return launch_jobs(mp::job_route(knobs, n_jobs, n_pairs, false, /*raw_glued=*/true), knobs,
+                     JobBatch{p_xy, nullptr, q_xy, nullptr, pair_offsets, n_jobs, n_pairs, 0, f_out, nullptr, 1, /*iso=*/0}, stream);
 }
 
 int32_t sylow_hip_miller_loop_precomputed_batch(const uint64_t* coeffs, size_t n_tables, const uint64_t* table_idx, const uint64_t* p_xy,
@@ -1048,104 +1130,26 @@ int32_t sylow_hip_glued_miller_loop_precomputed_batch(const uint64_t* coeffs, si
   plk::k_miller_precomputed<<<GRID(2 * n_jobs)>>>(coeffs, n_tables, table_idx, p_xy, n_pairs, pair_offsets, n_jobs, f_out); LAUNCHED();
 }
 
-// Chunked Miller loops + product tree: leaves ONE raw Miller product (SoA stride 1 = 48 contiguous words) in the leased workspace.
-// n_pairs > 0.  The caller releases the lease after enqueueing whatever consumes *result.
-static int32_t miller_product_tree(const uint64_t* p_xy, const uint8_t* p_inf, const uint64_t* q_xy, const uint8_t* q_inf, size_t n_pairs,
-                                   int32_t skip_infinity, host::Lease& ws, u64** result, void* stream, const u64* range = nullptr) {
-  hipStream_t st = (hipStream_t)stream;
-  // pairs per lane pair: as few as keep the whole product inside ONE round of the GPU (2^16 lane pairs resident), at most KPROD --
-  // a small product is latency-bound (one pair per lane pair on the single-pair loop: one Miller loop deep), a large one
-  // throughput-bound (shared squarings)
-  size_t chunk = (n_pairs + 65535) / 65536;
-  if (chunk > (size_t)plk::KPROD) chunk = plk::KPROD;
-  const size_t n_jobs = (n_pairs + chunk - 1) / chunk;
-  // workspace: chunk offsets + two ping-pong buffers of Fp12 values
-  const size_t n_off = (n_jobs + 2) & ~(size_t)1, n_a = 48 * n_jobs, n_b = 48 * ((n_jobs + 1) / 2);
-  int32_t rc = ws.acquire((n_off + n_a + n_b) * sizeof(u64), st);
-  if (rc != SYLOW_HIP_OK) return rc;
-  u64 *off = (u64*)ws.p, *bufa = off + n_off, *bufb = bufa + n_a;
-  // ONE pair (the collapsed halves of the aggregate verifiers): pure latency on one lane pair -- the whole wavefront takes it
-  if (n_pairs == 1 && skip_infinity && plkh::small_routes_on()) {
-    plk::k_miller_single_wide<<<1, 64, 0, st>>>(p_xy, p_inf, q_xy, q_inf, 1, range, bufa);
-    *result = bufa;
-    return SYLOW_HIP_OK;
-  }
-  // FEW pairs (small aggregate verifications, short products): one pair per lane pair would be one Miller loop deep on lone wavefronts
-  // (2.5 ms) -- a wavefront per one or two pairs instead (0.6 ms), then the same product tree over the n_pairs values
-  if (chunk == 1 && !range && skip_infinity && n_pairs <= plkh::wide_batch_max()) {
-    launch_miller_wide(p_xy, p_inf, q_xy, q_inf, bufa, nullptr, nullptr, nullptr, nullptr, nullptr, n_pairs, st);
-  } else {
-  plk::k_chunk_offsets<<<GRID(n_jobs + 1)>>>(off, n_jobs, n_pairs, chunk, range);
-  // chunks of two or more pairs: lines to HBM + the table-driven loop (SYLOW_HIP_OPT_MULTI_TABLES = 0: the in-register KPROD-slot schedule)
-  const size_t round_table = (size_t)65536 * chunk * plk::LT_LINES * plk::LT_CHUNKS * 2 * sizeof(plk::u32x4);     // one round of chunk-slot jobs
-  if (chunk >= 2 && multi_tables_mode() != 0 && (round_table <= table_budget() || multi_tables_mode() == 1)) {
-    rc = multi_pairing_tables(p_xy, p_inf, q_xy, q_inf, off, n_jobs, n_pairs, skip_infinity, bufa, nullptr, 1, /*iso=*/1, stream);
-    if (rc != SYLOW_HIP_OK) return rc;
-  }
-  else if (chunk <= 2) plk::k_multi_pairing<plk::KMAXW><<<GRID(2 * n_jobs)>>>(p_xy, p_inf, q_xy, q_inf, off, n_jobs, n_pairs, skip_infinity, bufa, nullptr, 1);
-  else plk::k_multi_pairing<plk::KPROD><<<GRID(2 * n_jobs)>>>(p_xy, p_inf, q_xy, q_inf, off, n_jobs, n_pairs, skip_infinity, bufa, nullptr, 1);
-  }
-  u64 *cur = bufa, *nxt = bufb;
-  size_t m = n_jobs;
-  while (m > (size_t)BLOCK) {
-    const size_t h = (m + 1) / 2;
-    plk::k_fp12_tree_level<<<GRID(2 * h)>>>(cur, m, nxt, h);
-    u64* tmp = cur; cur = nxt; nxt = tmp;
-    m = h;
-  }
-  if (m > 1) {                                     // the rest of the tree in one block; the product lands in the other buffer, stride 1
-    plk::k_fp12_tree_tail<<<1, BLOCK, 0, st>>>(cur, m, m, nxt);
-    cur = nxt;
-  }
-  *result = cur;
-  return SYLOW_HIP_OK;
-}
-// FEW jobs with few pairs (a single ecPairing call, a single Groth16-style check, a handful of them): one wavefront per pair for the
-// Miller loops, one per job for the product of its pairs and the final exponentiation -- 1.1 + 1.3 ms of latency whatever the job size,
-// against a whole glued loop and a final exponentiation on one lane pair per job (one job of 4 pairs: 7.9 ms).  The jobs' pair ranges
-// stay on the device.  EIP-197 reading of identities only (skip_infinity).
-static bool single_job_route(size_t n_jobs, size_t n_pairs, int32_t skip_infinity) {
-  const size_t cap = plkh::wide_batch_max();
-  return cap != 0 && n_pairs >= 1 && n_pairs <= cap && n_jobs <= 1024 && skip_infinity;
-}
-static int32_t single_job_product(const uint64_t* p_xy, const uint8_t* p_inf, const uint64_t* q_xy, const uint8_t* q_inf, const uint64_t* pair_offsets,
-                                  size_t n_jobs, size_t n_pairs, uint64_t* gt_out, uint8_t* is_one, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
-  host::Lease ws;
-  if (n_jobs == 1 && n_pairs > 256) {               // one LONG job: a log-depth product tree instead of a chain of products on one wavefront
-    u64* prod = nullptr;
-    int32_t rc = miller_product_tree(p_xy, p_inf, q_xy, q_inf, n_pairs, 1, ws, &prod, stream, pair_offsets);
-    if (rc != SYLOW_HIP_OK) return rc;
-    plk::k_final_exp_flag<<<1, 64, 0, st>>>(prod, 1, gt_out, is_one, plkh::small_routes_on());
-    return host::finish(SYLOW_HIP_OK, ws);
-  }
-  int32_t rc = ws.acquire(48 * n_pairs * sizeof(u64), st);
-  if (rc != SYLOW_HIP_OK) return rc;
-  u64* raw = (u64*)ws.p;
-  launch_miller_wide(p_xy, p_inf, q_xy, q_inf, raw, nullptr, nullptr, nullptr, nullptr, nullptr, n_pairs, st);
-  plk::k_final_exp_wide_jobs<<<dim3((unsigned)n_jobs), dim3(64), 0, st>>>(raw, n_pairs, pair_offsets, n_jobs, gt_out, is_one);
-  return host::finish(SYLOW_HIP_OK, ws);
-}
 int32_t sylow_hip_pairing_product_batch(const uint64_t* p_xy, const uint8_t* p_inf, const uint64_t* q_xy, const uint8_t* q_inf,
                                         size_t n_pairs, int32_t skip_infinity, uint64_t* gt_out, uint8_t* is_one, void* stream) {
   ARGCHK((gt_out || is_one) && (n_pairs == 0 || (p_xy && q_xy)));
   hipStream_t st = (hipStream_t)stream;
-  if (n_pairs == 0) { plk::k_final_exp_flag<<<1, 64, 0, st>>>(nullptr, 0, gt_out, is_one, plkh::small_routes_on()); LAUNCHED(); }
+  const mp::Knobs knobs = knobs_now();
+  if (n_pairs == 0) { plk::k_final_exp_flag<<<1, 64, 0, st>>>(nullptr, 0, gt_out, is_one, knobs.small_routes); LAUNCHED(); }
   host::Lease ws;
-  if (n_pairs >= 2 && n_pairs <= 256 && skip_infinity && plkh::small_routes_on()) {
+  if (n_pairs >= 2 && n_pairs <= 256 && skip_infinity && knobs.small_routes) {
     // a short product: one wavefront per Miller loop, then one wavefront multiplies the values and exponentiates (2.0 - 3.0 ms against 3.3)
     int32_t rc = ws.acquire((48 * n_pairs + 2) * sizeof(u64), st);
     if (rc != SYLOW_HIP_OK) return rc;
     u64 *off = (u64*)ws.p, *raw = off + 2;
     plk::k_chunk_offsets<<<1, 64, 0, st>>>(off, 1, n_pairs, n_pairs, nullptr);
-    launch_miller_wide(p_xy, p_inf, q_xy, q_inf, raw, nullptr, nullptr, nullptr, nullptr, nullptr, n_pairs, st);
-    plk::k_final_exp_wide_jobs<<<1, 64, 0, st>>>(raw, n_pairs, off, 1, gt_out, is_one);
+    wide_jobs_product(p_xy, p_inf, q_xy, q_inf, n_pairs, raw, off, 1, gt_out, is_one, st);
     return host::finish(SYLOW_HIP_OK, ws);
   }
-  u64* prod = nullptr;
-  int32_t rc = miller_product_tree(p_xy, p_inf, q_xy, q_inf, n_pairs, skip_infinity, ws, &prod, stream);
+  const u64* prod = nullptr;
+  int32_t rc = miller_product_tree(knobs, p_xy, p_inf, q_xy, q_inf, n_pairs, skip_infinity, ws, &prod, stream);
   if (rc != SYLOW_HIP_OK) return rc;
-  plk::k_final_exp_flag<<<1, 64, 0, st>>>(prod, 1, gt_out, is_one, plkh::small_routes_on());
+  plk::k_final_exp_flag<<<1, 64, 0, st>>>(prod, 1, gt_out, is_one, knobs.small_routes);
   return host::finish(SYLOW_HIP_OK, ws);
 }
 int32_t sylow_hip_pairing_product_partial_batch(const uint64_t* p_xy, const uint8_t* p_inf, const uint64_t* q_xy, const uint8_t* q_inf,
@@ -1154,8 +1158,8 @@ int32_t sylow_hip_pairing_product_partial_batch(const uint64_t* p_xy, const uint
   hipStream_t st = (hipStream_t)stream;
   if (n_pairs == 0) { plk::k_fp12_set_one<<<1, 64, 0, st>>>(f_out); LAUNCHED(); }
   host::Lease ws;
-  u64* prod = nullptr;
-  int32_t rc = miller_product_tree(p_xy, p_inf, q_xy, q_inf, n_pairs, skip_infinity, ws, &prod, stream);
+  const u64* prod = nullptr;
+  int32_t rc = miller_product_tree(knobs_now(), p_xy, p_inf, q_xy, q_inf, n_pairs, skip_infinity, ws, &prod, stream);
   if (rc != SYLOW_HIP_OK) return rc;
   const hipError_t e = hipMemcpyAsync(f_out, prod, 48 * sizeof(u64), hipMemcpyDeviceToDevice, st);
   return host::finish(e != hipSuccess ? host::fail(e, "hipMemcpyAsync(partial product)") : SYLOW_HIP_OK, ws);
@@ -1168,10 +1172,6 @@ int32_t sylow_hip_pairing_product_partial_batch(const uint64_t* p_xy, const uint
 // `weights` (NULL = none): w_i as Fp values [4][n]; the product becomes prod_i [e(sig_i, G2gen) e(-H(m_i), pk_i)]^(w_i) = e(sum w_i sig_i, G2gen)
 // prod_i e(-w_i H(m_i), pk_i) -- the small-exponent batch test (SURVEY.md e1 "alternative aggregate check"): with weights drawn after
 // the signatures are fixed, a batch that contains an invalid signature passes with probability at most 2^-(bits of the weights).
-// A short-lived side stream for work that does not depend on the long kernels of the caller's stream (here: the sum of the
-// signatures and the one Miller loop it feeds run beside the batch's hashing instead of after it).  open(): the side stream waits for
-// everything the caller's stream holds at this point; join(): the caller's stream waits for the side work.  Any failure to create the
-// stream or its events degrades to the caller's stream (same results, no overlap); SYLOW_HIP_OPT_AGG_FORK = 0 forces that.
 using host::Fork;
 static int32_t aggregate_partial(const uint64_t* pk_xy, const uint8_t* pk_inf, size_t n_pk, const uint8_t* msgs, const uint64_t* msg_offsets,
                                  const uint64_t* sig_xy, const uint8_t* sig_inf, const uint64_t* weights, size_t n, uint64_t* f_out, void* stream) {
@@ -1191,7 +1191,8 @@ static int32_t aggregate_partial(const uint64_t* pk_xy, const uint8_t* pk_inf, s
   u64 *hxy = (u64*)ws.p, *acc = hxy + w_h, *acc2 = acc + (one_key ? w_acc : 0), *sw = acc2 + w_acc, *pa2 = sw + w_sw, *pb2 = pa2 + 8, *qa2 = pb2 + 8, *qb2 = qa2 + 16;
   uint8_t *hinf = (uint8_t*)(qb2 + 16), *p2inf = hinf + n, *q2inf = p2inf + 2, *swinf = q2inf + 2;
   host::Lease wa, wb;
-  u64 *pa = nullptr, *pb = nullptr;
+  const u64 *pa = nullptr, *pb = nullptr;
+  const mp::Knobs knobs = knobs_now();
   // The G2gen half -- e(sum_i sig_i, G2gen), or e(sum_i w_i sig_i, G2gen) with weights: a (scalar multiplication,) summation tree and ONE
   // Miller loop, a few ms of pure latency -- depends on the signatures (and weights) only: it runs on a side stream beside the hashing.
   Fork fork;
@@ -1206,7 +1207,7 @@ static int32_t aggregate_partial(const uint64_t* pk_xy, const uint8_t* pk_inf, s
     if (rc == SYLOW_HIP_OK) rc = g1h::sum(sp, spi, n, acc, pb2, p2inf + 1, 1, 0, 0, sd);
     if (rc == SYLOW_HIP_OK) {
       plk::k_g2_set_column<<<1, 64, 0, sd>>>(qb2, q2inf + 1, 1, 0, nullptr, nullptr);
-      rc = miller_product_tree(pb2, p2inf + 1, qb2, q2inf + 1, 1, 1, wb, &pb, sd);
+      rc = miller_product_tree(knobs, pb2, p2inf + 1, qb2, q2inf + 1, 1, 1, wb, &pb, sd);
     }
   }
   // committees: the key sums depend on the keys only -- a segmented G2 sum on a side stream of its own beside the hashing (behind the
@@ -1234,7 +1235,7 @@ static int32_t aggregate_partial(const uint64_t* pk_xy, const uint8_t* pk_inf, s
     // prod_i e(-[w_i] H_i, apk_i): n pairs
     rc = fork_keys.join(st);
     if (wx.slot >= 0) wx.st = st;      // as wb below
-    if (rc == SYLOW_HIP_OK) rc = miller_product_tree(hxy, hinf, fxy, finf, n, 1, wa, &pa, stream);
+    if (rc == SYLOW_HIP_OK) rc = miller_product_tree(knobs, hxy, hinf, fxy, finf, n, 1, wa, &pa, stream);
   } else if (rc == SYLOW_HIP_OK && key_reuse) {
     // prod_j e(-sum_t [w] H[t n_pk + j], pk_j): n_pk pairs
     const size_t w_fold = g1h::sum_segments_scratch_words(n_pk, n / n_pk);
@@ -1244,17 +1245,17 @@ static int32_t aggregate_partial(const uint64_t* pk_xy, const uint8_t* pk_inf, s
       finf = (uint8_t*)(fxy + 8 * n_pk + w_fold);
       rc = g1h::sum_segments(hxy, hinf, n_pk, n / n_pk, fxy + 8 * n_pk, fxy, finf, stream);
     }
-    if (rc == SYLOW_HIP_OK) rc = miller_product_tree(fxy, finf, pk_xy, pk_inf, n_pk, 1, wa, &pa, stream);
+    if (rc == SYLOW_HIP_OK) rc = miller_product_tree(knobs, fxy, finf, pk_xy, pk_inf, n_pk, 1, wa, &pa, stream);
   } else if (rc == SYLOW_HIP_OK && !one_key) {
     // prod_i e(-H_i, pk_i) over the batch
-    rc = miller_product_tree(hxy, hinf, pk_xy, pk_inf, n, 1, wa, &pa, stream);
+    rc = miller_product_tree(knobs, hxy, hinf, pk_xy, pk_inf, n, 1, wa, &pa, stream);
   } else if (rc == SYLOW_HIP_OK) {
     // one key: the other half collapses too -- e(-sum H, pk), one more single-pair loop
     rc = hash_into_tree ? g1h::sum_tree(acc2, n, pa2, p2inf, 1, 0, /*negate=*/1, stream)
                         : g1h::sum(hxy, hinf, n, acc2, pa2, p2inf, 1, 0, /*negate=*/1, stream);
     if (rc == SYLOW_HIP_OK) {
       plk::k_g2_set_column<<<1, 64, 0, st>>>(qa2, q2inf, 1, 0, pk_xy, pk_inf);
-      rc = miller_product_tree(pa2, p2inf, qa2, q2inf, 1, 1, wa, &pa, stream);
+      rc = miller_product_tree(knobs, pa2, p2inf, qa2, q2inf, 1, 1, wa, &pa, stream);
     }
   }
   const int32_t joined = fork.join(st);
@@ -1280,22 +1281,9 @@ int32_t sylow_hip_fp12_product_final_exp(const uint64_t* parts, size_t k, uint64
   const size_t n_a = 48 * ((k + 1) / 2), n_b = 48 * ((k + 3) / 4);
   int32_t rc = ws.acquire((n_a + n_b) * sizeof(u64), st);
   if (rc != SYLOW_HIP_OK) return rc;
-  const u64* cur = parts;
-  u64 *nxt = (u64*)ws.p, *other = nxt + n_a;
-  size_t m = k;
-  bool own = false;                                 // the caller's array is never multiplied in place: one out-of-place level first
-  while (m > 1 && (m > (size_t)BLOCK || !own)) {
-    const size_t h = (m + 1) / 2;
-    plk::k_fp12_tree_level<<<GRID(2 * h)>>>(cur, m, nxt, h);
-    cur = nxt; u64* tmp = nxt; nxt = other; other = tmp;
-    m = h;
-    own = true;
-  }
-  if (m > 1) {
-    plk::k_fp12_tree_tail<<<1, BLOCK, 0, st>>>((u64*)cur, m, m, nxt);
-    cur = nxt;
-  }
-  plk::k_final_exp_flag<<<1, 64, 0, st>>>(cur, 1, gt_out, is_one, plkh::small_routes_on());
+  // the caller's array is never multiplied in place
+  const u64* prod = fp12_tree_reduce(parts, k, /*overwrite=*/false, (u64*)ws.p, (u64*)ws.p + n_a, stream);
+  plk::k_final_exp_flag<<<1, 64, 0, st>>>(prod, 1, gt_out, is_one, plkh::small_routes_on());
   return host::finish(SYLOW_HIP_OK, ws);
 }
 
@@ -1318,10 +1306,9 @@ int32_t sylow_hip_evm_ecpairing_batch(const uint8_t* in, const uint64_t* pair_of
   uint8_t* isone = pst + np;
   if (n_pairs) rc = plkh::evm_decode_pairs(in, n_pairs, pxy, pinf, qxy, qinf, pst, stream);
   if (rc == SYLOW_HIP_OK) {
-    if (single_job_route(n_jobs, n_pairs, 1)) rc = single_job_product(pxy, pinf, qxy, qinf, pair_offsets, n_jobs, n_pairs, nullptr, isone, stream);
-    else if (use_tables(n_jobs, n_pairs)) rc = multi_pairing_tables(pxy, pinf, qxy, qinf, pair_offsets, n_jobs, n_pairs, /*skip_infinity=*/1, nullptr, isone, 0, /*iso=*/1, stream);
-    else if (n_pairs <= 2 * n_jobs) plk::k_multi_pairing<2><<<GRID(2 * n_jobs)>>>(pxy, pinf, qxy, qinf, pair_offsets, n_jobs, n_pairs, /*skip_infinity=*/1, nullptr, isone, 0);
-    else plk::k_multi_pairing<plk::KMAXW><<<GRID(2 * n_jobs)>>>(pxy, pinf, qxy, qinf, pair_offsets, n_jobs, n_pairs, /*skip_infinity=*/1, nullptr, isone, 0);
+    const mp::Knobs knobs = knobs_now();
+    rc = launch_jobs(mp::job_route(knobs, n_jobs, n_pairs, /*skip_infinity=*/true, /*raw_glued=*/false), knobs,
+                     JobBatch{pxy, pinf, qxy, qinf, pair_offsets, n_jobs, n_pairs, /*skip_infinity=*/1, nullptr, isone, 0, /*iso=*/1}, stream);
   }
   if (rc == SYLOW_HIP_OK) k_evm_pair_finalize<<<GRID(n_jobs)>>>(pst, pair_offsets, n_jobs, isone, result, status);
   return host::finish(rc, lease);

@@ -488,7 +488,8 @@ int32_t sylow_hip_trim(size_t keep_bytes) {
   return SYLOW_HIP_OK;
 }
 // Upper bound for the line tables of the multi-pair routes (plk_multi.hip), the one scratch user whose size is not proportional to its
-// input: 0 = the default (12 GB).  Process-wide; read at the start of each call.
+// input: 0 = the default (a quarter of the device memory that is free at the device's first multi-pair call, between 64 MB and 12 GB:
+// plk_multi.hip table_budget).  Process-wide; read at the start of each call.
 int32_t sylow_hip_set_scratch_limit(size_t bytes) { host::g_scratch_limit.store(bytes, std::memory_order_relaxed); return SYLOW_HIP_OK; }
 // Route selectors and thresholds (include/sylow_hip.h): the library reads no environment variable
 int32_t sylow_hip_set_option(int32_t option, int64_t value) {

@@ -52,6 +52,35 @@ def test_sharded_product_equals_glued_pairing(engine, coracle, pairs):
     assert one
 
 
+TREE_SCALARS = [(3, 5), (0x1F2E3D4C5B6A79881122334455667788, 7), (11, R.R_ORDER - 2), (R.R_ORDER - 1, 0x0123456789ABCDEF0FEDCBA987654321)]
+
+
+@pytest.fixture(scope="module")
+def tree_parts(engine):
+    """the raw Miller values of the four single pairs (a_j G1, b_j G2): [4, 48]"""
+    p, _ = engine.g1_scalar_mul(np.repeat(pack(G1, 8), 4, 0), limbs([a for a, _ in TREE_SCALARS]))
+    q, _ = engine.g2_scalar_mul(np.repeat(pack(G2, 16), 4, 0), limbs([b for _, b in TREE_SCALARS]))
+    return np.concatenate([engine.pairing_product_partial(p[j:j + 1], q[j:j + 1]) for j in range(4)], axis=0)
+
+
+@pytest.mark.parametrize("k", [2, 3, 256, 257, 513])
+def test_fp12_product_final_exp_tree_sizes(engine, coracle, tree_parts, k):
+    """sylow_hip_fp12_product_final_exp over k parts on every branch of the tree reduction: one out-of-place level alone (2), an odd
+    level and the one-block tail (3), a full block after the first level (256 -> 128), the odd tail copied at the top (257), two levels
+    before the tail (513 -> 257 -> 129).  Parts: the four single-pair values repeated cyclically.  Expected: by bilinearity the
+    oracle's ONE pairing e(s G1, G2), s = sum of a_j b_j with multiplicity mod r.  The caller's array is left bit-identical."""
+    parts = tree_parts[np.arange(k) % 4]
+    d_parts = engine.to_device_soa(parts, 48)                            # the C entry point on a device array of the test's own
+    d_gt, d_one = engine.empty((48, 1)), engine.empty((1,), np.uint8)
+    engine._call("sylow_hip_fp12_product_final_exp", d_parts.ptr, k, d_gt.ptr, d_one.ptr)
+    gt, one = engine.from_device_soa(d_gt), bool(d_one.download()[0])
+    assert np.array_equal(engine.from_device_soa(d_parts), parts)
+    s = sum(a * b * len(range(j, k, 4)) for j, (a, b) in enumerate(TREE_SCALARS)) % R.R_ORDER
+    sg, _ = coracle.g1_to_affine(coracle.g1_scalar_mul(proj1(pack(G1, 8)), limbs([s])))
+    exp = coracle.pairing(proj1(sg), proj2(pack(G2, 16)))
+    assert np.array_equal(gt.reshape(-1), exp[0]) and not one
+
+
 def test_all_valid_and_product_all_single_rank(engine, pairs):
     p, q = pairs
     flags = engine.to_device(np.ones(1000, dtype=np.uint8))

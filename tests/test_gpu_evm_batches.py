@@ -189,7 +189,7 @@ def _two_slot_batch(pool, pair_sets):
 
 
 def test_ecpairing_pool_single_job_route(engine, pool, exp, pair_sets):
-    """the pool as it is.  Route: single_job_product (plk_multi.hip single_job_route: 1 <= n_pairs <= 6144 and n_jobs <= 1024) -- one
+    """the pool as it is.  Route: single_job_product (multi_plan.hpp single_job_route: 1 <= n_pairs <= 6144 and n_jobs <= 1024) -- one
     wavefront per pair, one per job for the product and the final exponentiation"""
     n, k = shape(pool.pair, pair_sets["dev"])
     assert n <= 1024 and 1 <= k <= 6144, (n, k)
