@@ -778,6 +778,47 @@ int32_t sylow_hip_kzg_batch_verify_weighted(const uint64_t* tau_g2_xy, const uin
                                             const uint64_t* pi_xy, const uint8_t* pi_inf, const uint64_t* weights, size_t n,
                                             uint64_t* gt_out, uint8_t* is_one, void* stream);
 
+/* ---- KZG, the prover's side: commit to and open polynomials under ONE SRS (kzg_prove.hip; geometry and routes in kzg_prove_plan.hpp) ----
+ * The G1 half of the SRS as the prover holds it: srs_g1_xy [8][len], the affine points tau^k G1gen for k = 0 .. len - 1, WITHOUT a flag array.
+ * Conventions of the four calls (those of the KZG block above):
+ *   polynomials: m polynomials of len coefficients each (len >= 1), lowest degree first.  Each is an ordinary Fr SoA array [4][len] and the m
+ *              arrays lie one after another -- coeffs [m][4][len], word w of coefficient k of polynomial j at (j * 4 + w) * len + k -- so that
+ *              polynomial j is, as it lies, an array of len scalars of stride len.  A shorter polynomial is padded with zeros by the caller; a
+ *              host with a longer SRS passes a packed prefix of it (the SoA stride is len).
+ *   scalars:   coefficients and z are ANY 256-bit words, taken mod r (NOT like Fp::new first: a coefficient word >= p is its residue mod r).
+ *   words:     coordinate words >= p are reduced like Fp::new, as everywhere.
+ *   points:    taken as given: no on-curve check, no subgroup check.
+ *   outputs:   q_out [m][4][len] in the layout of coeffs, canonical words below r, q_{len - 1} = 0 written; y [4][m]; points as [8][m] affine +
+ *              [m] flags, the identity as (0, 1) + its flag.
+ *   calls:     stream-ordered, no host synchronisation; scratch leased per call.  len = 0: SYLOW_HIP_E_ARG.  m = 0: OK, nothing launched,
+ *              nothing written.  NULL where a pointer is required: SYLOW_HIP_E_ARG, no launch, nothing written. */
+/* q_j(X) = (f_j(X) - f_j(z_j)) / (X - z_j) and y_j = f_j(z_j): the recurrence h_len = 0, h_k = f_k + z h_{k+1}; y = h_0, q_k = h_{k+1} for
+ * k < len - 1, q_{len-1} = 0.  Exact in Fr.  Either output may be NULL, not both; q_out = NULL is plain polynomial evaluation.  q_out must
+ * NOT overlap coeffs.  A lane owns 8 consecutive coefficients, a block a chunk of 2048; a polynomial of at most one chunk is ONE launch,
+ * a longer one three (chunk totals, one carry level, the chunks again). */
+/* @shape coeffs=u64[4*len*m] z=u64[4*m] q_out=u64[4*len*m]? y_out=u64[4*m]? */
+int32_t sylow_hip_kzg_quotient_batch(const uint64_t* coeffs, size_t len, size_t m, const uint64_t* z,
+                                     uint64_t* q_out, uint64_t* y_out, void* stream);
+/* out_j = sum_k f_jk srs_k: the canonical affine words of one group element, hence identical on every route and for every chunking.
+ * len >= the bucket route's crossover (that of sylow_hip_g1_msm): the coefficients mod r, then one sylow_hip_g1_msm_tuned per polynomial and
+ * one gather.  Shorter: all m len (polynomial, term) pairs through ONE sylow_hip_g1_scalar_mul_batch and a segmented sum, in chunks of
+ * whole polynomials that fit sylow_hip_set_scratch_limit (default 1 GB) at about 1.3 KB per pair; if not even one polynomial fits, each
+ * goes through sylow_hip_g1_msm.  A zero polynomial (coefficients 0 mod r) and a sum that lands on the identity give (0, 1) + the flag. */
+/* @shape srs_g1_xy=u64[8*len] coeffs=u64[4*len*m] out_xy=u64[8*m] out_inf=u8[m] */
+int32_t sylow_hip_kzg_commit_batch(const uint64_t* srs_g1_xy, const uint64_t* coeffs, size_t len, size_t m,
+                                   uint64_t* out_xy, uint8_t* out_inf, void* stream);
+/* The same with the plan pinned, as sylow_hip_g1_msm_tuned: window (4..16, < 0 = the default) is passed to the bucket route; min_len is the
+ * smallest len that takes it (< 0 = the default, 0 = always).  The points do not depend on either. */
+/* @shape srs_g1_xy=u64[8*len] coeffs=u64[4*len*m] out_xy=u64[8*m] out_inf=u8[m] */
+int32_t sylow_hip_kzg_commit_batch_tuned(const uint64_t* srs_g1_xy, const uint64_t* coeffs, size_t len, size_t m,
+                                         int32_t window, int64_t min_len, uint64_t* out_xy, uint8_t* out_inf, void* stream);
+/* The opening of f_j at z_j: y_j = f_j(z_j) and pi_j = commit(q_j) -- the quotient into leased scratch, then the commitment of the quotients
+ * over the same SRS.  pi_j is flagged as the identity exactly when q_j = 0 (f_j constant), the case sylow_hip_kzg_verify_batch reads as
+ * "valid iff C = y G1gen".  (C, z, y, pi) with C from sylow_hip_kzg_commit_batch is a valid row of the verifiers above under tau_g2. */
+/* @shape srs_g1_xy=u64[8*len] coeffs=u64[4*len*m] z=u64[4*m] y_out=u64[4*m] pi_xy=u64[8*m] pi_inf=u8[m] */
+int32_t sylow_hip_kzg_open_batch(const uint64_t* srs_g1_xy, const uint64_t* coeffs, size_t len, size_t m, const uint64_t* z,
+                                 uint64_t* y_out, uint64_t* pi_xy, uint8_t* pi_inf, void* stream);
+
 /* ---- test hooks (stable enough for the repo's own tests; not part of the drop-in surface) ------------------------------------
  * Granger-Scott cyclotomic square (pairing.rs:309-350) and the raw Fp12 selector: 0..7 one-element-per-lane tower ops (tower.hip), 8 / 9 product /
  * cyclotomic square on the carry-free core, 10 / 11 exp_by_neg_z (carry-free / saturated), 16..31 the lane-pair Fp12 layer: 16 product,

@@ -496,6 +496,71 @@ class KzgVerifier {
  private:
   DeviceBuffer tau_, table_;
 };
+// The prover's half of the SRS (sylow_hip.h, "KZG, the prover's side"): srs_g1[k] = tau^k G1gen, kept on the device.  A polynomial is its
+// coefficients, lowest degree first -- any 256-bit words, taken mod r -- padded with zeros by the caller to the length of the SRS.
+class KzgProver {
+ public:
+  explicit KzgProver(const std::vector<G1Affine>& srs_g1) : len_(srs_g1.size()), srs_(to_device_soa(srs_g1)) {
+    if (!len_) throw Error("KzgProver: the SRS holds at least G1gen");
+  }
+  size_t len() const { return len_; }
+  // C_j = sum_k polys[j][k] srs_g1[k] (sylow_hip_kzg_commit_batch_tuned; window / min_len < 0 = the defaults, the points do not depend on them);
+  // *infinity (if given) receives the identity flags (the zero polynomial)
+  std::vector<G1Affine> commit(const std::vector<std::vector<Fp>>& polys, std::vector<uint8_t>* infinity = nullptr, int32_t window = -1, int64_t min_len = -1) const {
+    const size_t m = polys.size();
+    DeviceBuffer dc = upload("KzgProver::commit", polys);
+    DeviceBuffer dout(m * sizeof(G1Affine) + 8), dinf(m + 8);
+    check(sylow_hip_kzg_commit_batch_tuned(srs_.as<uint64_t>(), dc.as<uint64_t>(), len_, m, window, min_len, dout.as<uint64_t>(), dinf.as<uint8_t>(), nullptr),
+          "sylow_hip_kzg_commit_batch_tuned");
+    fetch_flags(infinity, dinf, m);
+    return from_device_soa<G1Affine>(dout, m);
+  }
+  // y_j = f_j(z_j) and pi_j = commit((f_j - y_j) / (X - z_j)) (sylow_hip_kzg_open_batch); a flagged pi_j is the proof for a constant polynomial
+  std::vector<G1Affine> open(const std::vector<std::vector<Fp>>& polys, const std::vector<Fp>& z, std::vector<Fp>* y, std::vector<uint8_t>* infinity = nullptr) const {
+    const size_t m = polys.size();
+    if (z.size() != m) throw Error("KzgProver::open: one point per polynomial");
+    DeviceBuffer dc = upload("KzgProver::open", polys);
+    auto dz = to_device_soa(z);
+    DeviceBuffer dy(m * sizeof(Fp) + 8), dpi(m * sizeof(G1Affine) + 8), dinf(m + 8);
+    check(sylow_hip_kzg_open_batch(srs_.as<uint64_t>(), dc.as<uint64_t>(), len_, m, dz.as<uint64_t>(), dy.as<uint64_t>(), dpi.as<uint64_t>(), dinf.as<uint8_t>(), nullptr),
+          "sylow_hip_kzg_open_batch");
+    fetch_flags(infinity, dinf, m);
+    if (y) *y = from_device_soa<Fp>(dy, m);
+    return from_device_soa<G1Affine>(dpi, m);
+  }
+  // q_j = (f_j - f_j(z_j)) / (X - z_j), canonical words, q_j[len - 1] = 0, and y_j (sylow_hip_kzg_quotient_batch)
+  std::vector<std::vector<Fp>> quotient(const std::vector<std::vector<Fp>>& polys, const std::vector<Fp>& z, std::vector<Fp>* y = nullptr) const {
+    const size_t m = polys.size();
+    if (z.size() != m) throw Error("KzgProver::quotient: one point per polynomial");
+    DeviceBuffer dc = upload("KzgProver::quotient", polys);
+    auto dz = to_device_soa(z);
+    DeviceBuffer dq(4 * len_ * m * sizeof(uint64_t) + 8), dy(m * sizeof(Fp) + 8);
+    check(sylow_hip_kzg_quotient_batch(dc.as<uint64_t>(), len_, m, dz.as<uint64_t>(), dq.as<uint64_t>(), dy.as<uint64_t>(), nullptr), "sylow_hip_kzg_quotient_batch");
+    std::vector<uint64_t> flat(4 * len_ * m);
+    if (m) check(sylow_hip_memcpy_d2h(flat.data(), dq.as<void>(), flat.size() * sizeof(uint64_t), nullptr), "d2h");
+    check(sylow_hip_stream_sync(nullptr), "sync");
+    std::vector<std::vector<Fp>> q(m, std::vector<Fp>(len_));
+    for (size_t j = 0; j < m; ++j) for (size_t k = 0; k < len_; ++k) for (size_t w = 0; w < 4; ++w) q[j][k].w[w] = flat[(j * 4 + w) * len_ + k];
+    if (y) *y = from_device_soa<Fp>(dy, m);
+    return q;
+  }
+
+ private:
+  // the block layout of the prover's calls: word w of coefficient k of polynomial j at (j * 4 + w) * len + k
+  DeviceBuffer upload(const char* who, const std::vector<std::vector<Fp>>& polys) const {
+    const size_t m = polys.size();
+    std::vector<uint64_t> flat(4 * len_ * m);
+    for (size_t j = 0; j < m; ++j) {
+      if (polys[j].size() != len_) throw Error(std::string(who) + ": every polynomial has one coefficient per SRS point (pad with zeros)");
+      for (size_t k = 0; k < len_; ++k) for (size_t w = 0; w < 4; ++w) flat[(j * 4 + w) * len_ + k] = polys[j][k].w[w];
+    }
+    DeviceBuffer d(flat.size() * sizeof(uint64_t) + 8);
+    if (m) { check(sylow_hip_memcpy_h2d(d.as<void>(), flat.data(), flat.size() * sizeof(uint64_t), nullptr), "h2d"); check(sylow_hip_stream_sync(nullptr), "sync"); }
+    return d;
+  }
+  size_t len_;
+  DeviceBuffer srs_;
+};
 // Many signers, ONE message (examples/threshold_signing.rs:92-121): e(sig, G2gen) e(-H(msg), sum_j pubkeys[j]) == identity -- one hash, one G2
 // sum and two Miller loops whatever the number of keys.  `sig` is the signers' aggregate signature (sum() of the individual ones).
 inline bool verify_one_message(const std::vector<G2Affine>& pubkeys, const std::vector<uint8_t>& msg, const G1Affine& sig, Gt* product = nullptr) {

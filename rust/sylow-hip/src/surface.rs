@@ -916,6 +916,85 @@ pub fn kzg_batch_verify_weighted(dev: &Device, tau_g2: &DeviceG2, o: &KzgOpening
     let words = dev.download_aos::<48>(&gt, 1)?;
     Ok((gt_from_words(&words[0]), dev.download(&one)?[0] != 0))
 }
+/// m polynomials of `len` coefficients each on the device, lowest degree first, in the block layout of the prover's calls: word w of
+/// coefficient k of polynomial j at (j * 4 + w) * len + k.  Coefficients are any 256-bit words, taken mod r.
+pub struct KzgPolys {
+    pub words: DeviceBuf<u64>,
+    pub len: usize,
+    pub m: usize,
+}
+impl KzgPolys {
+    /// `polys[j][k]` = coefficient k of polynomial j; every polynomial padded by the caller to the same length >= 1
+    pub fn upload(dev: &Device, polys: &[Vec<Fr>]) -> Result<Self, HipError> {
+        let (m, len) = (polys.len(), polys.first().map_or(1, |f| f.len()));
+        assert!(len >= 1 && polys.iter().all(|f| f.len() == len), "polynomials are padded to one length >= 1");
+        let mut flat = vec![0u64; 4 * len * m];
+        for (j, f) in polys.iter().enumerate() {
+            for (k, c) in fr_words(f).iter().enumerate() {
+                for w in 0..4 {
+                    flat[(j * 4 + w) * len + k] = c[w];
+                }
+            }
+        }
+        Ok(KzgPolys { words: dev.upload(&flat)?, len, m })
+    }
+}
+/// The G1 half of a KZG SRS as the prover's calls take it: `srs.n` affine points tau^k G1gen, k = 0 .. n - 1, and polynomials of exactly
+/// that many coefficients (a host with a longer SRS uploads a prefix).
+fn kzg_srs_fits(srs: &DeviceG1, p: &KzgPolys) {
+    assert!(srs.n == p.len, "the SRS holds one point per coefficient");
+}
+/// q_j = (f_j - f_j(z_j)) / (X - z_j) and y_j = f_j(z_j) (`sylow_hip_kzg_quotient_batch`): the quotients in the layout of `p`, y as [4][m] words.
+pub fn kzg_quotient(dev: &Device, p: &KzgPolys, z: &[Fr]) -> Result<(KzgPolys, Vec<[u64; 4]>), HipError> {
+    assert!(z.len() == p.m);
+    let dz = dev.upload_soa::<4>(&fr_words(z))?;
+    let (q, y) = (dev.alloc::<u64>(4 * p.len * p.m)?, dev.alloc::<u64>(4 * p.m)?);
+    // SAFETY: m polynomials of len coefficients in and out (distinct buffers), 4 * m words of z and of y.
+    device::check(unsafe { ffi::sylow_hip_kzg_quotient_batch(p.words.as_ptr(), p.len, p.m, dz.as_ptr(), q.as_mut_ptr(), y.as_mut_ptr(), dev.stream) })?;
+    let yw = dev.download_aos::<4>(&y, p.m)?;
+    Ok((KzgPolys { words: q, len: p.len, m: p.m }, yw))
+}
+/// y_j = f_j(z_j) alone: the same entry point without a quotient buffer.
+pub fn kzg_evaluate(dev: &Device, p: &KzgPolys, z: &[Fr]) -> Result<Vec<[u64; 4]>, HipError> {
+    assert!(z.len() == p.m);
+    let dz = dev.upload_soa::<4>(&fr_words(z))?;
+    let y = dev.alloc::<u64>(4 * p.m)?;
+    // SAFETY: as kzg_quotient; a NULL q_out is the documented evaluation-only form.
+    device::check(unsafe { ffi::sylow_hip_kzg_quotient_batch(p.words.as_ptr(), p.len, p.m, dz.as_ptr(), std::ptr::null_mut(), y.as_mut_ptr(), dev.stream) })?;
+    Ok(dev.download_aos::<4>(&y, p.m)?)
+}
+/// C_j = sum_k f_jk srs_k for every polynomial (`sylow_hip_kzg_commit_batch`): m points, the identity as (0, 1) + flag.
+pub fn kzg_commit(dev: &Device, srs: &DeviceG1, p: &KzgPolys) -> Result<DeviceG1, HipError> {
+    kzg_srs_fits(srs, p);
+    let out = DeviceG1 { xy: dev.alloc::<u64>(8 * p.m)?, inf: dev.alloc::<u8>(p.m)?, n: p.m };
+    // SAFETY: len SRS points (no flags), m polynomials of len coefficients, m points and flags out.
+    device::check(unsafe { ffi::sylow_hip_kzg_commit_batch(srs.xy.as_ptr(), p.words.as_ptr(), p.len, p.m, out.xy.as_mut_ptr(), out.inf.as_mut_ptr(), dev.stream) })?;
+    Ok(out)
+}
+/// The same with the plan pinned (`sylow_hip_kzg_commit_batch_tuned`): `window` 4..16 for the bucket route, `min_len` the smallest length
+/// that takes it; negative = the defaults.  The points do not depend on either.
+pub fn kzg_commit_tuned(dev: &Device, srs: &DeviceG1, p: &KzgPolys, window: i32, min_len: i64) -> Result<DeviceG1, HipError> {
+    kzg_srs_fits(srs, p);
+    let out = DeviceG1 { xy: dev.alloc::<u64>(8 * p.m)?, inf: dev.alloc::<u8>(p.m)?, n: p.m };
+    // SAFETY: as kzg_commit.
+    device::check(unsafe {
+        ffi::sylow_hip_kzg_commit_batch_tuned(srs.xy.as_ptr(), p.words.as_ptr(), p.len, p.m, window, min_len, out.xy.as_mut_ptr(), out.inf.as_mut_ptr(), dev.stream)
+    })?;
+    Ok(out)
+}
+/// The opening of every f_j at z_j (`sylow_hip_kzg_open_batch`): (y as [4][m] words, pi); pi_j is the identity exactly when f_j is constant.
+pub fn kzg_open(dev: &Device, srs: &DeviceG1, p: &KzgPolys, z: &[Fr]) -> Result<(Vec<[u64; 4]>, DeviceG1), HipError> {
+    kzg_srs_fits(srs, p);
+    assert!(z.len() == p.m);
+    let dz = dev.upload_soa::<4>(&fr_words(z))?;
+    let y = dev.alloc::<u64>(4 * p.m)?;
+    let pi = DeviceG1 { xy: dev.alloc::<u64>(8 * p.m)?, inf: dev.alloc::<u8>(p.m)?, n: p.m };
+    // SAFETY: len SRS points, m polynomials of len coefficients, 4 * m words of z and of y, m points and flags out.
+    device::check(unsafe {
+        ffi::sylow_hip_kzg_open_batch(srs.xy.as_ptr(), p.words.as_ptr(), p.len, p.m, dz.as_ptr(), y.as_mut_ptr(), pi.xy.as_mut_ptr(), pi.inf.as_mut_ptr(), dev.stream)
+    })?;
+    Ok((dev.download_aos::<4>(&y, p.m)?, pi))
+}
 /// AND of a device-resident flag vector (one rank; `all_valid` in lib.rs adds the reduce over ranks).
 pub fn flags_all(dev: &Device, flags: &DeviceBuf<u8>) -> Result<bool, HipError> {
     let out = dev.alloc::<i32>(1)?;

@@ -157,6 +157,10 @@ SIGNATURES = {
     "sylow_hip_kzg_verify_batch": [c_u64p, c_u64p, c_u8p, c_u64p, c_u64p, c_u64p, c_u8p, c_u8p, c_sz, c_vp],
     "sylow_hip_kzg_verify_line_table_batch": [c_vp, c_u64p, c_u8p, c_u64p, c_u64p, c_u64p, c_u8p, c_u8p, c_sz, c_vp],
     "sylow_hip_kzg_batch_verify_weighted": [c_u64p, c_u64p, c_u8p, c_u64p, c_u64p, c_u64p, c_u8p, c_u64p, c_sz, c_u64p, c_u8p, c_vp],
+    "sylow_hip_kzg_quotient_batch": [c_u64p, c_sz, c_sz, c_u64p, c_u64p, c_u64p, c_vp],
+    "sylow_hip_kzg_commit_batch": [c_u64p, c_u64p, c_sz, c_sz, c_u64p, c_u8p, c_vp],
+    "sylow_hip_kzg_commit_batch_tuned": [c_u64p, c_u64p, c_sz, c_sz, c_i32, ctypes.c_int64, c_u64p, c_u8p, c_vp],
+    "sylow_hip_kzg_open_batch": [c_u64p, c_u64p, c_sz, c_sz, c_u64p, c_u64p, c_u64p, c_u8p, c_vp],
     "sylow_hip_g1_msm": [c_u64p, c_u8p, c_u64p, c_sz, c_u64p, c_u8p, c_vp],
     "sylow_hip_g1_msm_tuned": [c_u64p, c_u8p, c_u64p, c_sz, c_i32, ctypes.c_int64, c_u64p, c_u8p, c_vp],
     "sylow_hip_g2_sum_batch": [c_u64p, c_u8p, c_sz, c_u64p, c_u8p, c_vp],

@@ -575,6 +575,36 @@ class KzgVerifier:
         return engine().kzg_batch_verify_weighted(self.tau_g2.xy, c.xy, self._words(z), self._words(y), pi.xy, self._words(weights), c.infinity, pi.infinity)[1]
 
 
+class KzgProver:
+    """The prover's half of a BN254 KZG SRS: srs_g1 = (tau^k G1gen) for k = 0 .. len - 1.  `polys` below is [m, len, 4] words or m lists of
+    Python ints (lowest degree first, padded with zeros to the length of the SRS by the caller if shorter) -- any 256-bit values, taken mod
+    r; z as for KzgVerifier.  (commit(polys), z, *open(polys, z)) is the tuple KzgVerifier.verify takes."""
+
+    def __init__(self, srs_g1: G1Affine):
+        if len(srs_g1) < 1 or srs_g1.infinity.any():
+            raise ValueError("KzgProver: srs_g1 holds at least G1gen and no identity")
+        self.srs_g1 = srs_g1
+
+    def _polys(self, polys):
+        a = np.asarray(polys)
+        if a.dtype == object or a.ndim == 2:
+            rows = [list(f) for f in polys]
+            a = fp([int(v) for f in rows for v in f]).reshape(len(rows), -1, 4) if rows else np.zeros((0, len(self.srs_g1), 4), dtype=np.uint64)
+        if a.ndim != 3 or a.shape[1] != len(self.srs_g1):
+            raise ValueError("KzgProver: every polynomial has one coefficient per SRS point (pad with zeros)")
+        return a
+
+    def commit(self, polys) -> G1Affine:
+        """C_j = sum_k f_jk srs_k (sylow_hip_kzg_commit_batch); the zero polynomial commits to the identity."""
+        return G1Affine(*engine().kzg_commit(self.srs_g1.xy, self._polys(polys)))
+
+    def open(self, polys, z):
+        """(y [m, 4] words, pi: G1Affine) with y_j = f_j(z_j) and pi_j the commitment to (f_j - y_j) / (X - z_j) (sylow_hip_kzg_open_batch); a
+        constant polynomial opens with the identity."""
+        y, pi_xy, pi_inf = engine().kzg_open(self.srs_g1.xy, self._polys(polys), KzgVerifier._words(z))
+        return y, G1Affine(pi_xy, pi_inf)
+
+
 class KeyPair:
     """KeyPair (lib.rs:105-137), a batch of them: secret_key = Fp::new(Fr::rand().value()) -- a scalar below r held as an Fp --
     and public_key = G2Projective::generator() * secret_key."""

@@ -118,6 +118,11 @@ int32_t sum_tree_strided(uint64_t* acc, size_t acc_stride, size_t m, uint64_t* o
 size_t sum_segments_scratch_words(size_t n_seg, size_t c);
 int32_t sum_segments(const uint64_t* p_xy, const uint8_t* p_inf, size_t n_seg, size_t c, uint64_t* acc, uint64_t* out_xy, uint8_t* out_inf, void* stream);
 }  // namespace g1h
+namespace msmh {        // msm.hip: what sylow_hip_g1_msm(_tuned) does by default, for the units that plan around it
+size_t g1_default_min();           // the smallest n that takes the bucket route (G1Lane::DEFAULT_MIN)
+size_t default_budget();           // bytes of scratch a call may take when sylow_hip_set_scratch_limit is 0
+bool window_ok(int32_t window);    // what the _tuned entry points accept: < 0 (the default) or a width they support
+}  // namespace msmh
 namespace kzgh {        // kzg.hip: F_i = C_i - y_i G1gen + z_i pi_i (affine SoA + flags, stride n) and, when neg_xy is given, -pi_i beside it: one launch
 int32_t fold(const uint64_t* c_xy, const uint8_t* c_inf, const uint64_t* z, const uint64_t* y, const uint64_t* pi_xy, const uint8_t* pi_inf,
              uint64_t* out_xy, uint8_t* out_inf, uint64_t* neg_xy, uint8_t* neg_inf, size_t n, void* stream);

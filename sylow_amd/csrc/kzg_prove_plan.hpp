@@ -1,0 +1,59 @@
+// kzg_prove_plan.hpp -- the geometry of the KZG quotient kernels and the route of a commitment (kzg_prove.hip): every decision between an
+// entry point and its kernels, plain C++ so that tests/cpp/kzg_prove_plan_test.cpp can compile it with g++ on a box without a GPU.  The
+// launch code asks these functions and decides nothing itself.
+#pragma once
+#include <cstddef>
+
+namespace kzg_plan {
+// ---- the quotient: q(X) = (f(X) - f(z)) / (X - z) as the recurrence h_len = 0, h_k = f_k + z h_{k+1} --------------------------------
+// A lane owns KZG_POLY_LANE_COEFFS consecutive coefficients, a block of KZG_POLY_BLOCK lanes a chunk of KZG_POLY_CHUNK; the chunks of one
+// polynomial are joined by ONE carry level: a block per polynomial walks the chunk totals from the top in tiles of KZG_POLY_BLOCK chunks
+// and hands the running carry from tile to tile, so the carry pass has no capacity of its own.
+constexpr int KZG_POLY_BLOCK = 256;              // == BLOCK of common.hpp (kzg_prove.hip asserts it)
+constexpr int KZG_POLY_LANE_COEFFS = 8;          // L: a power of two (the scan's multipliers are z^(L 2^s), a chain of squarings)
+constexpr size_t KZG_POLY_CHUNK = 2048;          // CH = KZG_POLY_BLOCK * KZG_POLY_LANE_COEFFS
+static_assert(KZG_POLY_CHUNK == (size_t)KZG_POLY_BLOCK * KZG_POLY_LANE_COEFFS, "a chunk is a block of lanes");
+static_assert((KZG_POLY_LANE_COEFFS & (KZG_POLY_LANE_COEFFS - 1)) == 0 && (KZG_POLY_BLOCK & (KZG_POLY_BLOCK - 1)) == 0, "powers of two");
+constexpr size_t KZG_QUOT_GRID_CAP = (size_t)1 << 20;   // blocks of one launch; more work than that is walked with a grid stride
+
+constexpr size_t quot_chunks(size_t len) { return (len + KZG_POLY_CHUNK - 1) / KZG_POLY_CHUNK; }
+// (polynomial, chunk) pairs of a batch: the work items of the two chunk kernels.  m len <= 2^64 - 1 is the caller's array; no product here
+// is larger than it
+constexpr size_t quot_items(size_t len, size_t m) { return quot_chunks(len) * m; }
+constexpr size_t quot_grid(size_t items) { return items < KZG_QUOT_GRID_CAP ? items : KZG_QUOT_GRID_CAP; }
+// 0: every polynomial is one chunk -- ONE launch, no totals, no carries; 1: totals, the carry level, then the chunks again
+constexpr int quot_carry_levels(size_t len) { return quot_chunks(len) > 1 ? 1 : 0; }
+// serial tiles of the carry level per polynomial
+constexpr size_t quot_carry_tiles(size_t len) { return (quot_chunks(len) + KZG_POLY_BLOCK - 1) / KZG_POLY_BLOCK; }
+// u64 words of scratch the quotient leases: the chunk totals and the carries, [4][m chunks] each; none for one chunk
+constexpr size_t quot_scratch_words(size_t len, size_t m) { return quot_carry_levels(len) ? 2 * 4 * quot_items(len, m) : 0; }
+
+// ---- the commitment: out_j = sum_k f_jk srs_k ----------------------------------------------------------------------------------------
+enum class Route {
+  SHORT,       // every (polynomial, term) pair a lane of ONE sylow_hip_g1_scalar_mul_batch, then the segmented sum; in chunks of whole polynomials
+  BUCKET,      // sylow_hip_g1_msm_tuned(min_n = 0) per polynomial: the bucket method
+  MSM_EACH,    // sylow_hip_g1_msm per polynomial with its own defaults: the short route's fallback when ONE polynomial does not fit the budget
+};
+// Bytes the short route takes per (polynomial, term) pair: the window table sylow_hip_g1_scalar_mul_batch leases (1 KB), the scalar mod r
+// (32), the replicated base (64), the product (64 + its flag, padded to 8) and the segmented sum's partials (at most one projective point, 96)
+constexpr size_t KZG_SHORT_BYTES_PER_TERM = 1024 + 32 + 64 + 64 + 8 + 96;
+// len * KZG_SHORT_BYTES_PER_TERM, saturated (len itself is bounded by the caller's array; the product need not be)
+constexpr size_t short_bytes_per_poly(size_t len) {
+  return len > (size_t)-1 / KZG_SHORT_BYTES_PER_TERM ? (size_t)-1 : len * KZG_SHORT_BYTES_PER_TERM;
+}
+// polynomials one chunk of the short route holds under `budget` bytes: 0 when not even one fits
+constexpr size_t short_polys_per_chunk(size_t len, size_t m, size_t budget) {
+  return budget / short_bytes_per_poly(len) < m ? budget / short_bytes_per_poly(len) : m;
+}
+struct CommitPlan {
+  Route route;
+  size_t polys_per_chunk;      // SHORT only: whole polynomials per chunk, >= 1
+};
+// min_len: the smallest len that takes the bucket route (the caller resolved a negative argument to the default); budget: the scratch
+// limit in force, or the default
+constexpr CommitPlan commit_plan(size_t len, size_t m, size_t min_len, size_t budget) {
+  return len >= min_len ? CommitPlan{Route::BUCKET, 0}
+         : short_polys_per_chunk(len, m, budget) == 0 ? CommitPlan{Route::MSM_EACH, 0}
+                                                      : CommitPlan{Route::SHORT, short_polys_per_chunk(len, m, budget)};
+}
+}  // namespace kzg_plan

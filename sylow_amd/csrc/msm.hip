@@ -46,6 +46,9 @@ int32_t composed(const uint64_t* p_xy, const uint8_t* p_inf, const uint64_t* k, 
   if (rc == SYLOW_HIP_OK) rc = g1h::sum(xy, inf, n, acc, out_xy, out_inf, 1, 0, 0, stream);
   return host::finish(rc, ws);
 }
+size_t g1_default_min() { return G1Lane::DEFAULT_MIN; }
+size_t default_budget() { return msm::MSM_DEFAULT_BUDGET; }
+bool window_ok(int32_t window) { return window < 0 || (window >= msm::MSM_C_MIN && window <= msm::MSM_C_MAX); }
 }  // namespace msmh
 
 extern "C" {

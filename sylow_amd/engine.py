@@ -1011,6 +1011,56 @@ class Engine:
         self._call("sylow_hip_kzg_batch_verify_weighted", dtau.ptr, *args, self._ptr(dw), n, dgt.ptr, dis.ptr)
         return self.from_device_soa(dgt), bool(dis.download()[0])
 
+    # ---- KZG, the prover's side.  polys [m, len, 4]: m polynomials of len coefficients, lowest degree first, any 256-bit words taken mod r;
+    # srs_g1 [len, 8]: tau^k G1gen, k = 0 .. len - 1; z [m, 4].  The device layout is [m][4][len] (include/sylow_hip.h) ----
+    @staticmethod
+    def _kzg_polys(polys):
+        a = np.ascontiguousarray(polys, dtype=np.uint64)
+        assert a.ndim == 3 and a.shape[2] == 4 and a.shape[1] >= 1, a.shape
+        return a
+
+    def _kzg_polys_up(self, a):
+        return self.to_device(np.ascontiguousarray(a.transpose(0, 2, 1))) if a.shape[0] else None
+
+    def kzg_quotient(self, polys, z, want_q=True, want_y=True):
+        """q_j = (f_j - f_j(z_j)) / (X - z_j) as [m, len, 4] canonical words (q[len - 1] = 0) and y_j = f_j(z_j) as [m, 4]
+        (sylow_hip_kzg_quotient_batch); an output that is not wanted is None (want_q = False is plain evaluation)."""
+        a, z = self._kzg_polys(polys), _aos(z, 4)
+        m, ln = a.shape[0], a.shape[1]
+        assert z.shape[0] == m and (want_q or want_y)
+        dc, dz = self._kzg_polys_up(a), (self.to_device_soa(z, 4) if m else None)
+        dq = self.empty((max(m, 1), 4, ln)) if want_q else None
+        dy = self.empty((4, max(m, 1))) if want_y else None
+        self._call("sylow_hip_kzg_quotient_batch", self._ptr(dc), ln, m, self._ptr(dz), self._ptr(dq), self._ptr(dy))
+        q = np.ascontiguousarray(dq.download()[:m].transpose(0, 2, 1)) if want_q else None
+        return q, (self.from_device_soa(dy)[:m] if want_y else None)
+
+    def kzg_commit(self, srs_g1, polys, window=-1, min_len=-1):
+        """C_j = sum_k f_jk srs_k for every polynomial (sylow_hip_kzg_commit_batch): ([m, 8] affine words, [m] flags).  window / min_len >= 0 pin
+        the plan (sylow_hip_kzg_commit_batch_tuned: the bucket route's window width, the smallest len that takes it); the points do not
+        depend on them."""
+        a, srs = self._kzg_polys(polys), _aos(srs_g1, 8)
+        m, ln = a.shape[0], a.shape[1]
+        assert srs.shape[0] == ln
+        dc, ds = self._kzg_polys_up(a), self.to_device_soa(srs, 8)
+        do, doi = self.empty((8, max(m, 1))), self.empty((max(m, 1),), np.uint8)
+        if window < 0 and min_len < 0:
+            self._call("sylow_hip_kzg_commit_batch", ds.ptr, self._ptr(dc), ln, m, do.ptr, doi.ptr)
+        else:
+            self._call("sylow_hip_kzg_commit_batch_tuned", ds.ptr, self._ptr(dc), ln, m, int(window), int(min_len), do.ptr, doi.ptr)
+        return self.from_device_soa(do)[:m], doi.download()[:m]
+
+    def kzg_open(self, srs_g1, polys, z):
+        """The opening of every f_j at z_j (sylow_hip_kzg_open_batch): (y [m, 4], pi [m, 8] affine words, pi flags [m]); pi_j is the identity
+        exactly when f_j is constant."""
+        a, srs, z = self._kzg_polys(polys), _aos(srs_g1, 8), _aos(z, 4)
+        m, ln = a.shape[0], a.shape[1]
+        assert srs.shape[0] == ln and z.shape[0] == m
+        dc, ds, dz = self._kzg_polys_up(a), self.to_device_soa(srs, 8), (self.to_device_soa(z, 4) if m else None)
+        dy, dp, dpi = self.empty((4, max(m, 1))), self.empty((8, max(m, 1))), self.empty((max(m, 1),), np.uint8)
+        self._call("sylow_hip_kzg_open_batch", ds.ptr, self._ptr(dc), ln, m, self._ptr(dz), dy.ptr, dp.ptr, dpi.ptr)
+        return self.from_device_soa(dy)[:m], self.from_device_soa(dp)[:m], dpi.download()[:m]
+
     def bls_aggregate_partial(self, pk_xy, msgs, sig_xy, weights=None, pk_inf=None, sig_inf=None):
         """One shard's raw Miller product of the (weighted) aggregate check, [1, 48] words: the input of fp12_product_final_exp."""
         pk_xy, sig_xy = _aos(pk_xy, 16), _aos(sig_xy, 8)
