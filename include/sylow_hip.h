@@ -197,6 +197,32 @@ int32_t sylow_hip_fr_neg_batch(const uint64_t* a, uint64_t* out, size_t n, void*
 /* @shape a=u64[4*n] out=u64[4*n] */
 int32_t sylow_hip_fr_inv_batch(const uint64_t* a, uint64_t* out, size_t n, void* stream);
 
+/* ---- Fr: transforms on radix-2 domains (ntt.hip; geometry, ping-pong and scratch in ntt_plan.hpp) ---------------------------------------
+ * r - 1 = 2^28 * odd, so Fr holds the domains of n = 2^log_n points for 0 <= log_n <= 28, generated by w_n = W^(2^(28 - log_n)) with
+ * W = 5^((r - 1) / 2^28) = 0x2a3c09f0a58a7e8500e0a7eb8ef62abc402d111e41112ed49bd61b6e725b19f0 (the root arkworks, gnark and snarkjs use).
+ * Natural order in, natural order out; the optional coset shift is g (shift = NULL: g = 1):
+ *   forward (inverse = 0):  out_i = sum_k a_k (g w_n^i)^k         -- the values of the polynomial a on the coset g <w_n>
+ *   inverse (inverse = 1):  out_k = n^-1 g^-k sum_i a_i w_n^(-ik)  -- the coefficients from those values
+ * Conventions (those of the KZG prover block below):
+ *   arrays:    in and out are [m][4][n]: m Fr SoA arrays one after another, word w of element k of array j at (j * 4 + w) * n + k -- the layout of
+ *              `coeffs`.  shift is [4] device words.
+ *   scalars:   inputs and shift are ANY 256-bit words, taken mod r; outputs are canonical words below r.
+ *   calls:     stream-ordered, no host synchronisation; scratch leased per call (the table w_n^e, e < n/2, is built per call: 16 n bytes; a
+ *              transform of more than one step also leases one buffer of the size of `out`).  m = 0: OK, nothing launched, nothing written.
+ *   errors:    SYLOW_HIP_E_ARG, no launch, nothing written, for: NULL in or out; log_n < 0 or > 28; inverse not 0 or 1; out overlapping in
+ *              (the two byte ranges of 32 n m bytes are compared); for the _tuned form stages == 0 or stages > 10.
+ *   inverse with shift = 0 mod r: g^-1 is the library's inv(0) = 0, so out_0 = n^-1 sum_i a_i and every other out_k = 0.
+ * One launch builds the table, one more per pass, and one element-wise launch (c s^k a_k) carries the forward shift or the inverse's scale:
+ * a pass is a radix-2^s step (Stockham autosort, s <= 10 stages in LDS, 5 by default), so a transform of log_n <= 5 has ONE pass and a
+ * longer one ceil(log_n / 5); no bit-reversal launch.  log_n is an int32_t like every other small integer of this header. */
+/* @shape in=u64[4*2**log_n*m] shift=u64[4]? out=u64[4*2**log_n*m] */
+int32_t sylow_hip_fr_ntt_batch(const uint64_t* in, int32_t log_n, size_t m, int32_t inverse, const uint64_t* shift, uint64_t* out, void* stream);
+/* The same with the stages of a pass pinned: 1 .. 10 (NTT_STAGES_MAX of ntt_plan.hpp), < 0 = the default (5).  The last pass takes what is left
+ * of log_n.  The values do not depend on it. */
+/* @shape in=u64[4*2**log_n*m] shift=u64[4]? out=u64[4*2**log_n*m] */
+int32_t sylow_hip_fr_ntt_batch_tuned(const uint64_t* in, int32_t log_n, size_t m, int32_t inverse, const uint64_t* shift, int32_t stages,
+                                     uint64_t* out, void* stream);
+
 /* ---- extension tower (test hooks): fields/fp2.rs:285-306,164-171,355-360; fp6.rs:283-367,
  * 415-423; fp12.rs:229-238,536-550,281-286,515-522,426-503 ------------------------------------ */
 /* FieldExtension<D, N, F> component-wise operators (fields/extensions.rs:67-238): Add / Sub / Neg and scale by a base-field
@@ -818,6 +844,12 @@ int32_t sylow_hip_kzg_commit_batch_tuned(const uint64_t* srs_g1_xy, const uint64
 /* @shape srs_g1_xy=u64[8*len] coeffs=u64[4*len*m] z=u64[4*m] y_out=u64[4*m] pi_xy=u64[8*m] pi_inf=u8[m] */
 int32_t sylow_hip_kzg_open_batch(const uint64_t* srs_g1_xy, const uint64_t* coeffs, size_t len, size_t m, const uint64_t* z,
                                  uint64_t* y_out, uint64_t* pi_xy, uint8_t* pi_inf, void* stream);
+/* The commitment of m polynomials given by their VALUES on the domain of n = 2^log_n points (evals [m][4][n], evals_ji = f_j(w_n^i), any words,
+ * taken mod r): sylow_hip_fr_ntt_batch(inverse = 1, no shift) into leased scratch, then sylow_hip_kzg_commit_batch over len = n -- the same
+ * canonical words as committing the interpolated coefficients.  srs_g1_xy is [8][n].  log_n < 0 or > 28: SYLOW_HIP_E_ARG. */
+/* @shape srs_g1_xy=u64[8*2**log_n] evals=u64[4*2**log_n*m] out_xy=u64[8*m] out_inf=u8[m] */
+int32_t sylow_hip_kzg_commit_evals_batch(const uint64_t* srs_g1_xy, const uint64_t* evals, int32_t log_n, size_t m,
+                                         uint64_t* out_xy, uint8_t* out_inf, void* stream);
 
 /* ---- test hooks (stable enough for the repo's own tests; not part of the drop-in surface) ------------------------------------
  * Granger-Scott cyclotomic square (pairing.rs:309-350) and the raw Fp12 selector: 0..7 one-element-per-lane tower ops (tower.hip), 8 / 9 product /

@@ -201,6 +201,33 @@ inline std::vector<Fp> inv(const std::vector<Fp>& a) {
   check(sylow_hip_fr_inv_batch(da.as<uint64_t>(), dout.as<uint64_t>(), a.size(), nullptr), "sylow_hip_fr_inv_batch");
   return from_device_soa<Fp>(dout, a.size());
 }
+// The transform on the domain of n = a.size() = 2^log_n points (sylow_hip_fr_ntt_batch_tuned), natural order in and out.  forward:
+// out_i = sum_k a_k (g w_n^i)^k; inverse: out_k = n^-1 g^-k sum_i a_i w_n^(-ik); shift = the coset shift g (nullptr: 1); stages >= 1 pins the
+// stages of a pass (the values do not depend on it).  Any 256-bit words in, taken mod r; canonical words out.
+inline std::vector<std::vector<Fp>> ntt(const std::vector<std::vector<Fp>>& arrays, bool inverse = false, const Fp* shift = nullptr, int32_t stages = -1) {
+  const size_t m = arrays.size(), n = m ? arrays[0].size() : 1;
+  int32_t log_n = 0;
+  while (((size_t)1 << log_n) < n) ++log_n;
+  if (n != (size_t)1 << log_n) throw Error("fr::ntt: the length is a power of two");
+  std::vector<uint64_t> flat(4 * n * m);
+  for (size_t j = 0; j < m; ++j) {
+    if (arrays[j].size() != n) throw Error("fr::ntt: arrays of one length");
+    for (size_t k = 0; k < n; ++k) for (size_t w = 0; w < 4; ++w) flat[(j * 4 + w) * n + k] = arrays[j][k].w[w];
+  }
+  DeviceBuffer din(flat.size() * sizeof(uint64_t) + 8), dout(flat.size() * sizeof(uint64_t) + 8), dshift(sizeof(Fp));
+  if (m) check(sylow_hip_memcpy_h2d(din.as<void>(), flat.data(), flat.size() * sizeof(uint64_t), nullptr), "h2d");
+  if (shift) check(sylow_hip_memcpy_h2d(dshift.as<void>(), shift->w, sizeof(Fp), nullptr), "h2d");
+  check(sylow_hip_fr_ntt_batch_tuned(din.as<uint64_t>(), log_n, m, inverse ? 1 : 0, shift ? dshift.as<uint64_t>() : nullptr, stages, dout.as<uint64_t>(), nullptr),
+        "sylow_hip_fr_ntt_batch_tuned");
+  if (m) check(sylow_hip_memcpy_d2h(flat.data(), dout.as<void>(), flat.size() * sizeof(uint64_t), nullptr), "d2h");
+  check(sylow_hip_stream_sync(nullptr), "sync");
+  std::vector<std::vector<Fp>> out(m, std::vector<Fp>(n));
+  for (size_t j = 0; j < m; ++j) for (size_t k = 0; k < n; ++k) for (size_t w = 0; w < 4; ++w) out[j][k].w[w] = flat[(j * 4 + w) * n + k];
+  return out;
+}
+inline std::vector<Fp> ntt(const std::vector<Fp>& a, bool inverse = false, const Fp* shift = nullptr, int32_t stages = -1) {
+  return ntt(std::vector<std::vector<Fp>>{a}, inverse, shift, stages)[0];
+}
 }  // namespace fr
 // sum_i k[j][i] * P[j][i] per job (examples/threshold_signing.rs:124-143); rows term-major: row i*n_jobs + j
 inline std::vector<G1Affine> aggregate(const std::vector<G1Affine>& p, const std::vector<Fp>& k, size_t n_jobs, size_t n_terms) {
@@ -512,6 +539,20 @@ class KzgProver {
     DeviceBuffer dout(m * sizeof(G1Affine) + 8), dinf(m + 8);
     check(sylow_hip_kzg_commit_batch_tuned(srs_.as<uint64_t>(), dc.as<uint64_t>(), len_, m, window, min_len, dout.as<uint64_t>(), dinf.as<uint8_t>(), nullptr),
           "sylow_hip_kzg_commit_batch_tuned");
+    fetch_flags(infinity, dinf, m);
+    return from_device_soa<G1Affine>(dout, m);
+  }
+  // The same commitments from the VALUES evals[j][i] = f_j(w_n^i) on the domain of len() = 2^log_n points (sylow_hip_kzg_commit_evals_batch):
+  // word for word commit(fr::ntt(evals, /*inverse=*/true))
+  std::vector<G1Affine> commit_evals(const std::vector<std::vector<Fp>>& evals, std::vector<uint8_t>* infinity = nullptr) const {
+    const size_t m = evals.size();
+    int32_t log_n = 0;
+    while (((size_t)1 << log_n) < len_) ++log_n;
+    if (len_ != (size_t)1 << log_n) throw Error("KzgProver::commit_evals: the SRS holds a power of two of points");
+    DeviceBuffer dc = upload("KzgProver::commit_evals", evals);
+    DeviceBuffer dout(m * sizeof(G1Affine) + 8), dinf(m + 8);
+    check(sylow_hip_kzg_commit_evals_batch(srs_.as<uint64_t>(), dc.as<uint64_t>(), log_n, m, dout.as<uint64_t>(), dinf.as<uint8_t>(), nullptr),
+          "sylow_hip_kzg_commit_evals_batch");
     fetch_flags(infinity, dinf, m);
     return from_device_soa<G1Affine>(dout, m);
   }

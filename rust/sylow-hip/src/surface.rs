@@ -995,6 +995,51 @@ pub fn kzg_open(dev: &Device, srs: &DeviceG1, p: &KzgPolys, z: &[Fr]) -> Result<
     })?;
     Ok((dev.download_aos::<4>(&y, p.m)?, pi))
 }
+/// The commitments of m polynomials given by their VALUES on the domain of `srs.n` = 2^log_n points, `evals` in the layout of `KzgPolys` with
+/// evals_ji = f_j(w_n^i) (`sylow_hip_kzg_commit_evals_batch`): word for word `kzg_commit` of the interpolated coefficients.
+pub fn kzg_commit_evals(dev: &Device, srs: &DeviceG1, evals: &KzgPolys) -> Result<DeviceG1, HipError> {
+    kzg_srs_fits(srs, evals);
+    let log_n = radix2_log(evals.len);
+    let out = DeviceG1 { xy: dev.alloc::<u64>(8 * evals.m)?, inf: dev.alloc::<u8>(evals.m)?, n: evals.m };
+    // SAFETY: 2^log_n SRS points (no flags), m arrays of 2^log_n values, m points and flags out.
+    device::check(unsafe {
+        ffi::sylow_hip_kzg_commit_evals_batch(srs.xy.as_ptr(), evals.words.as_ptr(), log_n, evals.m, out.xy.as_mut_ptr(), out.inf.as_mut_ptr(), dev.stream)
+    })?;
+    Ok(out)
+}
+/// log2 of a radix-2 domain's size (at most 2^28 points: r - 1 = 2^28 * odd)
+fn radix2_log(n: usize) -> i32 {
+    assert!(n.is_power_of_two() && n <= 1 << 28, "a radix-2 domain of at most 2^28 points");
+    n.trailing_zeros() as i32
+}
+/// The transform over Fr of m arrays of n = 2^log_n elements in the layout of `KzgPolys` (`sylow_hip_fr_ntt_batch`), natural order in and out:
+/// forward out_i = sum_k a_k (g w_n^i)^k, inverse out_k = n^-1 g^-k sum_i a_i w_n^(-ik); `shift` is the coset shift g (None: 1).  Any
+/// 256-bit words in, taken mod r; canonical words out, in a buffer of their own.
+pub fn fr_ntt(dev: &Device, a: &KzgPolys, inverse: bool, shift: Option<&Fr>) -> Result<KzgPolys, HipError> {
+    let log_n = radix2_log(a.len);
+    let dsh = match shift {
+        Some(g) => Some(dev.upload_soa::<4>(&fr_words(std::slice::from_ref(g)))?),
+        None => None,
+    };
+    let psh = dsh.as_ref().map_or(std::ptr::null(), |d| d.as_ptr());
+    let out = dev.alloc::<u64>(4 * (1 << log_n) * a.m)?;
+    // SAFETY: m arrays of 2^log_n elements in and out (distinct buffers), 4 words of shift or NULL.
+    device::check(unsafe { ffi::sylow_hip_fr_ntt_batch(a.words.as_ptr(), log_n, a.m, inverse as i32, psh, out.as_mut_ptr(), dev.stream) })?;
+    Ok(KzgPolys { words: out, len: a.len, m: a.m })
+}
+/// The same with the stages of a pass pinned (`sylow_hip_fr_ntt_batch_tuned`): 1..=10, negative = the default.  The values do not depend on it.
+pub fn fr_ntt_tuned(dev: &Device, a: &KzgPolys, inverse: bool, shift: Option<&Fr>, stages: i32) -> Result<KzgPolys, HipError> {
+    let log_n = radix2_log(a.len);
+    let dsh = match shift {
+        Some(g) => Some(dev.upload_soa::<4>(&fr_words(std::slice::from_ref(g)))?),
+        None => None,
+    };
+    let psh = dsh.as_ref().map_or(std::ptr::null(), |d| d.as_ptr());
+    let out = dev.alloc::<u64>(4 * (1 << log_n) * a.m)?;
+    // SAFETY: as fr_ntt.
+    device::check(unsafe { ffi::sylow_hip_fr_ntt_batch_tuned(a.words.as_ptr(), log_n, a.m, inverse as i32, psh, stages, out.as_mut_ptr(), dev.stream) })?;
+    Ok(KzgPolys { words: out, len: a.len, m: a.m })
+}
 /// AND of a device-resident flag vector (one rank; `all_valid` in lib.rs adds the reduce over ranks).
 pub fn flags_all(dev: &Device, flags: &DeviceBuf<u8>) -> Result<bool, HipError> {
     let out = dev.alloc::<i32>(1)?;

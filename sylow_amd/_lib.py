@@ -161,6 +161,9 @@ SIGNATURES = {
     "sylow_hip_kzg_commit_batch": [c_u64p, c_u64p, c_sz, c_sz, c_u64p, c_u8p, c_vp],
     "sylow_hip_kzg_commit_batch_tuned": [c_u64p, c_u64p, c_sz, c_sz, c_i32, ctypes.c_int64, c_u64p, c_u8p, c_vp],
     "sylow_hip_kzg_open_batch": [c_u64p, c_u64p, c_sz, c_sz, c_u64p, c_u64p, c_u64p, c_u8p, c_vp],
+    "sylow_hip_kzg_commit_evals_batch": [c_u64p, c_u64p, c_i32, c_sz, c_u64p, c_u8p, c_vp],
+    "sylow_hip_fr_ntt_batch": [c_u64p, c_i32, c_sz, c_i32, c_u64p, c_u64p, c_vp],
+    "sylow_hip_fr_ntt_batch_tuned": [c_u64p, c_i32, c_sz, c_i32, c_u64p, c_i32, c_u64p, c_vp],
     "sylow_hip_g1_msm": [c_u64p, c_u8p, c_u64p, c_sz, c_u64p, c_u8p, c_vp],
     "sylow_hip_g1_msm_tuned": [c_u64p, c_u8p, c_u64p, c_sz, c_i32, ctypes.c_int64, c_u64p, c_u8p, c_vp],
     "sylow_hip_g2_sum_batch": [c_u64p, c_u8p, c_sz, c_u64p, c_u8p, c_vp],

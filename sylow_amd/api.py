@@ -605,6 +605,39 @@ class KzgProver:
         return y, G1Affine(pi_xy, pi_inf)
 
 
+    def commit_evals(self, evals) -> G1Affine:
+        """The same commitments from the VALUES of the polynomials on the domain of len(srs_g1) = 2^log_n points, evals[j][i] = f_j(w_n^i)
+        (sylow_hip_kzg_commit_evals_batch): word for word commit(intt(evals))."""
+        n = len(self.srs_g1)
+        if n & (n - 1):
+            raise ValueError("KzgProver.commit_evals: the SRS holds a power of two of points")
+        return G1Affine(*engine().kzg_commit_evals(self.srs_g1.xy, self._polys(evals)))
+
+
+def _fr_arrays(values):
+    """a numpy uint64 array is words ([m, n, 4] or [n, 4]); anything else is Python ints, [m][n] or [n]"""
+    if isinstance(values, np.ndarray) and values.dtype == np.uint64:
+        return values
+    a = np.asarray(values, dtype=object)
+    if a.ndim not in (1, 2):
+        raise ValueError("ntt: ints as [n] or [m][n], words as a uint64 array [n, 4] or [m, n, 4]")
+    words = fp(list(a.reshape(-1)))
+    return words.reshape(a.shape + (4,))
+
+
+def ntt(values, shift=None, inverse: bool = False, stages: int = -1) -> np.ndarray:
+    """The values on the domain <w_n> (on the coset g <w_n> with shift = g) of the polynomials whose coefficients are `values`: [m, n, 4] or
+    [n, 4] words, or (lists of) Python ints, n = 2^log_n <= 2^28, natural order in and out: out_i = sum_k a_k (g w_n^i)^k with
+    w_n = W^(2^(28 - log_n)), W = 5^((r - 1) / 2^28) (sylow_hip_fr_ntt_batch).  Canonical words in the shape of the input."""
+    sh = None if shift is None else (fp([int(shift)])[0] if isinstance(shift, int) else np.asarray(shift, dtype=np.uint64).reshape(4))
+    return engine().fr_ntt(_fr_arrays(values), inverse=inverse, shift=sh, stages=stages)
+
+
+def intt(values, shift=None, stages: int = -1) -> np.ndarray:
+    """The inverse of ntt: out_k = n^-1 g^-k sum_i a_i w_n^(-ik).  shift = 0 mod r uses inv(0) = 0."""
+    return ntt(values, shift=shift, inverse=True, stages=stages)
+
+
 class KeyPair:
     """KeyPair (lib.rs:105-137), a batch of them: secret_key = Fp::new(Fr::rand().value()) -- a scalar below r held as an Fp --
     and public_key = G2Projective::generator() * secret_key."""

@@ -1,6 +1,7 @@
 // kzg_prove.hip -- the prover's half of KZG on BN254 under ONE SRS (include/sylow_hip.h, "KZG, the prover's side"): the quotient
 //   q(X) = (f(X) - f(z)) / (X - z) and y = f(z) for m polynomials, as a scan in Fr (the new kernels of this unit); the commitment
-//   sum_k f_k srs_k of m polynomials, composed from the library's own stream-ordered calls; and the opening (y, pi = commit(q)).
+//   sum_k f_k srs_k of m polynomials, composed from the library's own stream-ordered calls; and the opening (y, pi = commit(q)); the
+//   commitment from values on a radix-2 domain is the inverse transform of ntt.hip in front of the same commitment.
 // Geometry and routes: kzg_prove_plan.hpp -- nothing here decides one.
 #include "host.hpp"
 #include "kzg_prove_plan.hpp"
@@ -276,6 +277,18 @@ int32_t sylow_hip_kzg_open_batch(const uint64_t* srs_g1_xy, const uint64_t* coef
   if (rc != SYLOW_HIP_OK) return rc;
   rc = kzgp::quotient(coeffs, len, m, z, (uint64_t*)ws.p, y_out, stream);
   if (rc == SYLOW_HIP_OK) rc = kzgp::commit(srs_g1_xy, (const uint64_t*)ws.p, len, m, /*canonical=*/true, -1, -1, pi_xy, pi_inf, stream);
+  return host::finish(rc, ws);
+}
+int32_t sylow_hip_kzg_commit_evals_batch(const uint64_t* srs_g1_xy, const uint64_t* evals, int32_t log_n, size_t m, uint64_t* out_xy, uint8_t* out_inf, void* stream) {
+  ARGCHK(log_n >= 0 && log_n <= 28); if (!m) return SYLOW_HIP_OK;
+  ARGCHK(srs_g1_xy && evals && out_xy && out_inf);
+  const size_t len = (size_t)1 << log_n;
+  ARGCHK(m <= (size_t)-1 / (4 * sizeof(u64)) / len);
+  host::Lease ws;
+  int32_t rc = ws.acquire(4 * len * m * sizeof(u64), (hipStream_t)stream);
+  if (rc != SYLOW_HIP_OK) return rc;
+  rc = sylow_hip_fr_ntt_batch(evals, log_n, m, /*inverse=*/1, nullptr, (uint64_t*)ws.p, stream);      // the coefficients, canonical
+  if (rc == SYLOW_HIP_OK) rc = kzgp::commit(srs_g1_xy, (const uint64_t*)ws.p, len, m, /*canonical=*/true, -1, -1, out_xy, out_inf, stream);
   return host::finish(rc, ws);
 }
 }  // extern "C"

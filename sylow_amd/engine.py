@@ -1061,6 +1061,39 @@ class Engine:
         self._call("sylow_hip_kzg_open_batch", ds.ptr, self._ptr(dc), ln, m, self._ptr(dz), dy.ptr, dp.ptr, dpi.ptr)
         return self.from_device_soa(dy)[:m], self.from_device_soa(dp)[:m], dpi.download()[:m]
 
+    def kzg_commit_evals(self, srs_g1, evals):
+        """C_j for m polynomials given by their values on the domain of n = 2^log_n points, evals [m, n, 4] with evals[j, i] = f_j(w_n^i)
+        (sylow_hip_kzg_commit_evals_batch: the inverse transform into scratch, then the commitment): ([m, 8] affine words, [m] flags)."""
+        a, srs = self._kzg_polys(evals), _aos(srs_g1, 8)
+        m, n = a.shape[0], a.shape[1]
+        log_n = n.bit_length() - 1
+        assert n == 1 << log_n and srs.shape[0] == n, (n, srs.shape)
+        dc, ds = self._kzg_polys_up(a), self.to_device_soa(srs, 8)
+        do, doi = self.empty((8, max(m, 1))), self.empty((max(m, 1),), np.uint8)
+        self._call("sylow_hip_kzg_commit_evals_batch", ds.ptr, self._ptr(dc), log_n, m, do.ptr, doi.ptr)
+        return self.from_device_soa(do)[:m], doi.download()[:m]
+
+    # ---- Fr transforms on radix-2 domains.  values [m, n, 4] (or [n, 4]: one array), n = 2^log_n <= 2^28, any 256-bit words taken mod r ----
+    def fr_ntt(self, values, inverse=False, shift=None, stages=-1):
+        """forward: out_i = sum_k a_k (g w_n^i)^k; inverse: out_k = n^-1 g^-k sum_i a_i w_n^(-ik), natural order both ways, per array
+        (sylow_hip_fr_ntt_batch).  shift: the coset shift g as [4] words (None: 1).  stages >= 1 pins the stages of a pass
+        (sylow_hip_fr_ntt_batch_tuned); the values do not depend on it.  Canonical words in the shape of `values`."""
+        a = np.ascontiguousarray(values, dtype=np.uint64)
+        one = a.ndim == 2
+        a = self._kzg_polys(a[None] if one else a)
+        m, n = a.shape[0], a.shape[1]
+        log_n = n.bit_length() - 1
+        assert n == 1 << log_n, n
+        din = self._kzg_polys_up(a)
+        dsh = None if shift is None else self.to_device(np.ascontiguousarray(shift, dtype=np.uint64).reshape(4))
+        dout = self.empty((max(m, 1), 4, n))
+        if stages < 0:
+            self._call("sylow_hip_fr_ntt_batch", self._ptr(din), log_n, m, int(bool(inverse)), self._ptr(dsh), dout.ptr)
+        else:
+            self._call("sylow_hip_fr_ntt_batch_tuned", self._ptr(din), log_n, m, int(bool(inverse)), self._ptr(dsh), int(stages), dout.ptr)
+        out = np.ascontiguousarray(dout.download()[:m].transpose(0, 2, 1))
+        return out[0] if one else out
+
     def bls_aggregate_partial(self, pk_xy, msgs, sig_xy, weights=None, pk_inf=None, sig_inf=None):
         """One shard's raw Miller product of the (weighted) aggregate check, [1, 48] words: the input of fp12_product_final_exp."""
         pk_xy, sig_xy = _aos(pk_xy, 16), _aos(sig_xy, 8)

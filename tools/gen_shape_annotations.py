@@ -133,6 +133,9 @@ POLYS = "coeffs=u64[4*len*m]"
 S["kzg_quotient_batch"] = POLYS + " z=u64[4*m] q_out=u64[4*len*m]? y_out=u64[4*m]?"
 S["kzg_commit_batch"] = S["kzg_commit_batch_tuned"] = "srs_g1_xy=u64[8*len] " + POLYS + " out_xy=u64[8*m] out_inf=u8[m]"
 S["kzg_open_batch"] = "srs_g1_xy=u64[8*len] " + POLYS + " z=u64[4*m] y_out=u64[4*m] pi_xy=u64[8*m] pi_inf=u8[m]"
+EVALS = "u64[4*2**log_n*m]"               # m arrays of n = 2^log_n Fr elements
+S["fr_ntt_batch"] = S["fr_ntt_batch_tuned"] = f"in={EVALS} shift=u64[4]? out={EVALS}"
+S["kzg_commit_evals_batch"] = f"srs_g1_xy=u64[8*2**log_n] evals={EVALS} out_xy=u64[8*m] out_inf=u8[m]"
 S["pairing_host"] = "p_aos=u64[8*n] p_inf=u8[n]? q_aos=u64[16*n] q_inf=u8[n]? gt_aos=u64[48*n]"
 S["bls_verify_host"] = "pk_aos=u64[16*n] pk_inf=u8[n]? msgs=u8[*]? msg_offsets=u64[n+1] sig_aos=u64[8*n] sig_inf=u8[n]? ok=u8[n]"
 S["pairing_host_bytes"] = "p_be=u8[64*n] q_be=u8[128*n] gt_aos=u64[48*n] status_p=u8[n] status_q=u8[n]"
