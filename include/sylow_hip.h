@@ -851,6 +851,72 @@ int32_t sylow_hip_kzg_open_batch(const uint64_t* srs_g1_xy, const uint64_t* coef
 int32_t sylow_hip_kzg_commit_evals_batch(const uint64_t* srs_g1_xy, const uint64_t* evals, int32_t log_n, size_t m,
                                          uint64_t* out_xy, uint8_t* out_inf, void* stream);
 
+/* ---- Groth16, the prover's side: R1CS products, the quotient and the proof under ONE proving key (groth16_prove.hip; lanes per row, grids,
+ * scratch and chunks in groth16_prove_plan.hpp) ------------------------------------------------------------------------------------------
+ * Conventions of the calls below (those of the transforms and of the KZG prover block):
+ *   Fr arrays: [4][n] SoA words; batches are [m][4][n], m arrays one after another.  ANY 256-bit word is taken mod r on input (not like
+ *              Fp::new first); outputs are canonical words below r.
+ *   points:    G1 [8][n] / G2 [16][n] affine SoA words with an optional identity-flag array ([n] bytes, NULL = none flagged); outputs carry
+ *              their flags, the identity as (0, 1) + its flag.  Taken as given: no on-curve check, no subgroup check.
+ *   calls:     stream-ordered, no host synchronisation; scratch leased per call.  m = 0: OK, nothing launched, nothing written.  NULL where
+ *              a pointer is required: SYLOW_HIP_E_ARG, no launch, nothing written. */
+/* out_j = M w_j over Fr for a sparse matrix M in CSR and m vectors: row_ptr [rows + 1] (non-decreasing, row_ptr[rows] = nnz), col [nnz],
+ * val [4][nnz]; w [m][4][n_cols]; out [m][4][n_out] with n_out >= rows:
+ *     out_j[i] = sum over the entries e of row i of val_e w_j[col_e] mod r,     out_j[i] = 0 for rows <= i < n_out (the padding to a domain).
+ * THE KERNEL NEVER READS OUTSIDE ITS ARRAYS, whatever the index arrays hold: an entry with col >= n_cols contributes zero, and a row's ends are
+ * clamped to nnz (an end before its start is an empty row) -- a malformed matrix gives a wrong number, never a fault.  Column indices are
+ * uint64_t because this header has no other unsigned integer array type.  n_out < rows, or a size whose byte count overflows:
+ * SYLOW_HIP_E_ARG.  m = 0 or n_out = 0: OK, nothing launched.  2^k lanes share a row (k = 0 .. 6, from nnz / rows alone: a lane gets at least 8
+ * entries of an average row); a lane adds up to 16 products UNREDUCED in 16 limbs per Barrett reduction; the vectors are brought to canonical
+ * form once per call into leased scratch (32 n_cols m bytes, SoA as they came). */
+/* @shape row_ptr=u64[rows+1] col=u64[nnz]? val=u64[4*nnz]? w=u64[4*n_cols*m]? out=u64[4*n_out*m] */
+int32_t sylow_hip_fr_spmv_batch(const uint64_t* row_ptr, const uint64_t* col, const uint64_t* val, size_t rows, size_t nnz, const uint64_t* w,
+                                size_t n_cols, size_t m, size_t n_out, uint64_t* out, void* stream);
+/* The same with the lanes per row pinned: 2^lanes_log, lanes_log = 0 .. 6, < 0 = the default; more than 6: SYLOW_HIP_E_ARG.  The values do not
+ * depend on it. */
+/* @shape row_ptr=u64[rows+1] col=u64[nnz]? val=u64[4*nnz]? w=u64[4*n_cols*m]? out=u64[4*n_out*m] */
+int32_t sylow_hip_fr_spmv_batch_tuned(const uint64_t* row_ptr, const uint64_t* col, const uint64_t* val, size_t rows, size_t nnz, const uint64_t* w,
+                                      size_t n_cols, size_t m, size_t n_out, int32_t lanes_log, uint64_t* out, void* stream);
+/* a, b, c [m][4][n], n = 2^log_n, 0 <= log_n <= 28: the values of three polynomials of degree < n on the domain <w_n> of the transforms above.
+ * h_out [m][4][n]: the coefficients of THE polynomial of degree < n that equals (a b - c) / (X^n - 1) on the coset 5 <w_n>.  Where
+ * a_i b_i = c_i on the whole domain that is the exact quotient, of degree <= n - 2, and h[n - 1] = 0 is written; otherwise it is what the
+ * definition says, and no error is raised.  Three inverse transforms, three forward ones onto the coset, ONE element-wise kernel
+ * (a b - c) zinv -- X^n - 1 is the constant 5^n - 1 there, its inverse a table of 29 constants -- and one inverse transform from the coset:
+ * the 3 m arrays lie in one leased buffer, so it is three sylow_hip_fr_ntt_batch calls.  Scratch: 192 n m bytes and what those calls lease.
+ * h_out may be a, b or c.  log_n < 0 or > 28: SYLOW_HIP_E_ARG. */
+/* @shape a=u64[4*2**log_n*m] b=u64[4*2**log_n*m] c=u64[4*2**log_n*m] h_out=u64[4*2**log_n*m] */
+int32_t sylow_hip_groth16_quotient_batch(const uint64_t* a, const uint64_t* b, const uint64_t* c, int32_t log_n, size_t m, uint64_t* h_out, void* stream);
+/* m proofs for m witnesses of ONE circuit under ONE proving key, with the caller's randomness.
+ *   circuit:   three CSR matrices A, B, C (a_*, b_*, c_* as in sylow_hip_fr_spmv_batch) of n_cons rows and n_vars columns; the domain has
+ *              n = 2^log_n >= n_cons points; variable 0 is the constant 1, variables 1 .. n_inputs are public, n_inputs < n_vars.
+ *   key:       arkworks' names.  alpha_g1, beta_g1, delta_g1 [8][1] and beta_g2, delta_g2 [16][1] WITHOUT flag arrays; a_query [8][n_vars],
+ *              b_g1_query [8][n_vars], b_g2_query [16][n_vars], h_query [8][n - 1], l_query [8][n_vars - n_inputs - 1], each with its optional
+ *              flag array (a variable absent from A or B has the identity there).  h_query and l_query may be NULL when they hold no point.
+ *   witnesses: z [m][4][n_vars]; randomness r, s [4][m].  Any words, taken mod r.
+ *   proofs:    A [8][m], B [16][m], C [8][m] with their flags -- what sylow_hip_groth16_verify_batch takes.
+ * With h = the quotient above of (A z, B z, C z) padded to the domain:
+ *     A  = alpha_g1 + sum_i z_i a_query_i + r delta_g1          B  = beta_g2 + sum_i z_i b_g2_query_i + s delta_g2
+ *     B1 = beta_g1 + sum_i z_i b_g1_query_i + s delta_g1
+ *     C  = sum_{i > n_inputs} z_i l_query_{i - n_inputs - 1} + sum_{k < n - 1} h_k h_query_k + s A + r B1 - (r s mod r) delta_g1
+ * Per witness four sylow_hip_g1_msm and one sylow_hip_g2_msm (whatever route they pick) on canonical scalars; the closing sums run through
+ * sylow_hip_g1_scalar_mul_batch / sylow_hip_g2_scalar_mul_batch / the add calls, one lane per witness.
+ * THE LIBRARY CHECKS NEITHER z_0 = 1 NOR THAT THE CONSTRAINTS HOLD: an unsatisfied witness yields a proof the verifier rejects.
+ * Witnesses go through in chunks of whole witnesses under sylow_hip_set_scratch_limit (default 1 GB; about 320 n + 64 n_vars bytes each and 16 n once); if
+ * not even one fits: SYLOW_HIP_E_HIP, the code of a failed scratch allocation, with the bytes needed in sylow_hip_last_error.
+ * log_n < 0 or > 28, n_cons > 2^log_n, n_inputs >= n_vars: SYLOW_HIP_E_ARG. */
+/* @shape a_row_ptr=u64[n_cons+1] a_col=u64[a_nnz]? a_val=u64[4*a_nnz]? b_row_ptr=u64[n_cons+1] b_col=u64[b_nnz]? b_val=u64[4*b_nnz]? c_row_ptr=u64[n_cons+1] c_col=u64[c_nnz]? c_val=u64[4*c_nnz]? alpha_g1=u64[8] beta_g1=u64[8] delta_g1=u64[8] beta_g2=u64[16] delta_g2=u64[16] a_query=u64[8*n_vars] a_query_inf=u8[n_vars]? b_g1_query=u64[8*n_vars] b_g1_query_inf=u8[n_vars]? b_g2_query=u64[16*n_vars] b_g2_query_inf=u8[n_vars]? h_query=u64[*]? h_query_inf=u8[*]? l_query=u64[*]? l_query_inf=u8[*]? z=u64[4*n_vars*m] r=u64[4*m] s=u64[4*m] a_xy=u64[8*m] a_inf=u8[m] b_xy=u64[16*m] b_inf=u8[m] c_xy=u64[8*m] c_inf=u8[m] */
+int32_t sylow_hip_groth16_prove_batch(const uint64_t* a_row_ptr, const uint64_t* a_col, const uint64_t* a_val, size_t a_nnz,
+                                      const uint64_t* b_row_ptr, const uint64_t* b_col, const uint64_t* b_val, size_t b_nnz,
+                                      const uint64_t* c_row_ptr, const uint64_t* c_col, const uint64_t* c_val, size_t c_nnz,
+                                      size_t n_cons, size_t n_vars, size_t n_inputs, int32_t log_n,
+                                      const uint64_t* alpha_g1, const uint64_t* beta_g1, const uint64_t* delta_g1,
+                                      const uint64_t* beta_g2, const uint64_t* delta_g2,
+                                      const uint64_t* a_query, const uint8_t* a_query_inf, const uint64_t* b_g1_query, const uint8_t* b_g1_query_inf,
+                                      const uint64_t* b_g2_query, const uint8_t* b_g2_query_inf, const uint64_t* h_query, const uint8_t* h_query_inf,
+                                      const uint64_t* l_query, const uint8_t* l_query_inf,
+                                      const uint64_t* z, const uint64_t* r, const uint64_t* s, size_t m,
+                                      uint64_t* a_xy, uint8_t* a_inf, uint64_t* b_xy, uint8_t* b_inf, uint64_t* c_xy, uint8_t* c_inf, void* stream);
+
 /* ---- test hooks (stable enough for the repo's own tests; not part of the drop-in surface) ------------------------------------
  * Granger-Scott cyclotomic square (pairing.rs:309-350) and the raw Fp12 selector: 0..7 one-element-per-lane tower ops (tower.hip), 8 / 9 product /
  * cyclotomic square on the carry-free core, 10 / 11 exp_by_neg_z (carry-free / saturated), 16..31 the lane-pair Fp12 layer: 16 product,

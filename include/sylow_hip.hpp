@@ -631,6 +631,127 @@ inline std::vector<G1Affine> sub(const std::vector<G1Affine>& a, const std::vect
   return from_device_soa<G1Affine>(dout, n);
 }
 
+// ---- Groth16, the prover's side (sylow_hip.h, "Groth16, the prover's side") ----------------------------------------------------------------
+// A sparse matrix over Fr in CSR: the entries of row i are col / val [row_ptr[i] .. row_ptr[i + 1])
+struct CsrMatrix {
+  std::vector<uint64_t> row_ptr{0}, col;
+  std::vector<Fp> val;
+  size_t rows() const { return row_ptr.size() - 1; }
+  void add_row(const std::vector<std::pair<uint64_t, Fp>>& entries) {
+    for (const auto& e : entries) { col.push_back(e.first); val.push_back(e.second); }
+    row_ptr.push_back(col.size());
+  }
+};
+namespace detail {
+// m arrays of n elements <-> the block layout [m][4][n]: word w of element k of array j at (j * 4 + w) * n + k
+inline DeviceBuffer fr_arrays_up(const char* who, const std::vector<std::vector<Fp>>& a, size_t n) {
+  std::vector<uint64_t> flat(4 * n * a.size());
+  for (size_t j = 0; j < a.size(); ++j) {
+    if (a[j].size() != n) throw Error(std::string(who) + ": arrays of one length");
+    for (size_t k = 0; k < n; ++k) for (size_t w = 0; w < 4; ++w) flat[(j * 4 + w) * n + k] = a[j][k].w[w];
+  }
+  DeviceBuffer d(flat.size() * sizeof(uint64_t) + 8);
+  if (!flat.empty()) { check(sylow_hip_memcpy_h2d(d.as<void>(), flat.data(), flat.size() * sizeof(uint64_t), nullptr), "h2d"); check(sylow_hip_stream_sync(nullptr), "sync"); }
+  return d;
+}
+inline std::vector<std::vector<Fp>> fr_arrays_down(const DeviceBuffer& d, size_t n, size_t m) {
+  std::vector<uint64_t> flat(4 * n * m);
+  if (!flat.empty()) check(sylow_hip_memcpy_d2h(flat.data(), d.as<void>(), flat.size() * sizeof(uint64_t), nullptr), "d2h");
+  check(sylow_hip_stream_sync(nullptr), "sync");
+  std::vector<std::vector<Fp>> out(m, std::vector<Fp>(n));
+  for (size_t j = 0; j < m; ++j) for (size_t k = 0; k < n; ++k) for (size_t w = 0; w < 4; ++w) out[j][k].w[w] = flat[(j * 4 + w) * n + k];
+  return out;
+}
+struct CsrDevice {
+  DeviceBuffer row_ptr, col, val;
+  size_t rows, nnz;
+};
+inline CsrDevice csr_up(const CsrMatrix& m) {
+  if (m.row_ptr.empty() || m.col.size() != m.val.size()) throw Error("CsrMatrix: row_ptr holds rows + 1 offsets, col and val one entry each");
+  DeviceBuffer rp(m.row_ptr.size() * 8 + 8), col(m.col.size() * 8 + 8);
+  check(sylow_hip_memcpy_h2d(rp.as<void>(), m.row_ptr.data(), m.row_ptr.size() * 8, nullptr), "h2d");
+  if (!m.col.empty()) check(sylow_hip_memcpy_h2d(col.as<void>(), m.col.data(), m.col.size() * 8, nullptr), "h2d");
+  check(sylow_hip_stream_sync(nullptr), "sync");
+  return CsrDevice{std::move(rp), std::move(col), to_device_soa(m.val), m.rows(), m.col.size()};
+}
+}  // namespace detail
+namespace fr {
+// out[j] = M w[j] for m vectors of one length, padded with zero rows to n_out (0: M.rows()) (sylow_hip_fr_spmv_batch_tuned; lanes_log >= 0 pins
+// 2^lanes_log lanes per row, the values do not depend on it).  An entry whose column is past the vectors contributes zero.
+inline std::vector<std::vector<Fp>> spmv(const CsrMatrix& mat, const std::vector<std::vector<Fp>>& w, size_t n_out = 0, int32_t lanes_log = -1) {
+  const size_t m = w.size(), n_cols = m ? w[0].size() : 0;
+  if (!n_out) n_out = mat.rows();
+  detail::CsrDevice d = detail::csr_up(mat);
+  DeviceBuffer dw = detail::fr_arrays_up("fr::spmv", w, n_cols), dout(4 * n_out * m * sizeof(uint64_t) + 8);
+  check(sylow_hip_fr_spmv_batch_tuned(d.row_ptr.as<uint64_t>(), d.col.as<uint64_t>(), d.val.as<uint64_t>(), d.rows, d.nnz, dw.as<uint64_t>(), n_cols, m, n_out, lanes_log,
+                                      dout.as<uint64_t>(), nullptr), "sylow_hip_fr_spmv_batch_tuned");
+  return detail::fr_arrays_down(dout, n_out, m);
+}
+}  // namespace fr
+// h[j] = the coefficients of the polynomial of degree < n that equals (a[j] b[j] - c[j]) / (X^n - 1) on the coset 5 <w_n>, for the values of three
+// polynomials on the domain of n = 2^log_n points (sylow_hip_groth16_quotient_batch); h[j][n - 1] = 0 where a b = c on the whole domain
+inline std::vector<std::vector<Fp>> groth16_quotient(const std::vector<std::vector<Fp>>& a, const std::vector<std::vector<Fp>>& b, const std::vector<std::vector<Fp>>& c) {
+  const size_t m = a.size(), n = m ? a[0].size() : 1;
+  int32_t log_n = 0;
+  while (((size_t)1 << log_n) < n) ++log_n;
+  if (n != (size_t)1 << log_n || b.size() != m || c.size() != m) throw Error("groth16_quotient: three batches of m arrays of 2^log_n values");
+  DeviceBuffer da = detail::fr_arrays_up("groth16_quotient", a, n), db = detail::fr_arrays_up("groth16_quotient", b, n), dc = detail::fr_arrays_up("groth16_quotient", c, n);
+  DeviceBuffer dh(4 * n * m * sizeof(uint64_t) + 8);
+  check(sylow_hip_groth16_quotient_batch(da.as<uint64_t>(), db.as<uint64_t>(), dc.as<uint64_t>(), log_n, m, dh.as<uint64_t>(), nullptr), "sylow_hip_groth16_quotient_batch");
+  return detail::fr_arrays_down(dh, n, m);
+}
+// An R1CS for the prover: variable 0 is the constant 1, variables 1 .. n_inputs are public, the domain has 2^log_n >= a.rows() points
+struct Groth16Circuit {
+  CsrMatrix a, b, c;
+  size_t n_vars, n_inputs;
+  int32_t log_n;
+};
+// A proving key, arkworks' names; *_inf are the queries' identity flags (empty: none flagged)
+struct Groth16ProvingKey {
+  G1Affine alpha_g1, beta_g1, delta_g1;
+  G2Affine beta_g2, delta_g2;
+  std::vector<G1Affine> a_query, b_g1_query;
+  std::vector<G2Affine> b_g2_query;
+  std::vector<G1Affine> h_query, l_query;                 // 2^log_n - 1 and n_vars - n_inputs - 1 points
+  std::vector<uint8_t> a_query_inf, b_g1_query_inf, b_g2_query_inf, h_query_inf, l_query_inf;
+};
+struct Groth16Proofs {
+  std::vector<G1Affine> a, c;
+  std::vector<G2Affine> b;
+  std::vector<uint8_t> a_inf, b_inf, c_inf;
+};
+// One proof per witness z[j] (n_vars values each) with the caller's randomness r[j], s[j] (sylow_hip_groth16_prove_batch): what groth16_verify
+// takes with inputs z[j][1 .. n_inputs].  Neither z_0 = 1 nor the constraints are checked.
+inline Groth16Proofs groth16_prove(const Groth16ProvingKey& pk, const Groth16Circuit& ct, const std::vector<std::vector<Fp>>& z, const std::vector<Fp>& r,
+                                   const std::vector<Fp>& s) {
+  const size_t m = z.size(), n = (size_t)1 << ct.log_n;
+  if (r.size() != m || s.size() != m) throw Error("groth16_prove: one r and one s per witness");
+  if (ct.n_inputs >= ct.n_vars || pk.a_query.size() != ct.n_vars || pk.b_g1_query.size() != ct.n_vars || pk.b_g2_query.size() != ct.n_vars ||
+      pk.h_query.size() != n - 1 || pk.l_query.size() != ct.n_vars - ct.n_inputs - 1 || ct.b.rows() != ct.a.rows() || ct.c.rows() != ct.a.rows())
+    throw Error("groth16_prove: the proving key does not fit the circuit");
+  detail::CsrDevice da = detail::csr_up(ct.a), db = detail::csr_up(ct.b), dc = detail::csr_up(ct.c);
+  auto one1 = [](const G1Affine& p) { return to_device_soa(std::vector<G1Affine>{p}); };
+  auto one2 = [](const G2Affine& p) { return to_device_soa(std::vector<G2Affine>{p}); };
+  DeviceBuffer alpha = one1(pk.alpha_g1), beta1 = one1(pk.beta_g1), delta1 = one1(pk.delta_g1), beta2 = one2(pk.beta_g2), delta2 = one2(pk.delta_g2);
+  DeviceBuffer aq = to_device_soa(pk.a_query), b1q = to_device_soa(pk.b_g1_query), b2q = to_device_soa(pk.b_g2_query), hq = to_device_soa(pk.h_query), lq = to_device_soa(pk.l_query);
+  auto flags = [](const std::vector<uint8_t>& f, size_t n) { return Flags(f.empty() ? nullptr : &f, n); };
+  Flags aqi = flags(pk.a_query_inf, ct.n_vars), b1qi = flags(pk.b_g1_query_inf, ct.n_vars), b2qi = flags(pk.b_g2_query_inf, ct.n_vars), hqi = flags(pk.h_query_inf, n - 1),
+        lqi = flags(pk.l_query_inf, pk.l_query.size());
+  DeviceBuffer dz = detail::fr_arrays_up("groth16_prove", z, ct.n_vars);
+  auto dr = to_device_soa(r); auto ds = to_device_soa(s);
+  DeviceBuffer oa(m * sizeof(G1Affine) + 8), ob(m * sizeof(G2Affine) + 8), oc(m * sizeof(G1Affine) + 8), oai(m + 8), obi(m + 8), oci(m + 8);
+  check(sylow_hip_groth16_prove_batch(da.row_ptr.as<uint64_t>(), da.col.as<uint64_t>(), da.val.as<uint64_t>(), da.nnz, db.row_ptr.as<uint64_t>(), db.col.as<uint64_t>(),
+                                      db.val.as<uint64_t>(), db.nnz, dc.row_ptr.as<uint64_t>(), dc.col.as<uint64_t>(), dc.val.as<uint64_t>(), dc.nnz, da.rows, ct.n_vars,
+                                      ct.n_inputs, ct.log_n, alpha.as<uint64_t>(), beta1.as<uint64_t>(), delta1.as<uint64_t>(), beta2.as<uint64_t>(), delta2.as<uint64_t>(),
+                                      aq.as<uint64_t>(), aqi.ptr, b1q.as<uint64_t>(), b1qi.ptr, b2q.as<uint64_t>(), b2qi.ptr, hq.as<uint64_t>(), hqi.ptr, lq.as<uint64_t>(),
+                                      lqi.ptr, dz.as<uint64_t>(), dr.as<uint64_t>(), ds.as<uint64_t>(), m, oa.as<uint64_t>(), oai.as<uint8_t>(), ob.as<uint64_t>(),
+                                      obi.as<uint8_t>(), oc.as<uint64_t>(), oci.as<uint8_t>(), nullptr), "sylow_hip_groth16_prove_batch");
+  Groth16Proofs out;
+  fetch_flags(&out.a_inf, oai, m); fetch_flags(&out.b_inf, obi, m); fetch_flags(&out.c_inf, oci, m);
+  out.a = from_device_soa<G1Affine>(oa, m); out.b = from_device_soa<G2Affine>(ob, m); out.c = from_device_soa<G1Affine>(oc, m);
+  return out;
+}
+
 // ---- runtime knobs of the library (no reference counterpart: the reference is one element on one thread) -----------------------------------
 // Route selectors and thresholds (SYLOW_HIP_OPT_*): process-wide, results identical under every setting; value < 0 restores the default.
 inline void set_option(int32_t option, int64_t value) { check(sylow_hip_set_option(option, value), "sylow_hip_set_option"); }

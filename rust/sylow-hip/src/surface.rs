@@ -1040,6 +1040,112 @@ pub fn fr_ntt_tuned(dev: &Device, a: &KzgPolys, inverse: bool, shift: Option<&Fr
     device::check(unsafe { ffi::sylow_hip_fr_ntt_batch_tuned(a.words.as_ptr(), log_n, a.m, inverse as i32, psh, stages, out.as_mut_ptr(), dev.stream) })?;
     Ok(KzgPolys { words: out, len: a.len, m: a.m })
 }
+/// A sparse matrix over Fr on the device, in CSR: `row_ptr` [rows + 1], `col` [nnz], `val` [4][nnz].
+pub struct CsrMatrix {
+    pub row_ptr: DeviceBuf<u64>,
+    pub col: DeviceBuf<u64>,
+    pub val: DeviceBuf<u64>,
+    pub rows: usize,
+    pub nnz: usize,
+}
+impl CsrMatrix {
+    /// `rows[i]` = the (column, value) entries of row i
+    pub fn upload(dev: &Device, rows: &[Vec<(u64, Fr)>]) -> Result<Self, HipError> {
+        let mut row_ptr = vec![0u64];
+        let (mut col, mut val) = (Vec::new(), Vec::new());
+        for row in rows {
+            for (c, v) in row {
+                col.push(*c);
+                val.push(*v);
+            }
+            row_ptr.push(col.len() as u64);
+        }
+        let nnz = col.len();
+        Ok(CsrMatrix { row_ptr: dev.upload(&row_ptr)?, col: dev.upload(&col)?, val: dev.upload_soa::<4>(&fr_words(&val))?, rows: rows.len(), nnz })
+    }
+}
+/// out_j = M w_j over Fr for m vectors `w` of n_cols elements in the layout of `KzgPolys`, padded with zero rows to `n_out` >= M.rows
+/// (`sylow_hip_fr_spmv_batch`).  An entry whose column is n_cols or more contributes zero; no read leaves the arrays.
+pub fn fr_spmv(dev: &Device, mat: &CsrMatrix, w: &KzgPolys, n_out: usize) -> Result<KzgPolys, HipError> {
+    assert!(n_out >= mat.rows && n_out >= 1);
+    let (n_cols, m) = (w.len, w.m);
+    let out = dev.alloc::<u64>(4 * n_out * m)?;
+    // SAFETY: rows + 1 offsets, nnz columns and values, m vectors of n_cols elements, m arrays of n_out elements out.
+    device::check(unsafe {
+        ffi::sylow_hip_fr_spmv_batch(mat.row_ptr.as_ptr(), mat.col.as_ptr(), mat.val.as_ptr(), mat.rows, mat.nnz, w.words.as_ptr(), n_cols, m, n_out, out.as_mut_ptr(), dev.stream)
+    })?;
+    Ok(KzgPolys { words: out, len: n_out, m })
+}
+/// The same with 2^lanes_log lanes per row pinned (`sylow_hip_fr_spmv_batch_tuned`): 0..=6, negative = the default.  The values do not depend on it.
+pub fn fr_spmv_tuned(dev: &Device, mat: &CsrMatrix, w: &KzgPolys, n_out: usize, lanes_log: i32) -> Result<KzgPolys, HipError> {
+    assert!(n_out >= mat.rows && n_out >= 1);
+    let (n_cols, m) = (w.len, w.m);
+    let out = dev.alloc::<u64>(4 * n_out * m)?;
+    // SAFETY: as fr_spmv.
+    device::check(unsafe {
+        ffi::sylow_hip_fr_spmv_batch_tuned(mat.row_ptr.as_ptr(), mat.col.as_ptr(), mat.val.as_ptr(), mat.rows, mat.nnz, w.words.as_ptr(), n_cols, m, n_out, lanes_log, out.as_mut_ptr(), dev.stream)
+    })?;
+    Ok(KzgPolys { words: out, len: n_out, m })
+}
+/// h = the coefficients of the polynomial of degree < n that equals (a b - c) / (X^n - 1) on the coset 5 <w_n>, for the values a, b, c of three
+/// polynomials on the domain of n = 2^log_n points, m arrays each (`sylow_hip_groth16_quotient_batch`); h[n - 1] = 0 where a_i b_i = c_i everywhere.
+pub fn groth16_quotient(dev: &Device, a: &KzgPolys, b: &KzgPolys, c: &KzgPolys) -> Result<KzgPolys, HipError> {
+    assert!(a.len == b.len && a.len == c.len && a.m == b.m && a.m == c.m);
+    let log_n = radix2_log(a.len);
+    let h = dev.alloc::<u64>(4 * (1 << log_n) * a.m)?;
+    // SAFETY: m arrays of 2^log_n elements each in a, b, c and out.
+    device::check(unsafe { ffi::sylow_hip_groth16_quotient_batch(a.words.as_ptr(), b.words.as_ptr(), c.words.as_ptr(), log_n, a.m, h.as_mut_ptr(), dev.stream) })?;
+    Ok(KzgPolys { words: h, len: a.len, m: a.m })
+}
+/// An R1CS for the prover: the CSR matrices a, b, c (n_cons rows, n_vars columns each); variable 0 is the constant 1, variables
+/// 1..=n_inputs are public; the domain has 2^log_n >= n_cons points.
+pub struct Groth16Circuit {
+    pub a: CsrMatrix,
+    pub b: CsrMatrix,
+    pub c: CsrMatrix,
+    pub n_vars: usize,
+    pub n_inputs: usize,
+    pub log_n: i32,
+}
+/// A Groth16 proving key on the device, arkworks' names: a_query, b_g1_query, b_g2_query hold n_vars points, h_query 2^log_n - 1,
+/// l_query n_vars - n_inputs - 1; a query entry may be flagged as the identity.
+pub struct Groth16Pk {
+    pub alpha_g1: DeviceG1,
+    pub beta_g1: DeviceG1,
+    pub delta_g1: DeviceG1,
+    pub beta_g2: DeviceG2,
+    pub delta_g2: DeviceG2,
+    pub a_query: DeviceG1,
+    pub b_g1_query: DeviceG1,
+    pub b_g2_query: DeviceG2,
+    pub h_query: DeviceG1,
+    pub l_query: DeviceG1,
+}
+/// m proofs (A, B, C) for the witnesses `z` (m arrays of n_vars elements) under one key with the caller's randomness r, s
+/// (`sylow_hip_groth16_prove_batch`): what `groth16_verify` takes.  Neither z_0 = 1 nor the constraints are checked.
+pub fn groth16_prove(dev: &Device, pk: &Groth16Pk, ct: &Groth16Circuit, z: &KzgPolys, r: &[Fr], s: &[Fr]) -> Result<(DeviceG1, DeviceG2, DeviceG1), HipError> {
+    let m = z.m;
+    assert!(z.len == ct.n_vars && r.len() == m && s.len() == m && ct.n_inputs < ct.n_vars);
+    assert!(ct.a.rows == ct.b.rows && ct.a.rows == ct.c.rows && ct.a.rows <= 1 << ct.log_n);
+    assert!(pk.alpha_g1.n == 1 && pk.beta_g1.n == 1 && pk.delta_g1.n == 1 && pk.beta_g2.n == 1 && pk.delta_g2.n == 1);
+    assert!(pk.a_query.n == ct.n_vars && pk.b_g1_query.n == ct.n_vars && pk.b_g2_query.n == ct.n_vars);
+    assert!(pk.h_query.n == (1 << ct.log_n) - 1 && pk.l_query.n == ct.n_vars - ct.n_inputs - 1);
+    let (dr, ds) = (dev.upload_soa::<4>(&fr_words(r))?, dev.upload_soa::<4>(&fr_words(s))?);
+    let a = DeviceG1 { xy: dev.alloc::<u64>(8 * m)?, inf: dev.alloc::<u8>(m)?, n: m };
+    let b = DeviceG2 { xy: dev.alloc::<u64>(16 * m)?, inf: dev.alloc::<u8>(m)?, n: m };
+    let c = DeviceG1 { xy: dev.alloc::<u64>(8 * m)?, inf: dev.alloc::<u8>(m)?, n: m };
+    // SAFETY: three CSR matrices of n_cons rows, the key's arrays of the lengths asserted above, m witnesses, 4 * m words of r and of s,
+    // m points and flags out for each of A, B, C.
+    device::check(unsafe {
+        ffi::sylow_hip_groth16_prove_batch(ct.a.row_ptr.as_ptr(), ct.a.col.as_ptr(), ct.a.val.as_ptr(), ct.a.nnz, ct.b.row_ptr.as_ptr(), ct.b.col.as_ptr(), ct.b.val.as_ptr(), ct.b.nnz,
+            ct.c.row_ptr.as_ptr(), ct.c.col.as_ptr(), ct.c.val.as_ptr(), ct.c.nnz, ct.a.rows, ct.n_vars, ct.n_inputs, ct.log_n,
+            pk.alpha_g1.xy.as_ptr(), pk.beta_g1.xy.as_ptr(), pk.delta_g1.xy.as_ptr(), pk.beta_g2.xy.as_ptr(), pk.delta_g2.xy.as_ptr(),
+            pk.a_query.xy.as_ptr(), pk.a_query.inf.as_ptr(), pk.b_g1_query.xy.as_ptr(), pk.b_g1_query.inf.as_ptr(), pk.b_g2_query.xy.as_ptr(), pk.b_g2_query.inf.as_ptr(),
+            pk.h_query.xy.as_ptr(), pk.h_query.inf.as_ptr(), pk.l_query.xy.as_ptr(), pk.l_query.inf.as_ptr(), z.words.as_ptr(), dr.as_ptr(), ds.as_ptr(), m,
+            a.xy.as_mut_ptr(), a.inf.as_mut_ptr(), b.xy.as_mut_ptr(), b.inf.as_mut_ptr(), c.xy.as_mut_ptr(), c.inf.as_mut_ptr(), dev.stream)
+    })?;
+    Ok((a, b, c))
+}
 /// AND of a device-resident flag vector (one rank; `all_valid` in lib.rs adds the reduce over ranks).
 pub fn flags_all(dev: &Device, flags: &DeviceBuf<u8>) -> Result<bool, HipError> {
     let out = dev.alloc::<i32>(1)?;

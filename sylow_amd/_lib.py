@@ -164,6 +164,11 @@ SIGNATURES = {
     "sylow_hip_kzg_commit_evals_batch": [c_u64p, c_u64p, c_i32, c_sz, c_u64p, c_u8p, c_vp],
     "sylow_hip_fr_ntt_batch": [c_u64p, c_i32, c_sz, c_i32, c_u64p, c_u64p, c_vp],
     "sylow_hip_fr_ntt_batch_tuned": [c_u64p, c_i32, c_sz, c_i32, c_u64p, c_i32, c_u64p, c_vp],
+    "sylow_hip_fr_spmv_batch": [c_u64p, c_u64p, c_u64p, c_sz, c_sz, c_u64p, c_sz, c_sz, c_sz, c_u64p, c_vp],
+    "sylow_hip_fr_spmv_batch_tuned": [c_u64p, c_u64p, c_u64p, c_sz, c_sz, c_u64p, c_sz, c_sz, c_sz, c_i32, c_u64p, c_vp],
+    "sylow_hip_groth16_quotient_batch": [c_u64p, c_u64p, c_u64p, c_i32, c_sz, c_u64p, c_vp],
+    "sylow_hip_groth16_prove_batch": [c_u64p, c_u64p, c_u64p, c_sz] * 3 + [c_sz, c_sz, c_sz, c_i32] + [c_u64p] * 5 + [c_u64p, c_u8p] * 5
+                                     + [c_u64p, c_u64p, c_u64p, c_sz] + [c_u64p, c_u8p] * 3 + [c_vp],
     "sylow_hip_g1_msm": [c_u64p, c_u8p, c_u64p, c_sz, c_u64p, c_u8p, c_vp],
     "sylow_hip_g1_msm_tuned": [c_u64p, c_u8p, c_u64p, c_sz, c_i32, ctypes.c_int64, c_u64p, c_u8p, c_vp],
     "sylow_hip_g2_sum_batch": [c_u64p, c_u8p, c_sz, c_u64p, c_u8p, c_vp],

@@ -545,6 +545,65 @@ def groth16_verify(vk: Groth16VerifyingKey, a: G1Affine, b: G2Affine, c: G1Affin
     return engine().groth16_verify(vk.arrays(), a.xy, b.xy, c.xy, x, a.infinity, b.infinity, c.infinity).astype(bool)
 
 
+class Groth16ProvingKey:
+    """A Groth16 proving key on BN254 under arkworks' names: the single points alpha_g1, beta_g1, delta_g1 (G1) and beta_g2, delta_g2 (G2), and
+    the queries a_query, b_g1_query [n_vars] (G1), b_g2_query [n_vars] (G2), h_query [n - 1] (G1) and l_query [n_vars - l - 1] (G1).  A query
+    entry may be the identity (a variable absent from A or B).  A plain holder: nothing is cached on the device between calls."""
+
+    def __init__(self, alpha_g1: G1Affine, beta_g1: G1Affine, delta_g1: G1Affine, beta_g2: G2Affine, delta_g2: G2Affine, a_query: G1Affine,
+                 b_g1_query: G1Affine, b_g2_query: G2Affine, h_query: G1Affine, l_query: G1Affine):
+        singles = (alpha_g1, beta_g1, delta_g1, beta_g2, delta_g2)
+        if any(len(p) != 1 or p.infinity.any() for p in singles):
+            raise ValueError("Groth16ProvingKey: alpha_g1, beta_g1, delta_g1, beta_g2, delta_g2 are single points, not the identity")
+        if not len(a_query) == len(b_g1_query) == len(b_g2_query):
+            raise ValueError("Groth16ProvingKey: a_query, b_g1_query and b_g2_query hold one point per variable")
+        self.alpha_g1, self.beta_g1, self.delta_g1, self.beta_g2, self.delta_g2 = singles
+        self.a_query, self.b_g1_query, self.b_g2_query, self.h_query, self.l_query = a_query, b_g1_query, b_g2_query, h_query, l_query
+
+    def arrays(self):
+        out = {k: getattr(self, k).xy for k in ("alpha_g1", "beta_g1", "delta_g1", "beta_g2", "delta_g2")}
+        out.update({k: (getattr(self, k).xy, getattr(self, k).infinity) for k in ("a_query", "b_g1_query", "b_g2_query", "h_query", "l_query")})
+        return out
+
+
+class Groth16Circuit:
+    """An R1CS over Fr for the prover: the matrices a, b, c in CSR -- each (row_ptr [n_cons + 1], col [nnz], val [nnz, 4] words or Python ints)
+    -- over n_vars variables, of which variable 0 is the constant 1 and variables 1 .. n_inputs are public, on the domain of 2^log_n >=
+    n_cons points."""
+
+    def __init__(self, a, b, c, n_vars: int, n_inputs: int, log_n: int):
+        self.mats = tuple(self._csr(m) for m in (a, b, c))
+        self.n_vars, self.n_inputs, self.log_n = int(n_vars), int(n_inputs), int(log_n)
+        self.n_cons = len(self.mats[0][0]) - 1
+        if any(len(m[0]) - 1 != self.n_cons for m in self.mats):
+            raise ValueError("Groth16Circuit: a, b and c have one row per constraint")
+        if not (0 <= self.log_n <= 28 and self.n_cons <= 1 << self.log_n and 0 <= self.n_inputs < self.n_vars):
+            raise ValueError("Groth16Circuit: n_cons <= 2^log_n <= 2^28 and n_inputs < n_vars")
+
+    @staticmethod
+    def _csr(m):
+        row_ptr, col, val = m
+        v = np.asarray(val)
+        if v.dtype != np.uint64:
+            v = fp([int(x) for x in np.asarray(val, dtype=object).reshape(-1)])
+        return (np.asarray([int(x) for x in row_ptr], dtype=np.uint64), np.asarray([int(x) for x in col], dtype=np.uint64), v.reshape(-1, 4))
+
+
+def groth16_prove(pk: Groth16ProvingKey, circuit: Groth16Circuit, witnesses, r, s):
+    """(A: G1Affine, B: G2Affine, C: G1Affine), one proof per witness, for witnesses [m, n_vars, 4] words (or m lists of Python ints) and the
+    caller's randomness r, s ([m, 4] words or Python ints) -- any 256-bit values, taken mod r (sylow_hip_groth16_prove_batch).  The three
+    points are what groth16_verify takes, with inputs = witnesses[:, 1 : n_inputs + 1].  Neither z_0 = 1 nor the constraints are checked: an
+    unsatisfied witness yields a proof the verifier rejects."""
+    z = _fr_arrays(witnesses)
+    if z.ndim != 3 or z.shape[1] != circuit.n_vars:
+        raise ValueError("groth16_prove: witnesses hold one value per variable")
+    if len(pk.a_query) != circuit.n_vars or len(pk.h_query) != (1 << circuit.log_n) - 1 or len(pk.l_query) != circuit.n_vars - circuit.n_inputs - 1:
+        raise ValueError("groth16_prove: the proving key does not fit the circuit")
+    (a, ai), (b, bi), (c, ci) = engine().groth16_prove(circuit.mats, circuit.n_vars, circuit.n_inputs, circuit.log_n, pk.arrays(), z,
+                                                       KzgVerifier._words(r), KzgVerifier._words(s))
+    return G1Affine(a, ai), G2Affine(b, bi), G1Affine(c, ci)
+
+
 class KzgVerifier:
     """The verifier's half of a BN254 KZG SRS: tau_g2 = tau G2gen (one point of G2 proper, not the identity) and its line table, built on
     first use and kept on the device.  An opening is (C, z, y, pi) and claims f(z) = y for the polynomial committed in C; `openings` below is

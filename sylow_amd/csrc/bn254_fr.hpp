@@ -47,25 +47,14 @@ BN_DEV Fp fr_neg(const Fp& a) {
 }
 BN_DEV Fp fr_sub(const Fp& a, const Fp& b) { return fr_add(a, fr_neg(b)); }
 
-// a*b mod r, any 256-bit operands: Barrett exactly as fp_mulmod_plain (HAC 14.42, b = 2^32, k = 8; the dropped low
-// partial products cost at most one unit of the quotient, so the remainder before correction is < 4r)
-BN_DEV Fp fr_mulmod_inline(const Fp& a, const Fp& b) {
+// T mod r for ANY T < 2^512 in 16 limbs: Barrett exactly as fp_mulmod_plain (HAC 14.42, b = 2^32, k = 8, valid for every x < b^(2k); the
+// dropped low partial products cost at most one unit of the quotient, so the remainder before correction is < 4r)
+BN_DEV Fp fr_reduce_wide(const u32 (&T)[16]) {
   const u32 p[8] = {BN_FR_R};
   const u32 mu[9] = {BN_FR_MU};
-  u32 T[16];
   u64 acc = 0;
   u32 ovf = 0;
-#pragma unroll
-  for (int k = 0; k < 15; ++k) {
-#pragma unroll
-    for (int i = (k > 7 ? k - 7 : 0); i <= (k < 7 ? k : 7); ++i) mac(acc, ovf, a.v[i], b.v[k - i]);
-    T[k] = (u32)acc;
-    acc = (acc >> 32) | ((u64)ovf << 32);
-    ovf = 0;
-  }
-  T[15] = (u32)acc;
   u32 q3[9];
-  acc = 0; ovf = 0;
 #pragma unroll
   for (int k = 7; k < 18; ++k) {
 #pragma unroll
@@ -91,6 +80,22 @@ BN_DEV Fp fr_mulmod_inline(const Fp& a, const Fp& b) {
   cond_sub_const(r, BN_FR_2R);
   cond_sub_const(r, BN_FR_R);
   return fp_from_limbs(r[0], r[1], r[2], r[3], r[4], r[5], r[6], r[7]);
+}
+// a*b mod r, any 256-bit operands: the 16-limb product, then fr_reduce_wide
+BN_DEV Fp fr_mulmod_inline(const Fp& a, const Fp& b) {
+  u32 T[16];
+  u64 acc = 0;
+  u32 ovf = 0;
+#pragma unroll
+  for (int k = 0; k < 15; ++k) {
+#pragma unroll
+    for (int i = (k > 7 ? k - 7 : 0); i <= (k < 7 ? k : 7); ++i) mac(acc, ovf, a.v[i], b.v[k - i]);
+    T[k] = (u32)acc;
+    acc = (acc >> 32) | ((u64)ovf << 32);
+    ovf = 0;
+  }
+  T[15] = (u32)acc;
+  return fr_reduce_wide(T);
 }
 BN_NOINLINE Fp fr_mul(Fp a, Fp b) { return fr_mulmod_inline(a, b); }
 

@@ -1094,6 +1094,81 @@ class Engine:
         out = np.ascontiguousarray(dout.download()[:m].transpose(0, 2, 1))
         return out[0] if one else out
 
+    # ---- Groth16, the prover's side.  A sparse matrix is CSR: (row_ptr [rows + 1], col [nnz], val [nnz, 4]); Fr batches are [m, n, 4] on the
+    # host and [m][4][n] on the device; any 256-bit words, taken mod r ----
+    def _csr_up(self, csr):
+        row_ptr, col, val = csr
+        row_ptr = np.ascontiguousarray(row_ptr, dtype=np.uint64).reshape(-1)
+        col, val = np.ascontiguousarray(col, dtype=np.uint64).reshape(-1), _aos(val, 4)
+        nnz = col.shape[0]
+        assert row_ptr.shape[0] >= 1 and val.shape[0] == nnz
+        return self.to_device(row_ptr), (self.to_device(col) if nnz else None), (self.to_device_soa(val, 4) if nnz else None), row_ptr.shape[0] - 1, nnz
+
+    def fr_spmv(self, csr, w, n_out=None, lanes_log=-1):
+        """out_j = M w_j for the CSR matrix `csr` and the vectors w [m, n_cols, 4] (or [n_cols, 4]: one vector), padded with zero rows to n_out
+        (None: rows) (sylow_hip_fr_spmv_batch).  lanes_log >= 0 pins 2^lanes_log lanes per row (sylow_hip_fr_spmv_batch_tuned); the values do
+        not depend on it.  An entry whose column is n_cols or more contributes zero.  Canonical words [m, n_out, 4] (or [n_out, 4])."""
+        a = np.ascontiguousarray(w, dtype=np.uint64)
+        one = a.ndim == 2
+        a = a[None] if one else a
+        assert a.ndim == 3 and a.shape[2] == 4, a.shape
+        m, n_cols = a.shape[0], a.shape[1]
+        drp, dcol, dval, rows, nnz = self._csr_up(csr)
+        n_out = rows if n_out is None else int(n_out)
+        dw = self._kzg_polys_up(a) if m and n_cols else None
+        dout = self.empty((max(m, 1), 4, max(n_out, 1)))
+        if lanes_log < 0:
+            self._call("sylow_hip_fr_spmv_batch", drp.ptr, self._ptr(dcol), self._ptr(dval), rows, nnz, self._ptr(dw), n_cols, m, n_out, dout.ptr)
+        else:
+            self._call("sylow_hip_fr_spmv_batch_tuned", drp.ptr, self._ptr(dcol), self._ptr(dval), rows, nnz, self._ptr(dw), n_cols, m, n_out, int(lanes_log), dout.ptr)
+        out = np.ascontiguousarray(dout.download()[:m, :, :n_out].transpose(0, 2, 1))
+        return out[0] if one else out
+
+    def groth16_quotient(self, a, b, c):
+        """h = the coefficients of the polynomial of degree < n that equals (a b - c) / (X^n - 1) on the coset 5 <w_n>, for a, b, c [m, n, 4]:
+        the values of three polynomials on the domain of n = 2^log_n points (sylow_hip_groth16_quotient_batch).  Canonical words [m, n, 4];
+        h[n - 1] = 0 where a_i b_i = c_i on the whole domain."""
+        a, b, c = (self._kzg_polys(x) for x in (a, b, c))
+        m, n = a.shape[0], a.shape[1]
+        log_n = n.bit_length() - 1
+        assert n == 1 << log_n and b.shape == a.shape and c.shape == a.shape, (a.shape, b.shape, c.shape)
+        da, db, dc = (self._kzg_polys_up(x) for x in (a, b, c))
+        dh = self.empty((max(m, 1), 4, n))
+        self._call("sylow_hip_groth16_quotient_batch", self._ptr(da), self._ptr(db), self._ptr(dc), log_n, m, dh.ptr)
+        return np.ascontiguousarray(dh.download()[:m].transpose(0, 2, 1))
+
+    def groth16_prove(self, mats, n_vars, n_inputs, log_n, pk, z, r, s):
+        """m proofs for the witnesses z [m, n_vars, 4] of one circuit under one proving key with the caller's randomness r, s [m, 4]
+        (sylow_hip_groth16_prove_batch).  mats: the CSR matrices (A, B, C), n_cons rows each; pk: a mapping with alpha_g1, beta_g1, delta_g1
+        [1, 8], beta_g2, delta_g2 [1, 16] and the queries a_query, b_g1_query, b_g2_query, h_query, l_query as (words, flags or None).
+        Returns ((A [m, 8], flags), (B [m, 16], flags), (C [m, 8], flags)).  Neither z_0 = 1 nor the constraints are checked."""
+        z, r, s = np.ascontiguousarray(z, dtype=np.uint64), _aos(r, 4), _aos(s, 4)
+        assert z.ndim == 3 and z.shape[2] == 4, z.shape
+        m = z.shape[0]
+        assert r.shape[0] == m and s.shape[0] == m and z.shape[1] == n_vars
+        up = [self._csr_up(x) for x in mats]
+        n_cons = up[0][3]
+        assert all(u[3] == n_cons for u in up)
+        csr_args = [v for u in up for v in (u[0].ptr, self._ptr(u[1]), self._ptr(u[2]), u[4])]
+        single = [self.to_device_soa(_aos(pk[k], w), w) for k, w in (("alpha_g1", 8), ("beta_g1", 8), ("delta_g1", 8), ("beta_g2", 16), ("delta_g2", 16))]
+        held, query_args = [], []
+        for k, w in (("a_query", 8), ("b_g1_query", 8), ("b_g2_query", 16), ("h_query", 8), ("l_query", 8)):
+            xy, inf = pk[k]
+            xy = _aos(xy, w)
+            dxy = self.to_device_soa(xy, w) if xy.shape[0] else None
+            dinf = self._flags(inf, xy.shape[0]) if xy.shape[0] else None
+            held += [dxy, dinf]
+            query_args += [self._ptr(dxy), self._ptr(dinf)]
+        dz = self._kzg_polys_up(z)
+        dr, ds = (self.to_device_soa(x, 4) if m else None for x in (r, s))
+        mm = max(m, 1)
+        da, dai, db, dbi, dc, dci = (self.empty((8, mm)), self.empty((mm,), np.uint8), self.empty((16, mm)), self.empty((mm,), np.uint8),
+                                     self.empty((8, mm)), self.empty((mm,), np.uint8))
+        self._call("sylow_hip_groth16_prove_batch", *csr_args, n_cons, int(n_vars), int(n_inputs), int(log_n), *[d.ptr for d in single], *query_args,
+                   self._ptr(dz), self._ptr(dr), self._ptr(ds), m, da.ptr, dai.ptr, db.ptr, dbi.ptr, dc.ptr, dci.ptr)
+        return ((self.from_device_soa(da)[:m], dai.download()[:m]), (self.from_device_soa(db)[:m], dbi.download()[:m]),
+                (self.from_device_soa(dc)[:m], dci.download()[:m]))
+
     def bls_aggregate_partial(self, pk_xy, msgs, sig_xy, weights=None, pk_inf=None, sig_inf=None):
         """One shard's raw Miller product of the (weighted) aggregate check, [1, 48] words: the input of fp12_product_final_exp."""
         pk_xy, sig_xy = _aos(pk_xy, 16), _aos(sig_xy, 8)

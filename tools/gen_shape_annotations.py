@@ -136,6 +136,15 @@ S["kzg_open_batch"] = "srs_g1_xy=u64[8*len] " + POLYS + " z=u64[4*m] y_out=u64[4
 EVALS = "u64[4*2**log_n*m]"               # m arrays of n = 2^log_n Fr elements
 S["fr_ntt_batch"] = S["fr_ntt_batch_tuned"] = f"in={EVALS} shift=u64[4]? out={EVALS}"
 S["kzg_commit_evals_batch"] = f"srs_g1_xy=u64[8*2**log_n] evals={EVALS} out_xy=u64[8*m] out_inf=u8[m]"
+CSR = lambda x, rows, nnz: f"{x}row_ptr=u64[{rows}+1] {x}col=u64[{nnz}]? {x}val=u64[4*{nnz}]?"      # col / val may be NULL when nnz = 0
+S["fr_spmv_batch"] = S["fr_spmv_batch_tuned"] = CSR("", "rows", "nnz") + " w=u64[4*n_cols*m]? out=u64[4*n_out*m]"
+S["groth16_quotient_batch"] = f"a={EVALS} b={EVALS} c={EVALS} h_out={EVALS}"
+# h_query holds 2^log_n - 1 points and l_query n_vars - n_inputs - 1: the grammar has no subtraction, so their lengths are [*]
+S["groth16_prove_batch"] = (CSR("a_", "n_cons", "a_nnz") + " " + CSR("b_", "n_cons", "b_nnz") + " " + CSR("c_", "n_cons", "c_nnz")
+                            + " alpha_g1=u64[8] beta_g1=u64[8] delta_g1=u64[8] beta_g2=u64[16] delta_g2=u64[16]"
+                            + " a_query=u64[8*n_vars] a_query_inf=u8[n_vars]? b_g1_query=u64[8*n_vars] b_g1_query_inf=u8[n_vars]?"
+                            + " b_g2_query=u64[16*n_vars] b_g2_query_inf=u8[n_vars]? h_query=u64[*]? h_query_inf=u8[*]? l_query=u64[*]? l_query_inf=u8[*]?"
+                            + " z=u64[4*n_vars*m] r=u64[4*m] s=u64[4*m] a_xy=u64[8*m] a_inf=u8[m] b_xy=u64[16*m] b_inf=u8[m] c_xy=u64[8*m] c_inf=u8[m]")
 S["pairing_host"] = "p_aos=u64[8*n] p_inf=u8[n]? q_aos=u64[16*n] q_inf=u8[n]? gt_aos=u64[48*n]"
 S["bls_verify_host"] = "pk_aos=u64[16*n] pk_inf=u8[n]? msgs=u8[*]? msg_offsets=u64[n+1] sig_aos=u64[8*n] sig_inf=u8[n]? ok=u8[n]"
 S["pairing_host_bytes"] = "p_be=u8[64*n] q_be=u8[128*n] gt_aos=u64[48*n] status_p=u8[n] status_q=u8[n]"
