@@ -197,6 +197,18 @@ int32_t sylow_hip_fr_neg_batch(const uint64_t* a, uint64_t* out, size_t n, void*
 /* @shape a=u64[4*n] out=u64[4*n] */
 int32_t sylow_hip_fr_inv_batch(const uint64_t* a, uint64_t* out, size_t n, void* stream);
 
+/* ---- Fr: inverses that share one inversion (kzg_evals.hip; geometry in kzg_evals_plan.hpp) ------------------------------------------------
+ * out_i = a_i^-1 mod r by Montgomery's trick: a [4][n] and out [4][n] as above, any 256-bit words taken mod r, canonical words out,
+ * inv(0) = 0 -- an element = 0 mod r yields 0 and does not disturb its neighbours (it enters the product chain as 1).  The words are
+ * bit-equal to what sylow_hip_fr_inv_batch writes (the inverse is unique); that call pays a power a^(r-2), about 380 products, per element,
+ * this one about 5 products per element and ONE inversion per chunk of 2048 elements: a lane owns 8 consecutive elements, a block a chunk,
+ * prefix and suffix products inside the lane and through LDS, and the chunk's product is inverted on one lane by the binary extended
+ * Euclidean algorithm.  ONE launch, no scratch, stream-ordered, no host synchronisation.  n = 0: OK, nothing launched, nothing written.
+ * SYLOW_HIP_E_ARG, no launch, nothing written, for: NULL a or out; out overlapping a (the two byte ranges of 32 n bytes are compared: the
+ * elements are read twice). */
+/* @shape a=u64[4*n] out=u64[4*n] */
+int32_t sylow_hip_fr_batch_inv(const uint64_t* a, uint64_t* out, size_t n, void* stream);
+
 /* ---- Fr: transforms on radix-2 domains (ntt.hip; geometry, ping-pong and scratch in ntt_plan.hpp) ---------------------------------------
  * r - 1 = 2^28 * odd, so Fr holds the domains of n = 2^log_n points for 0 <= log_n <= 28, generated by w_n = W^(2^(28 - log_n)) with
  * W = 5^((r - 1) / 2^28) = 0x2a3c09f0a58a7e8500e0a7eb8ef62abc402d111e41112ed49bd61b6e725b19f0 (the root arkworks, gnark and snarkjs use).
@@ -850,6 +862,40 @@ int32_t sylow_hip_kzg_open_batch(const uint64_t* srs_g1_xy, const uint64_t* coef
 /* @shape srs_g1_xy=u64[8*2**log_n] evals=u64[4*2**log_n*m] out_xy=u64[8*m] out_inf=u8[m] */
 int32_t sylow_hip_kzg_commit_evals_batch(const uint64_t* srs_g1_xy, const uint64_t* evals, int32_t log_n, size_t m,
                                          uint64_t* out_xy, uint8_t* out_inf, void* stream);
+
+/* ---- KZG, the prover's side, from evaluations: open polynomials held by their VALUES on a radix-2 domain, without leaving that form
+ * (kzg_evals.hip; geometry and scratch in kzg_evals_plan.hpp) -----------------------------------------------------------------------------
+ * Conventions (those of the transform block and of the KZG prover block above):
+ *   polynomials: evals [m][4][n], n = 2^log_n, 0 <= log_n <= 28: evals_ji = f_j(w_n^i) with w_n the root of the transform block, natural
+ *              order; f_j is THE polynomial of degree < n through those values.  z is [4][m].  Every word is taken mod r.
+ *   the SRS:   srs_lagrange_xy [8][n], the affine points L_i(tau) G1gen with L_i the Lagrange basis of the same domain,
+ *              L_i(tau) = (tau^n - 1) w^i / (n (tau - w^i)); supplied by the caller (ceremony files ship it), taken as given, no flag array.
+ *   outputs:   y_out [4][m]; q_out [m][4][n] in the layout of evals; canonical words below r; points as [8][m] affine + [m] flags.
+ *   calls:     stream-ordered, no host synchronisation; scratch leased per call.  m = 0: OK, nothing launched, nothing written.
+ *   errors:    SYLOW_HIP_E_ARG, no launch, nothing written, for: log_n < 0 or > 28; a required pointer NULL; q_out overlapping evals (the two
+ *              byte ranges of 32 n m bytes are compared).
+ * A COMMITMENT from evaluations under a Lagrange-basis SRS needs no entry point of its own: sum_i f_j(w^i) L_i(tau) G1gen = f_j(tau) G1gen is
+ * sylow_hip_kzg_commit_batch(srs_lagrange_xy, evals, n, m, ...) as it stands -- the same point sylow_hip_kzg_commit_evals_batch yields under
+ * the monomial SRS of the same tau. */
+/* y_j = f_j(z_j) and the values on the domain of q_j(X) = (f_j(X) - y_j) / (X - z_j), exact in Fr.  With d_i = z - w^i:
+ *   z outside the domain:   y = (z^n - 1) n^-1 sum_i f_i w^i d_i^-1 (the barycentric formula),   q_i = (y - f_i) d_i^-1;
+ *   z = w^k mod r (however the word was written):   y = f_k,   q_i = (y - f_i) d_i^-1 for i != k,   q_k = -w^-k sum_(i != k) q_i w^i = f_j'(w^k).
+ * A batch may mix rows of both kinds; at log_n = 0, y = f_0 and q_0 = 0 for every z.  Either output may be NULL, not both; q_out = NULL is
+ * barycentric evaluation alone.  The d_i^-1 share one inversion per chunk of 2048 points (the mechanism of sylow_hip_fr_batch_inv; inv(0) = 0
+ * marks the hit, whose q_k one lane repairs after the second sum).  Five launches with q_out (the powers of w_n once per call; d_i^-1 and
+ * the first sum per chunk; y per polynomial; q per chunk; the repair), three without.  Scratch: 32 bytes per (polynomial, chunk) and 8 (40
+ * without y_out) per polynomial, plus 928. */
+/* @shape evals=u64[4*2**log_n*m] z=u64[4*m] q_out=u64[4*2**log_n*m]? y_out=u64[4*m]? */
+int32_t sylow_hip_kzg_quotient_evals_batch(const uint64_t* evals, int32_t log_n, size_t m, const uint64_t* z,
+                                           uint64_t* q_out, uint64_t* y_out, void* stream);
+/* The opening of f_j at z_j from its values: y_j as above and pi_j = sum_i q_j(w^i) srs_lagrange_i = q_j(tau) G1gen -- the quotient's values
+ * into leased scratch (32 n m bytes), then the commitment code of sylow_hip_kzg_commit_batch over them, entered past its mod-r pass since the
+ * words are canonical.  pi_j is flagged as the identity exactly when q_j = 0 (f_j constant).  (C, z, y, pi) with C from
+ * sylow_hip_kzg_commit_batch(srs_lagrange_xy, evals, ...) is a valid row of the verifiers above under tau_g2; the words are those
+ * sylow_hip_kzg_open_batch yields for the interpolated coefficients under the monomial SRS of the same tau. */
+/* @shape srs_lagrange_xy=u64[8*2**log_n] evals=u64[4*2**log_n*m] z=u64[4*m] y_out=u64[4*m] pi_xy=u64[8*m] pi_inf=u8[m] */
+int32_t sylow_hip_kzg_open_evals_batch(const uint64_t* srs_lagrange_xy, const uint64_t* evals, int32_t log_n, size_t m, const uint64_t* z,
+                                       uint64_t* y_out, uint64_t* pi_xy, uint8_t* pi_inf, void* stream);
 
 /* ---- Groth16, the prover's side: R1CS products, the quotient and the proof under ONE proving key (groth16_prove.hip; lanes per row, grids,
  * scratch and chunks in groth16_prove_plan.hpp) ------------------------------------------------------------------------------------------

@@ -201,6 +201,13 @@ inline std::vector<Fp> inv(const std::vector<Fp>& a) {
   check(sylow_hip_fr_inv_batch(da.as<uint64_t>(), dout.as<uint64_t>(), a.size(), nullptr), "sylow_hip_fr_inv_batch");
   return from_device_soa<Fp>(dout, a.size());
 }
+// The same values as inv (inv(0) = 0) by Montgomery's trick (sylow_hip_fr_batch_inv): the elements of a chunk of 2048 share ONE inversion
+inline std::vector<Fp> batch_inv(const std::vector<Fp>& a) {
+  auto da = to_device_soa(a);
+  DeviceBuffer dout(a.size() * sizeof(Fp) + 8);
+  check(sylow_hip_fr_batch_inv(da.as<uint64_t>(), dout.as<uint64_t>(), a.size(), nullptr), "sylow_hip_fr_batch_inv");
+  return from_device_soa<Fp>(dout, a.size());
+}
 // The transform on the domain of n = a.size() = 2^log_n points (sylow_hip_fr_ntt_batch_tuned), natural order in and out.  forward:
 // out_i = sum_k a_k (g w_n^i)^k; inverse: out_k = n^-1 g^-k sum_i a_i w_n^(-ik); shift = the coset shift g (nullptr: 1); stages >= 1 pins the
 // stages of a pass (the values do not depend on it).  Any 256-bit words in, taken mod r; canonical words out.
@@ -600,6 +607,83 @@ class KzgProver {
     return d;
   }
   size_t len_;
+  DeviceBuffer srs_;
+};
+// The prover's half of the SRS for polynomials held in EVALUATION form (sylow_hip.h, "KZG, the prover's side, from evaluations"):
+// srs_lagrange[i] = L_i(tau) G1gen for the Lagrange basis of the domain of n = 2^log_n points, kept on the device.  A polynomial is its
+// values evals[i] = f(w_n^i), natural order -- any 256-bit words, taken mod r.  z may lie inside the domain.
+class KzgEvalProver {
+ public:
+  explicit KzgEvalProver(const std::vector<G1Affine>& srs_lagrange) : n_(srs_lagrange.size()), log_n_(0), srs_(to_device_soa(srs_lagrange)) {
+    while (((size_t)1 << log_n_) < n_) ++log_n_;
+    if (!n_ || n_ != (size_t)1 << log_n_ || log_n_ > 28) throw Error("KzgEvalProver: the SRS holds a power of two of points, at most 2^28");
+  }
+  size_t len() const { return n_; }
+  // C_j = sum_i evals[j][i] srs_lagrange[i] = f_j(tau) G1gen: sylow_hip_kzg_commit_batch over the values as they lie
+  std::vector<G1Affine> commit(const std::vector<std::vector<Fp>>& evals, std::vector<uint8_t>* infinity = nullptr) const {
+    const size_t m = evals.size();
+    DeviceBuffer dc = upload("KzgEvalProver::commit", evals);
+    DeviceBuffer dout(m * sizeof(G1Affine) + 8), dinf(m + 8);
+    check(sylow_hip_kzg_commit_batch(srs_.as<uint64_t>(), dc.as<uint64_t>(), n_, m, dout.as<uint64_t>(), dinf.as<uint8_t>(), nullptr), "sylow_hip_kzg_commit_batch");
+    fetch_flags(infinity, dinf, m);
+    return from_device_soa<G1Affine>(dout, m);
+  }
+  // y_j = f_j(z_j) by the barycentric formula (sylow_hip_kzg_quotient_evals_batch without a quotient buffer)
+  std::vector<Fp> evaluate(const std::vector<std::vector<Fp>>& evals, const std::vector<Fp>& z) const {
+    const size_t m = evals.size();
+    if (z.size() != m) throw Error("KzgEvalProver::evaluate: one point per polynomial");
+    DeviceBuffer dc = upload("KzgEvalProver::evaluate", evals);
+    auto dz = to_device_soa(z);
+    DeviceBuffer dy(m * sizeof(Fp) + 8);
+    check(sylow_hip_kzg_quotient_evals_batch(dc.as<uint64_t>(), log_n_, m, dz.as<uint64_t>(), nullptr, dy.as<uint64_t>(), nullptr), "sylow_hip_kzg_quotient_evals_batch");
+    return from_device_soa<Fp>(dy, m);
+  }
+  // the values on the domain of q_j = (f_j - y_j) / (X - z_j), canonical words, and y_j (sylow_hip_kzg_quotient_evals_batch)
+  std::vector<std::vector<Fp>> quotient(const std::vector<std::vector<Fp>>& evals, const std::vector<Fp>& z, std::vector<Fp>* y = nullptr) const {
+    const size_t m = evals.size();
+    if (z.size() != m) throw Error("KzgEvalProver::quotient: one point per polynomial");
+    DeviceBuffer dc = upload("KzgEvalProver::quotient", evals);
+    auto dz = to_device_soa(z);
+    DeviceBuffer dq(4 * n_ * m * sizeof(uint64_t) + 8), dy(m * sizeof(Fp) + 8);
+    check(sylow_hip_kzg_quotient_evals_batch(dc.as<uint64_t>(), log_n_, m, dz.as<uint64_t>(), dq.as<uint64_t>(), dy.as<uint64_t>(), nullptr),
+          "sylow_hip_kzg_quotient_evals_batch");
+    std::vector<uint64_t> flat(4 * n_ * m);
+    if (m) check(sylow_hip_memcpy_d2h(flat.data(), dq.as<void>(), flat.size() * sizeof(uint64_t), nullptr), "d2h");
+    check(sylow_hip_stream_sync(nullptr), "sync");
+    std::vector<std::vector<Fp>> q(m, std::vector<Fp>(n_));
+    for (size_t j = 0; j < m; ++j) for (size_t k = 0; k < n_; ++k) for (size_t w = 0; w < 4; ++w) q[j][k].w[w] = flat[(j * 4 + w) * n_ + k];
+    if (y) *y = from_device_soa<Fp>(dy, m);
+    return q;
+  }
+  // y_j and pi_j = the commitment to the quotient's values (sylow_hip_kzg_open_evals_batch); a flagged pi_j is the proof for a constant polynomial
+  std::vector<G1Affine> open(const std::vector<std::vector<Fp>>& evals, const std::vector<Fp>& z, std::vector<Fp>* y, std::vector<uint8_t>* infinity = nullptr) const {
+    const size_t m = evals.size();
+    if (z.size() != m) throw Error("KzgEvalProver::open: one point per polynomial");
+    DeviceBuffer dc = upload("KzgEvalProver::open", evals);
+    auto dz = to_device_soa(z);
+    DeviceBuffer dy(m * sizeof(Fp) + 8), dpi(m * sizeof(G1Affine) + 8), dinf(m + 8);
+    check(sylow_hip_kzg_open_evals_batch(srs_.as<uint64_t>(), dc.as<uint64_t>(), log_n_, m, dz.as<uint64_t>(), dy.as<uint64_t>(), dpi.as<uint64_t>(), dinf.as<uint8_t>(),
+                                         nullptr), "sylow_hip_kzg_open_evals_batch");
+    fetch_flags(infinity, dinf, m);
+    if (y) *y = from_device_soa<Fp>(dy, m);
+    return from_device_soa<G1Affine>(dpi, m);
+  }
+
+ private:
+  // the block layout of the prover's calls: word w of value i of polynomial j at (j * 4 + w) * n + i
+  DeviceBuffer upload(const char* who, const std::vector<std::vector<Fp>>& evals) const {
+    const size_t m = evals.size();
+    std::vector<uint64_t> flat(4 * n_ * m);
+    for (size_t j = 0; j < m; ++j) {
+      if (evals[j].size() != n_) throw Error(std::string(who) + ": every polynomial has one value per SRS point");
+      for (size_t k = 0; k < n_; ++k) for (size_t w = 0; w < 4; ++w) flat[(j * 4 + w) * n_ + k] = evals[j][k].w[w];
+    }
+    DeviceBuffer d(flat.size() * sizeof(uint64_t) + 8);
+    if (m) { check(sylow_hip_memcpy_h2d(d.as<void>(), flat.data(), flat.size() * sizeof(uint64_t), nullptr), "h2d"); check(sylow_hip_stream_sync(nullptr), "sync"); }
+    return d;
+  }
+  size_t n_;
+  int32_t log_n_;
   DeviceBuffer srs_;
 };
 // Many signers, ONE message (examples/threshold_signing.rs:92-121): e(sig, G2gen) e(-H(msg), sum_j pubkeys[j]) == identity -- one hash, one G2

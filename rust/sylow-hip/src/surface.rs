@@ -153,6 +153,11 @@ pub fn fr_neg_batch(dev: &Device, a: &[Fr]) -> Result<Vec<[u64; 4]>, HipError> {
 pub fn fr_inv_batch(dev: &Device, a: &[Fr]) -> Result<Vec<[u64; 4]>, HipError> {
     unop::<4>(dev, ffi::sylow_hip_fr_inv_batch, &fr_words(a))
 }
+/// The same words as `fr_inv_batch` (inv(0) = 0) by Montgomery's trick (`sylow_hip_fr_batch_inv`): the elements of a chunk of 2048 share ONE
+/// inversion, about 5 products per element instead of a power per element.  The output is a buffer of its own, as the call requires.
+pub fn fr_batch_inv(dev: &Device, a: &[Fr]) -> Result<Vec<[u64; 4]>, HipError> {
+    unop::<4>(dev, ffi::sylow_hip_fr_batch_inv, &fr_words(a))
+}
 
 // ------------------------------------------------------------------ FieldExtension<D, N, F> (extensions.rs:41-238) and the tower
 /// Component-wise `Add / Sub / Neg` and `scale(Fp)` of `FieldExtension` for degree 2, 6 or 12 (W = 4 * degree words per element).
@@ -1006,6 +1011,48 @@ pub fn kzg_commit_evals(dev: &Device, srs: &DeviceG1, evals: &KzgPolys) -> Resul
         ffi::sylow_hip_kzg_commit_evals_batch(srs.xy.as_ptr(), evals.words.as_ptr(), log_n, evals.m, out.xy.as_mut_ptr(), out.inf.as_mut_ptr(), dev.stream)
     })?;
     Ok(out)
+}
+/// y_j = f_j(z_j) and the values on the domain of q_j = (f_j - y_j) / (X - z_j), from the VALUES evals_ji = f_j(w_n^i) in the layout of
+/// `KzgPolys` (`sylow_hip_kzg_quotient_evals_batch`); z_j inside the domain is the documented 0 / 0 case, q_k = f_j'(w^k).  The quotients'
+/// values in the layout of `evals`, y as [4][m] words.
+pub fn kzg_quotient_evals(dev: &Device, evals: &KzgPolys, z: &[Fr]) -> Result<(KzgPolys, Vec<[u64; 4]>), HipError> {
+    assert!(z.len() == evals.m);
+    let log_n = radix2_log(evals.len);
+    let dz = dev.upload_soa::<4>(&fr_words(z))?;
+    let (q, y) = (dev.alloc::<u64>(4 * evals.len * evals.m)?, dev.alloc::<u64>(4 * evals.m)?);
+    // SAFETY: m arrays of 2^log_n values in and out (distinct buffers), 4 * m words of z and of y.
+    device::check(unsafe { ffi::sylow_hip_kzg_quotient_evals_batch(evals.words.as_ptr(), log_n, evals.m, dz.as_ptr(), q.as_mut_ptr(), y.as_mut_ptr(), dev.stream) })?;
+    let yw = dev.download_aos::<4>(&y, evals.m)?;
+    Ok((KzgPolys { words: q, len: evals.len, m: evals.m }, yw))
+}
+/// y_j = f_j(z_j) alone, by the barycentric formula: the same entry point without a quotient buffer.
+pub fn kzg_evaluate_evals(dev: &Device, evals: &KzgPolys, z: &[Fr]) -> Result<Vec<[u64; 4]>, HipError> {
+    assert!(z.len() == evals.m);
+    let log_n = radix2_log(evals.len);
+    let dz = dev.upload_soa::<4>(&fr_words(z))?;
+    let y = dev.alloc::<u64>(4 * evals.m)?;
+    // SAFETY: as kzg_quotient_evals; a NULL q_out is the documented evaluation-only form.
+    device::check(unsafe {
+        ffi::sylow_hip_kzg_quotient_evals_batch(evals.words.as_ptr(), log_n, evals.m, dz.as_ptr(), std::ptr::null_mut(), y.as_mut_ptr(), dev.stream)
+    })?;
+    Ok(dev.download_aos::<4>(&y, evals.m)?)
+}
+/// The opening of every f_j at z_j from its values, under the LAGRANGE-basis SRS of the same domain, `srs_lagrange.n` = 2^log_n points
+/// L_i(tau) G1gen (`sylow_hip_kzg_open_evals_batch`): (y as [4][m] words, pi); pi_j is the identity exactly when f_j is constant.  The
+/// commitment that goes with it is `kzg_commit(dev, srs_lagrange, evals)`.
+pub fn kzg_open_evals(dev: &Device, srs_lagrange: &DeviceG1, evals: &KzgPolys, z: &[Fr]) -> Result<(Vec<[u64; 4]>, DeviceG1), HipError> {
+    kzg_srs_fits(srs_lagrange, evals);
+    assert!(z.len() == evals.m);
+    let log_n = radix2_log(evals.len);
+    let dz = dev.upload_soa::<4>(&fr_words(z))?;
+    let y = dev.alloc::<u64>(4 * evals.m)?;
+    let pi = DeviceG1 { xy: dev.alloc::<u64>(8 * evals.m)?, inf: dev.alloc::<u8>(evals.m)?, n: evals.m };
+    // SAFETY: 2^log_n SRS points (no flags), m arrays of 2^log_n values, 4 * m words of z and of y, m points and flags out.
+    device::check(unsafe {
+        ffi::sylow_hip_kzg_open_evals_batch(srs_lagrange.xy.as_ptr(), evals.words.as_ptr(), log_n, evals.m, dz.as_ptr(), y.as_mut_ptr(), pi.xy.as_mut_ptr(),
+                                            pi.inf.as_mut_ptr(), dev.stream)
+    })?;
+    Ok((dev.download_aos::<4>(&y, evals.m)?, pi))
 }
 /// log2 of a radix-2 domain's size (at most 2^28 points: r - 1 = 2^28 * odd)
 fn radix2_log(n: usize) -> i32 {

@@ -348,6 +348,7 @@ class Fr:
     def __mul__(self, o): return Fr(engine().fr_mul(self.v, o.v))
     def __neg__(self): return Fr(engine().fr_neg(self.v))
     def inv(self): return Fr(engine().fr_inv(self.v))
+    def batch_inv(self): return Fr(engine().fr_batch_inv(self.v))   # the words of inv() (inv(0) = 0), one shared inversion per 2048 elements
     def __eq__(self, o): return (self.v == o.v).all(axis=1)
 
     @classmethod
@@ -671,6 +672,48 @@ class KzgProver:
         if n & (n - 1):
             raise ValueError("KzgProver.commit_evals: the SRS holds a power of two of points")
         return G1Affine(*engine().kzg_commit_evals(self.srs_g1.xy, self._polys(evals)))
+
+
+class KzgEvalProver:
+    """The prover's half of a BN254 KZG SRS for polynomials held in EVALUATION form: srs_lagrange = (L_i(tau) G1gen) for i = 0 .. n - 1, with L_i
+    the Lagrange basis of the domain <w_n> of n = 2^log_n points (the domain of ntt).  `evals` below is [m, n, 4] words or m lists of n Python
+    ints, evals[j][i] = f_j(w_n^i) -- any 256-bit values, taken mod r; z as for KzgVerifier, inside the domain or not.
+    (commit(evals), z, *open(evals, z)) is the tuple KzgVerifier.verify takes, word for word what KzgProver yields for the interpolated
+    coefficients under the monomial SRS of the same tau."""
+
+    def __init__(self, srs_lagrange: G1Affine):
+        n = len(srs_lagrange)
+        if n < 1 or n & (n - 1) or n > 1 << 28 or srs_lagrange.infinity.any():
+            raise ValueError("KzgEvalProver: srs_lagrange holds a power of two of points, at most 2^28, and no identity")
+        self.srs_lagrange = srs_lagrange
+
+    def _evals(self, evals):
+        a = np.asarray(evals)
+        n = len(self.srs_lagrange)
+        if a.dtype == object or a.ndim == 2:
+            rows = [list(f) for f in evals]
+            a = fp([int(v) for f in rows for v in f]).reshape(len(rows), -1, 4) if rows else np.zeros((0, n, 4), dtype=np.uint64)
+        if a.ndim != 3 or a.shape[1] != n:
+            raise ValueError("KzgEvalProver: every polynomial has one value per SRS point")
+        return a
+
+    def commit(self, evals) -> G1Affine:
+        """C_j = sum_i f_j(w^i) srs_lagrange_i = f_j(tau) G1gen: sylow_hip_kzg_commit_batch over the values as they lie."""
+        return G1Affine(*engine().kzg_commit(self.srs_lagrange.xy, self._evals(evals)))
+
+    def evaluate(self, evals, z) -> np.ndarray:
+        """y [m, 4] words, y_j = f_j(z_j), by the barycentric formula (sylow_hip_kzg_quotient_evals_batch without a quotient buffer)."""
+        return engine().kzg_quotient_evals(self._evals(evals), KzgVerifier._words(z), want_q=False)[1]
+
+    def quotient(self, evals, z):
+        """(q [m, n, 4], y [m, 4]): the values on the domain of (f_j - y_j) / (X - z_j), and y_j (sylow_hip_kzg_quotient_evals_batch)."""
+        return engine().kzg_quotient_evals(self._evals(evals), KzgVerifier._words(z))
+
+    def open(self, evals, z):
+        """(y [m, 4] words, pi: G1Affine) with pi_j the commitment to the quotient's values (sylow_hip_kzg_open_evals_batch); a constant
+        polynomial opens with the identity."""
+        y, pi_xy, pi_inf = engine().kzg_open_evals(self.srs_lagrange.xy, self._evals(evals), KzgVerifier._words(z))
+        return y, G1Affine(pi_xy, pi_inf)
 
 
 def _fr_arrays(values):

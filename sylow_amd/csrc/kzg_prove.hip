@@ -252,6 +252,9 @@ static int32_t commit(const uint64_t* srs, const uint64_t* coeffs, size_t len, s
   return commit_short(srs, coeffs, len, m, plan.polys_per_chunk, out_xy, out_inf, stream);
 }
 }  // namespace kzgp
+int32_t kzgph::commit_canonical(const uint64_t* srs_g1_xy, const uint64_t* coeffs, size_t len, size_t m, uint64_t* out_xy, uint8_t* out_inf, void* stream) {
+  return kzgp::commit(srs_g1_xy, coeffs, len, m, /*canonical=*/true, -1, -1, out_xy, out_inf, stream);
+}
 
 extern "C" {
 int32_t sylow_hip_kzg_quotient_batch(const uint64_t* coeffs, size_t len, size_t m, const uint64_t* z, uint64_t* q_out, uint64_t* y_out, void* stream) {

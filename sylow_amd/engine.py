@@ -219,6 +219,8 @@ class Engine:
     def fr_sqr(self, a): return self._unop("sylow_hip_fr_sqr_batch", 4, a)
     def fr_neg(self, a): return self._unop("sylow_hip_fr_neg_batch", 4, a)
     def fr_inv(self, a): return self._unop("sylow_hip_fr_inv_batch", 4, a)
+    # the same words as fr_inv by Montgomery's trick: ONE inversion per chunk of 2048 elements (sylow_hip_fr_batch_inv)
+    def fr_batch_inv(self, a): return self._unop("sylow_hip_fr_batch_inv", 4, a)
     def fp2_mul(self, a, b): return self._binop("sylow_hip_fp2_mul_batch", 8, a, b)
     def fp2_sqr(self, a): return self._unop("sylow_hip_fp2_sqr_batch", 8, a)
     def fp2_inv(self, a): return self._unop("sylow_hip_fp2_inv_batch", 8, a)
@@ -1072,6 +1074,38 @@ class Engine:
         do, doi = self.empty((8, max(m, 1))), self.empty((max(m, 1),), np.uint8)
         self._call("sylow_hip_kzg_commit_evals_batch", ds.ptr, self._ptr(dc), log_n, m, do.ptr, doi.ptr)
         return self.from_device_soa(do)[:m], doi.download()[:m]
+
+    # ---- KZG from evaluations.  evals [m, n, 4]: evals[j, i] = f_j(w_n^i), n = 2^log_n <= 2^28, any 256-bit words taken mod r;
+    # srs_lagrange [n, 8]: L_i(tau) G1gen for the Lagrange basis of the same domain; z [m, 4] ----
+    def _kzg_evals(self, evals):
+        a = self._kzg_polys(evals)
+        n = a.shape[1]
+        log_n = n.bit_length() - 1
+        assert n == 1 << log_n, n
+        return a, a.shape[0], n, log_n
+
+    def kzg_quotient_evals(self, evals, z, want_q=True, want_y=True):
+        """y_j = f_j(z_j) as [m, 4] and the values on the domain of q_j = (f_j - y_j) / (X - z_j) as [m, n, 4] canonical words
+        (sylow_hip_kzg_quotient_evals_batch; z_j inside the domain: q_j[k] = f_j'(w^k)); an output that is not wanted is None (want_q = False
+        is barycentric evaluation alone)."""
+        (a, m, n, log_n), z = self._kzg_evals(evals), _aos(z, 4)
+        assert z.shape[0] == m and (want_q or want_y)
+        dc, dz = self._kzg_polys_up(a), (self.to_device_soa(z, 4) if m else None)
+        dq = self.empty((max(m, 1), 4, n)) if want_q else None
+        dy = self.empty((4, max(m, 1))) if want_y else None
+        self._call("sylow_hip_kzg_quotient_evals_batch", self._ptr(dc), log_n, m, self._ptr(dz), self._ptr(dq), self._ptr(dy))
+        q = np.ascontiguousarray(dq.download()[:m].transpose(0, 2, 1)) if want_q else None
+        return q, (self.from_device_soa(dy)[:m] if want_y else None)
+
+    def kzg_open_evals(self, srs_lagrange, evals, z):
+        """The opening of every f_j at z_j from its values under the Lagrange-basis SRS (sylow_hip_kzg_open_evals_batch): (y [m, 4], pi [m, 8]
+        affine words, pi flags [m]); pi_j is the identity exactly when f_j is constant."""
+        (a, m, n, log_n), srs, z = self._kzg_evals(evals), _aos(srs_lagrange, 8), _aos(z, 4)
+        assert srs.shape[0] == n and z.shape[0] == m
+        dc, ds, dz = self._kzg_polys_up(a), self.to_device_soa(srs, 8), (self.to_device_soa(z, 4) if m else None)
+        dy, dp, dpi = self.empty((4, max(m, 1))), self.empty((8, max(m, 1))), self.empty((max(m, 1),), np.uint8)
+        self._call("sylow_hip_kzg_open_evals_batch", ds.ptr, self._ptr(dc), log_n, m, self._ptr(dz), dy.ptr, dp.ptr, dpi.ptr)
+        return self.from_device_soa(dy)[:m], self.from_device_soa(dp)[:m], dpi.download()[:m]
 
     # ---- Fr transforms on radix-2 domains.  values [m, n, 4] (or [n, 4]: one array), n = 2^log_n <= 2^28, any 256-bit words taken mod r ----
     def fr_ntt(self, values, inverse=False, shift=None, stages=-1):

@@ -136,6 +136,9 @@ S["kzg_open_batch"] = "srs_g1_xy=u64[8*len] " + POLYS + " z=u64[4*m] y_out=u64[4
 EVALS = "u64[4*2**log_n*m]"               # m arrays of n = 2^log_n Fr elements
 S["fr_ntt_batch"] = S["fr_ntt_batch_tuned"] = f"in={EVALS} shift=u64[4]? out={EVALS}"
 S["kzg_commit_evals_batch"] = f"srs_g1_xy=u64[8*2**log_n] evals={EVALS} out_xy=u64[8*m] out_inf=u8[m]"
+S["fr_batch_inv"] = "a=u64[4*n] out=u64[4*n]"
+S["kzg_quotient_evals_batch"] = f"evals={EVALS} z=u64[4*m] q_out={EVALS}? y_out=u64[4*m]?"
+S["kzg_open_evals_batch"] = f"srs_lagrange_xy=u64[8*2**log_n] evals={EVALS} z=u64[4*m] y_out=u64[4*m] pi_xy=u64[8*m] pi_inf=u8[m]"
 CSR = lambda x, rows, nnz: f"{x}row_ptr=u64[{rows}+1] {x}col=u64[{nnz}]? {x}val=u64[4*{nnz}]?"      # col / val may be NULL when nnz = 0
 S["fr_spmv_batch"] = S["fr_spmv_batch_tuned"] = CSR("", "rows", "nnz") + " w=u64[4*n_cols*m]? out=u64[4*n_out*m]"
 S["groth16_quotient_batch"] = f"a={EVALS} b={EVALS} c={EVALS} h_out={EVALS}"
