@@ -235,6 +235,43 @@ int32_t sylow_hip_fr_ntt_batch(const uint64_t* in, int32_t log_n, size_t m, int3
 int32_t sylow_hip_fr_ntt_batch_tuned(const uint64_t* in, int32_t log_n, size_t m, int32_t inverse, const uint64_t* shift, int32_t stages,
                                      uint64_t* out, void* stream);
 
+/* ---- G1: transforms on radix-2 domains (g1_ntt.hip; butterflies, grids, ping-pong and scratch in g1_ntt_plan.hpp) ----------------------------
+ * The discrete Fourier transform of the block above with G1 POINTS as elements and the same roots w_n as twiddles, natural order in and out:
+ *   forward (inverse = 0):  out_i = sum_k w_n^(ik) P_k
+ *   inverse (inverse = 1):  out_k = n^-1 sum_i w_n^(-ik) P_i
+ * so for P_k = s_k G the output is NTT(s)_i G.  There is NO coset shift: transforms on a coset g <w_n> are out of scope.
+ *   arrays:    p_xy and out_xy are [m][8][n], n = 2^log_n, 0 <= log_n <= 28: m affine SoA arrays one after another, word w of point k of
+ *              array j at (j * 8 + w) * n + k.  p_inf is [m][n] bytes, optional (NULL = nothing flagged); out_inf is [m][n], required.
+ *   points:    taken as given, no on-curve check.  A flagged input is the identity whatever its words hold, and so is the pair (0, 1) that
+ *              every call writes for the identity, with or without its flag ((0, 1) is no point of the curve).  Outputs are the canonical
+ *              affine words of a group element, the identity as (0, 1) + its flag: they do NOT depend on the plan (max_blocks below).
+ *              At log_n = 0 the output is the input point made canonical, in both directions.
+ *   calls:     stream-ordered, no host synchronisation; scratch leased per call: two projective buffers of 96 n m bytes (one at log_n = 1,
+ *              none at 0), the twiddle table of 16 n bytes, and window tables of 1 KB per RESIDENT lane (at most 512 blocks of 256 lanes
+ *              by default: 128 MB, whatever n is).  A lease that does not fit returns SYLOW_HIP_E_HIP.  m = 0: OK, nothing launched,
+ *              nothing written.
+ *   errors:    SYLOW_HIP_E_ARG, no launch, nothing written, for: NULL p_xy, out_xy or out_inf; log_n < 0 or > 28; inverse not 0 or 1;
+ *              out_xy overlapping p_xy (the two byte ranges of 64 n m bytes are compared); out_inf overlapping p_inf (n m bytes);
+ *              max_blocks == 0.
+ * One launch builds the twiddle table (log_n >= 2), one per radix-2 Stockham stage (log_n of them; a butterfly (U, V) -> (U + kV, U - kV) is
+ * one scalar multiplication, skipped where k = 1: all of the first stage, one butterfly in 2^p of stage p), and ONE closing launch scales
+ * by n^-1 (inverse) and converts to affine, one Fp inversion per point. */
+/* @shape p_xy=u64[8*2**log_n*m] p_inf=u8[2**log_n*m]? out_xy=u64[8*2**log_n*m] out_inf=u8[2**log_n*m] */
+int32_t sylow_hip_g1_ntt_batch(const uint64_t* p_xy, const uint8_t* p_inf, int32_t log_n, size_t m, int32_t inverse,
+                               uint64_t* out_xy, uint8_t* out_inf, void* stream);
+/* The same with the blocks of a stage launch capped: max_blocks >= 1 (at most 4096; more is 4096), < 0 = the default (512).  Lanes walk the
+ * butterflies beyond the grid with a grid stride, and the window tables are max_blocks * 256 KB.  The values do not depend on it. */
+/* @shape p_xy=u64[8*2**log_n*m] p_inf=u8[2**log_n*m]? out_xy=u64[8*2**log_n*m] out_inf=u8[2**log_n*m] */
+int32_t sylow_hip_g1_ntt_batch_tuned(const uint64_t* p_xy, const uint8_t* p_inf, int32_t log_n, size_t m, int32_t inverse, int64_t max_blocks,
+                                     uint64_t* out_xy, uint8_t* out_inf, void* stream);
+/* The Lagrange-basis KZG SRS from the monomial one: srs_g1_xy [8][n] = tau^k G1gen, no flag array; out_xy [8][n] and out_inf [n] (required)
+ * = L_i(tau) G1gen = n^-1 sum_k w_n^(-ik) tau^k G1gen -- the inverse transform above with m = 1, and its errors.  A SET FLAG means that tau
+ * lies in the domain (some L_i(tau) = 0): such an SRS is unusable.  The output, fed to sylow_hip_kzg_commit_batch or
+ * sylow_hip_kzg_open_evals_batch, gives word for word what the monomial SRS gives through sylow_hip_kzg_commit_evals_batch or
+ * sylow_hip_kzg_open_batch on the interpolated coefficients; the forward transform takes it back to the monomial SRS. */
+/* @shape srs_g1_xy=u64[8*2**log_n] out_xy=u64[8*2**log_n] out_inf=u8[2**log_n] */
+int32_t sylow_hip_kzg_srs_lagrange(const uint64_t* srs_g1_xy, int32_t log_n, uint64_t* out_xy, uint8_t* out_inf, void* stream);
+
 /* ---- extension tower (test hooks): fields/fp2.rs:285-306,164-171,355-360; fp6.rs:283-367,
  * 415-423; fp12.rs:229-238,536-550,281-286,515-522,426-503 ------------------------------------ */
 /* FieldExtension<D, N, F> component-wise operators (fields/extensions.rs:67-238): Add / Sub / Neg and scale by a base-field

@@ -236,6 +236,24 @@ inline std::vector<Fp> ntt(const std::vector<Fp>& a, bool inverse = false, const
   return ntt(std::vector<std::vector<Fp>>{a}, inverse, shift, stages)[0];
 }
 }  // namespace fr
+// The transform of fr::ntt with G1 POINTS as elements, on the domain of n = p.size() = 2^log_n points (sylow_hip_g1_ntt_batch_tuned), natural
+// order in and out.  forward: out_i = sum_k w_n^(ik) P_k; inverse: out_k = n^-1 sum_i w_n^(-ik) P_i; no coset shift.  inf: the identity flags
+// of p (nullptr: none; the pair (0, 1) is the identity with or without its flag); max_blocks >= 1 caps the blocks of a stage launch (the
+// points do not depend on it).  Canonical affine words out, an identity as (0, 1) with its flag in inf_out.
+inline std::vector<G1Affine> g1_ntt(const std::vector<G1Affine>& p, bool inverse = false, const std::vector<uint8_t>* inf = nullptr,
+                                    std::vector<uint8_t>* inf_out = nullptr, int64_t max_blocks = -1) {
+  const size_t n = p.size();
+  int32_t log_n = 0;
+  while (((size_t)1 << log_n) < n) ++log_n;
+  if (!n || n != (size_t)1 << log_n) throw Error("g1_ntt: the length is a power of two");
+  auto dp = to_device_soa(p);
+  Flags f(inf, n);
+  DeviceBuffer dout(n * sizeof(G1Affine) + 8), dinf(n + 8);
+  check(sylow_hip_g1_ntt_batch_tuned(dp.as<uint64_t>(), f.ptr, log_n, 1, inverse ? 1 : 0, max_blocks, dout.as<uint64_t>(), dinf.as<uint8_t>(), nullptr),
+        "sylow_hip_g1_ntt_batch_tuned");
+  fetch_flags(inf_out, dinf, n);
+  return from_device_soa<G1Affine>(dout, n);
+}
 // sum_i k[j][i] * P[j][i] per job (examples/threshold_signing.rs:124-143); rows term-major: row i*n_jobs + j
 inline std::vector<G1Affine> aggregate(const std::vector<G1Affine>& p, const std::vector<Fp>& k, size_t n_jobs, size_t n_terms) {
   if (p.size() != n_jobs * n_terms || k.size() != p.size()) throw Error("aggregate: shape mismatch");
@@ -575,6 +593,19 @@ class KzgProver {
     fetch_flags(infinity, dinf, m);
     if (y) *y = from_device_soa<Fp>(dy, m);
     return from_device_soa<G1Affine>(dpi, m);
+  }
+  // The Lagrange-basis SRS L_i(tau) G1gen of the domain of len() = 2^log_n points (sylow_hip_kzg_srs_lagrange): what KzgEvalProver takes.
+  // Throws when tau lies in the domain (an identity comes back: some L_i(tau) = 0).
+  std::vector<G1Affine> lagrange_srs() const {
+    int32_t log_n = 0;
+    while (((size_t)1 << log_n) < len_) ++log_n;
+    if (len_ != (size_t)1 << log_n || log_n > 28) throw Error("KzgProver::lagrange_srs: the SRS holds a power of two of points, at most 2^28");
+    DeviceBuffer dout(len_ * sizeof(G1Affine) + 8), dinf(len_ + 8);
+    check(sylow_hip_kzg_srs_lagrange(srs_.as<uint64_t>(), log_n, dout.as<uint64_t>(), dinf.as<uint8_t>(), nullptr), "sylow_hip_kzg_srs_lagrange");
+    std::vector<uint8_t> inf;
+    fetch_flags(&inf, dinf, len_);
+    for (const uint8_t f : inf) if (f) throw Error("KzgProver::lagrange_srs: tau lies in the domain, the Lagrange-basis SRS is unusable");
+    return from_device_soa<G1Affine>(dout, len_);
   }
   // q_j = (f_j - f_j(z_j)) / (X - z_j), canonical words, q_j[len - 1] = 0, and y_j (sylow_hip_kzg_quotient_batch)
   std::vector<std::vector<Fp>> quotient(const std::vector<std::vector<Fp>>& polys, const std::vector<Fp>& z, std::vector<Fp>* y = nullptr) const {

@@ -1087,6 +1087,58 @@ pub fn fr_ntt_tuned(dev: &Device, a: &KzgPolys, inverse: bool, shift: Option<&Fr
     device::check(unsafe { ffi::sylow_hip_fr_ntt_batch_tuned(a.words.as_ptr(), log_n, a.m, inverse as i32, psh, stages, out.as_mut_ptr(), dev.stream) })?;
     Ok(KzgPolys { words: out, len: a.len, m: a.m })
 }
+/// m arrays of n = 2^log_n affine G1 points on the device as the G1 transform takes them: word w of point k of array j at (j * 8 + w) * n + k,
+/// flags [m][n].  With m = 1 this is the layout of `DeviceG1`.
+pub struct G1Arrays {
+    pub xy: DeviceBuf<u64>,
+    pub inf: DeviceBuf<u8>,
+    pub n: usize,
+    pub m: usize,
+}
+impl G1Arrays {
+    /// one array: the points as they lie
+    pub fn from_one(p: DeviceG1) -> Self {
+        G1Arrays { n: p.n, m: 1, xy: p.xy, inf: p.inf }
+    }
+    /// the only array of a batch of one
+    pub fn into_one(self) -> DeviceG1 {
+        assert!(self.m == 1, "a batch of one array");
+        DeviceG1 { n: self.n, xy: self.xy, inf: self.inf }
+    }
+}
+/// The transform of `fr_ntt` with G1 POINTS as elements (`sylow_hip_g1_ntt_batch`), natural order in and out: forward
+/// out_i = sum_k w_n^(ik) P_k, inverse out_k = n^-1 sum_i w_n^(-ik) P_i; no coset shift.  Points are taken as given; a flagged point, or the
+/// pair (0, 1), is the identity.  Canonical affine words and flags out, in buffers of their own.
+pub fn g1_ntt(dev: &Device, p: &G1Arrays, inverse: bool) -> Result<G1Arrays, HipError> {
+    let log_n = radix2_log(p.n);
+    let out = G1Arrays { xy: dev.alloc::<u64>(8 * (1 << log_n) * p.m)?, inf: dev.alloc::<u8>((1 << log_n) * p.m)?, n: p.n, m: p.m };
+    // SAFETY: m arrays of 2^log_n points and their flags in and out (distinct buffers).
+    device::check(unsafe {
+        ffi::sylow_hip_g1_ntt_batch(p.xy.as_ptr(), p.inf.as_ptr(), log_n, p.m, inverse as i32, out.xy.as_mut_ptr(), out.inf.as_mut_ptr(), dev.stream)
+    })?;
+    Ok(out)
+}
+/// The same with the blocks of a stage launch capped (`sylow_hip_g1_ntt_batch_tuned`): >= 1, negative = the default; 0 is refused.  The points
+/// do not depend on it.
+pub fn g1_ntt_tuned(dev: &Device, p: &G1Arrays, inverse: bool, max_blocks: i64) -> Result<G1Arrays, HipError> {
+    let log_n = radix2_log(p.n);
+    let out = G1Arrays { xy: dev.alloc::<u64>(8 * (1 << log_n) * p.m)?, inf: dev.alloc::<u8>((1 << log_n) * p.m)?, n: p.n, m: p.m };
+    // SAFETY: as g1_ntt.
+    device::check(unsafe {
+        ffi::sylow_hip_g1_ntt_batch_tuned(p.xy.as_ptr(), p.inf.as_ptr(), log_n, p.m, inverse as i32, max_blocks, out.xy.as_mut_ptr(), out.inf.as_mut_ptr(),
+                                          dev.stream)
+    })?;
+    Ok(out)
+}
+/// The Lagrange-basis SRS L_i(tau) G1gen from the monomial one (`sylow_hip_kzg_srs_lagrange`): what `kzg_open_evals` takes.  A set flag in
+/// the result means that tau lies in the domain and the SRS is unusable; the caller checks `inf`.
+pub fn kzg_srs_lagrange(dev: &Device, srs: &DeviceG1) -> Result<DeviceG1, HipError> {
+    let log_n = radix2_log(srs.n);
+    let out = DeviceG1 { xy: dev.alloc::<u64>(8 * (1 << log_n))?, inf: dev.alloc::<u8>(1 << log_n)?, n: srs.n };
+    // SAFETY: 2^log_n SRS points (no flags) in, as many points and flags out (distinct buffers).
+    device::check(unsafe { ffi::sylow_hip_kzg_srs_lagrange(srs.xy.as_ptr(), log_n, out.xy.as_mut_ptr(), out.inf.as_mut_ptr(), dev.stream) })?;
+    Ok(out)
+}
 /// A sparse matrix over Fr on the device, in CSR: `row_ptr` [rows + 1], `col` [nnz], `val` [4][nnz].
 pub struct CsrMatrix {
     pub row_ptr: DeviceBuf<u64>,

@@ -673,6 +673,21 @@ class KzgProver:
             raise ValueError("KzgProver.commit_evals: the SRS holds a power of two of points")
         return G1Affine(*engine().kzg_commit_evals(self.srs_g1.xy, self._polys(evals)))
 
+    def lagrange_srs(self) -> G1Affine:
+        """The Lagrange-basis SRS L_i(tau) G1gen of the domain of len(srs_g1) = 2^log_n points: the inverse G1 transform of the monomial SRS
+        (sylow_hip_kzg_srs_lagrange).  ValueError when tau lies in the domain (some L_i(tau) = 0: an identity comes back)."""
+        n = len(self.srs_g1)
+        if n & (n - 1) or n > 1 << 28:
+            raise ValueError("KzgProver.lagrange_srs: the SRS holds a power of two of points, at most 2^28")
+        xy, inf = engine().kzg_srs_lagrange(self.srs_g1.xy)
+        if inf.any():
+            raise ValueError("KzgProver.lagrange_srs: tau lies in the domain, the Lagrange-basis SRS holds an identity and is unusable")
+        return G1Affine(xy, inf)
+
+    def eval_prover(self) -> "KzgEvalProver":
+        """The prover for polynomials held in evaluation form under the same tau."""
+        return KzgEvalProver(self.lagrange_srs())
+
 
 class KzgEvalProver:
     """The prover's half of a BN254 KZG SRS for polynomials held in EVALUATION form: srs_lagrange = (L_i(tau) G1gen) for i = 0 .. n - 1, with L_i
@@ -738,6 +753,27 @@ def ntt(values, shift=None, inverse: bool = False, stages: int = -1) -> np.ndarr
 def intt(values, shift=None, stages: int = -1) -> np.ndarray:
     """The inverse of ntt: out_k = n^-1 g^-k sum_i a_i w_n^(-ik).  shift = 0 mod r uses inv(0) = 0."""
     return ntt(values, shift=shift, inverse=True, stages=stages)
+
+
+def g1_ntt(points, inverse: bool = False):
+    """The transform of ntt with G1 points as elements: `points` is a G1Affine of n = 2^log_n <= 2^28 points or a list of m of them (equal
+    lengths), natural order in and out: out_i = sum_k w_n^(ik) P_k (sylow_hip_g1_ntt_batch).  For P_k = s_k G that is ntt(s)_i G.  A G1Affine
+    (or a list of them) in canonical words, identities as (0, 1) + their flag."""
+    one = isinstance(points, G1Affine)
+    batch = [points] if one else list(points)
+    if not batch:
+        return []
+    n = len(batch[0])
+    if n < 1 or n & (n - 1) or n > 1 << 28 or any(len(p) != n for p in batch):
+        raise ValueError("g1_ntt: every array holds the same power of two of points, at most 2^28")
+    xy, inf = engine().g1_ntt(np.stack([p.xy for p in batch]), np.stack([p.infinity for p in batch]), inverse=inverse)
+    out = [G1Affine(xy[j], inf[j]) for j in range(len(batch))]
+    return out[0] if one else out
+
+
+def g1_intt(points):
+    """The inverse of g1_ntt: out_k = n^-1 sum_i w_n^(-ik) P_i."""
+    return g1_ntt(points, inverse=True)
 
 
 class KeyPair:

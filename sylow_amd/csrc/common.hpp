@@ -56,6 +56,20 @@ BN_DEV void load_scalar(u32 (&k)[8], const u64* base, size_t n, size_t i) {
   for (int j = 0; j < 8; ++j) k[j] = s.v[j];
 }
 
+// An affine SoA point as projective coordinates.  A FLAGGED point is the identity whatever its coordinate words hold: it is loaded as the
+// canonical (0 : 1 : 0) -- (x : y : 0) with x != 0 is not a point of the curve and the complete formulas owe it nothing
+BN_DEV G1P load_g1_flagged(const u64* xy, const uint8_t* inf, size_t n, size_t i) {
+  const bool z = inf && inf[i];
+  return G1P{z ? fp_zero() : load_fp(xy, n, i, 0), z ? fp_one() : load_fp(xy, n, i, 4), z ? fp_zero() : fp_one()};
+}
+// a projective point on the carry-free core <-> 12 canonical words of an SoA array [12][stride] (g1.hip's sums, g1_ntt.hip's stages)
+BN_DEV G1W g1w_load_proj(const u64* a, size_t stride, size_t i) {
+  return G1W{f29_from_fp_reduced(load_fp(a, stride, i, 0)), f29_from_fp_reduced(load_fp(a, stride, i, 4)), f29_from_fp_reduced(load_fp(a, stride, i, 8))};
+}
+BN_DEV void g1w_store_proj(u64* a, size_t stride, size_t i, const G1W& r) {
+  store_fp(a, stride, i, 0, f29_to_fp(r.x)); store_fp(a, stride, i, 4, f29_to_fp(r.y)); store_fp(a, stride, i, 8, f29_to_fp(r.z));
+}
+
 BN_DEV int wave_max(int v) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) { int o = __shfl_xor(v, off); v = o > v ? o : v; }

@@ -2,12 +2,6 @@
 // hash-to-G1 (XMD-Keccak256 + SvdW), BLS signing, the G1 wire format and the EIP-196 ecAdd / ecMul byte adapters.
 #include "host.hpp"
 
-// An affine SoA point as projective coordinates.  A FLAGGED point is the identity whatever its coordinate words hold: it is loaded as the
-// canonical (0 : 1 : 0) -- (x : y : 0) with x != 0 is not a point of the curve and the complete formulas owe it nothing
-BN_DEV G1P load_g1_flagged(const u64* xy, const uint8_t* inf, size_t n, size_t i) {
-  const bool z = inf && inf[i];
-  return G1P{z ? fp_zero() : load_fp(xy, n, i, 0), z ? fp_one() : load_fp(xy, n, i, 4), z ? fp_zero() : fp_one()};
-}
 // tables: NULL = window tables in the stack frame, else a block of n * G1_TABLE_BYTES_PER_LANE bytes (lane i's table contiguous)
 __global__ void HEAVY_BOUNDS k_g1_scalar_mul(const u64* pxy, const uint8_t* pinf, const u64* ks, u64* oxy, uint8_t* oinf, size_t n, uint8_t* tables) {
   size_t i = TID;
@@ -168,12 +162,6 @@ __global__ void HEAVY_BOUNDS k_g1_generator_mul(const u64* ks, const i32* __rest
 // converts to affine.  (The round-3 form -- a binary tree with one launch per level and every intermediate through HBM on the
 // saturated core -- took 4-6 ms per 2^20 points, neither issue- nor bandwidth-bound; this one is a few hundred microseconds.)
 constexpr size_t SUM_FOLD = 16;
-BN_DEV G1W g1w_load_proj(const u64* a, size_t stride, size_t i) {
-  return G1W{f29_from_fp_reduced(load_fp(a, stride, i, 0)), f29_from_fp_reduced(load_fp(a, stride, i, 4)), f29_from_fp_reduced(load_fp(a, stride, i, 8))};
-}
-BN_DEV void g1w_store_proj(u64* a, size_t stride, size_t i, const G1W& r) {
-  store_fp(a, stride, i, 0, f29_to_fp(r.x)); store_fp(a, stride, i, 4, f29_to_fp(r.y)); store_fp(a, stride, i, 8, f29_to_fp(r.z));
-}
 // affine points + identity flags (stride n) -> L partial sums in acc (stride acc_stride)
 __global__ void HEAVY_BOUNDS k_g1_sum_fold_affine(const u64* pxy, const uint8_t* pinf, size_t n, size_t L, u64* acc, size_t acc_stride) {
   const size_t t = TID;

@@ -126,6 +126,9 @@ bool window_ok(int32_t window);    // what the _tuned entry points accept: < 0 (
 namespace kzgph {       // kzg_prove.hip: sylow_hip_kzg_commit_batch for coefficients known to be canonical (below r), past the mod-r pass; len > 0, m > 0
 int32_t commit_canonical(const uint64_t* srs_g1_xy, const uint64_t* coeffs, size_t len, size_t m, uint64_t* out_xy, uint8_t* out_inf, void* stream);
 }  // namespace kzgph
+namespace ntth {        // ntt.hip: the twiddle table of the Fr transform, w_n^e for e < n / 2 as [4][n / 2] canonical words; log_n >= 1
+int32_t build_table(int log_n, uint64_t* table, void* stream);
+}  // namespace ntth
 namespace kzgh {        // kzg.hip: F_i = C_i - y_i G1gen + z_i pi_i (affine SoA + flags, stride n) and, when neg_xy is given, -pi_i beside it: one launch
 int32_t fold(const uint64_t* c_xy, const uint8_t* c_inf, const uint64_t* z, const uint64_t* y, const uint64_t* pi_xy, const uint8_t* pi_inf,
              uint64_t* out_xy, uint8_t* out_inf, uint64_t* neg_xy, uint8_t* neg_inf, size_t n, void* stream);

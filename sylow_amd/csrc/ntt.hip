@@ -189,6 +189,14 @@ static int32_t transform(const uint64_t* in, int log_n, size_t m, bool inverse, 
 }
 }  // namespace ntt
 
+namespace ntth {
+// the table w_n^e, e < n / 2, [4][n / 2] (ntt_plan::table_words), for a unit that walks the same domain (g1_ntt.hip); log_n >= 1
+int32_t build_table(int log_n, uint64_t* table, void* stream) {
+  ntt::k_ntt_table<<<dim3((unsigned)ntt_plan::grid(ntt_plan::table_blocks(log_n))), dim3(BLOCK), 0, (hipStream_t)stream>>>(log_n, table, nullptr, 0, nullptr);
+  LAUNCHED();
+}
+}  // namespace ntth
+
 extern "C" {
 int32_t sylow_hip_fr_ntt_batch_tuned(const uint64_t* in, int32_t log_n, size_t m, int32_t inverse, const uint64_t* shift, int32_t stages, uint64_t* out, void* stream) {
   using namespace ntt_plan;

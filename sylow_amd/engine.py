@@ -1128,6 +1128,39 @@ class Engine:
         out = np.ascontiguousarray(dout.download()[:m].transpose(0, 2, 1))
         return out[0] if one else out
 
+    # ---- G1 transforms on radix-2 domains.  xy [m, n, 8] (or [n, 8]: one array) affine words, inf [m, n] (or [n]) flags or None, n = 2^log_n ----
+    def g1_ntt(self, xy, inf=None, inverse=False, max_blocks=-1):
+        """forward: out_i = sum_k w_n^(ik) P_k; inverse: out_k = n^-1 sum_i w_n^(-ik) P_i, natural order both ways, per array
+        (sylow_hip_g1_ntt_batch).  max_blocks >= 1 caps the blocks of a stage launch (sylow_hip_g1_ntt_batch_tuned); the points do not depend
+        on it.  (canonical affine words in the shape of `xy`, flags), the identity as (0, 1) + its flag."""
+        a = np.ascontiguousarray(xy, dtype=np.uint64)
+        one = a.ndim == 2
+        a = a[None] if one else a
+        assert a.ndim == 3 and a.shape[2] == 8 and a.shape[1] >= 1, a.shape
+        m, n = a.shape[0], a.shape[1]
+        log_n = n.bit_length() - 1
+        assert n == 1 << log_n, n
+        din = self.to_device(np.ascontiguousarray(a.transpose(0, 2, 1))) if m else None
+        dinf = None if inf is None or not m else self.to_device(np.ascontiguousarray(inf, dtype=np.uint8).reshape(m, n))
+        do, doi = self.empty((max(m, 1), 8, n)), self.empty((max(m, 1), n), np.uint8)
+        if max_blocks < 0:
+            self._call("sylow_hip_g1_ntt_batch", self._ptr(din), self._ptr(dinf), log_n, m, int(bool(inverse)), do.ptr, doi.ptr)
+        else:
+            self._call("sylow_hip_g1_ntt_batch_tuned", self._ptr(din), self._ptr(dinf), log_n, m, int(bool(inverse)), int(max_blocks), do.ptr, doi.ptr)
+        out, flags = np.ascontiguousarray(do.download()[:m].transpose(0, 2, 1)), doi.download()[:m]
+        return (out[0], flags[0]) if one else (out, flags)
+
+    def kzg_srs_lagrange(self, xy):
+        """The Lagrange-basis SRS L_i(tau) G1gen from the monomial one, xy [n, 8] = tau^k G1gen, n = 2^log_n (sylow_hip_kzg_srs_lagrange):
+        ([n, 8] affine words, [n] flags); a set flag means tau lies in the domain."""
+        srs = _aos(xy, 8)
+        n = srs.shape[0]
+        log_n = n.bit_length() - 1
+        assert n >= 1 and n == 1 << log_n, n
+        ds, do, doi = self.to_device_soa(srs, 8), self.empty((8, n)), self.empty((n,), np.uint8)
+        self._call("sylow_hip_kzg_srs_lagrange", ds.ptr, log_n, do.ptr, doi.ptr)
+        return self.from_device_soa(do), doi.download()
+
     # ---- Groth16, the prover's side.  A sparse matrix is CSR: (row_ptr [rows + 1], col [nnz], val [nnz, 4]); Fr batches are [m, n, 4] on the
     # host and [m][4][n] on the device; any 256-bit words, taken mod r ----
     def _csr_up(self, csr):

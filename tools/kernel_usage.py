@@ -20,9 +20,9 @@ for u in units:
             cur = subprocess.run(["c++filt", m.group(1)], capture_output=True, text=True).stdout.strip().split("(")[0]
             rows[cur] = {}
             continue
-        m = re.search(r"remark:\s+(VGPRs|VGPR Spill|ScratchSize \[bytes/lane\]|LDS Size \[bytes/block\]|Occupancy \[waves/SIMD\]|AGPRs): (\d+)", line)
+        m = re.search(r"remark:\s+(VGPRs|VGPRs? Spill|ScratchSize \[bytes/lane\]|LDS Size \[bytes/block\]|Occupancy \[waves/SIMD\]|AGPRs): (\d+)", line)
         if m and cur:
-            rows[cur][m.group(1)] = int(m.group(2))
+            rows[cur][m.group(1).replace("VGPRs Spill", "VGPR Spill")] = int(m.group(2))      # the compiler writes "VGPRs Spill"
     print(f"== {u}.hip")
     print(f"{'kernel':58s} {'VGPR':>5s} {'spill':>6s} {'scratch B':>10s} {'LDS B':>7s} {'waves/SIMD':>10s} {'(LDS-limited, 256-thread blocks)':>s}")
     for k, v in rows.items():
