@@ -934,6 +934,50 @@ int32_t sylow_hip_kzg_quotient_evals_batch(const uint64_t* evals, int32_t log_n,
 int32_t sylow_hip_kzg_open_evals_batch(const uint64_t* srs_lagrange_xy, const uint64_t* evals, int32_t log_n, size_t m, const uint64_t* z,
                                        uint64_t* y_out, uint64_t* pi_xy, uint8_t* pi_inf, void* stream);
 
+/* ---- KZG, the prover's side: every point of the domain at once (kzg_open_all.hip; geometry, ping-pong and scratch in kzg_open_all_plan.hpp) ----
+ * The n proofs of ONE polynomial of n = 2^log_n coefficients at all n points w_n^i of its domain, in n log n instead of n^2 (Feist-Khovratovich):
+ *   pi_i = q_i(tau) G1gen,  q_i = (f - f(w^i)) / (X - w^i)   =   sum_b w^(ib) h_b,   h_b = sum_(t = 0 .. n-2-b) f_(b+1+t) s_t,   h_(n-1) = identity,
+ * a forward transform (that of sylow_hip_g1_ntt_batch) of a Toeplitz product, and the Toeplitz product a cyclic convolution of 2n points:
+ * h = the first n points of G1-INTT_2n(F_i T_i) with F = the Fr transform of (f, then n zeros) and T the transform of x, x_(2n-1-t) = s_t
+ * for t = 0 .. n-2 and the identity elsewhere (s_(n-1) is not used).  T depends on the SRS alone and serves every polynomial.
+ * Conventions (those of the transform blocks and of the KZG prover block above):
+ *   the SRS:   srs_g1_xy [8][n], the affine points s_t = tau^t G1gen, taken as given, no flag array.
+ *   the table: table_xy [8][2n] + table_inf [2n], canonical affine words, the identity as (0, 1) + its flag.  Read back, a flagged entry is the
+ *              identity whatever its words hold, and so is (0, 1) without a flag; table_inf may then be NULL.
+ *   polynomials: coeffs [m][4][n], 0 <= log_n <= 27 (the transform of 2n points must fit the 2^28 roots); ANY 256-bit words, taken mod r.
+ *   outputs:   y_out [m][4][n] in the layout of coeffs, y_ji = f_j(w^i), canonical words below r (the forward Fr transform; may be NULL);
+ *              pi_xy [m][8][n] + pi_inf [m][n] (required): the proofs as canonical affine words, the identity as (0, 1) + its flag, in the
+ *              layout of sylow_hip_g1_ntt_batch.  They do NOT depend on the plan (max_blocks below).  Row (C_j, w^i, y_ji, pi_ji) with C_j from
+ *              sylow_hip_kzg_commit_batch is a valid row of the verifiers above under tau_g2, and pi_ji is word for word what
+ *              sylow_hip_kzg_open_batch yields for f_j at z = w^i.
+ *   calls:     stream-ordered, no host synchronisation; scratch leased per call, summed in saturating arithmetic and refused before the lease.
+ *              m = 0: OK, nothing launched, nothing written.
+ *   errors:    SYLOW_HIP_E_ARG, no launch, nothing written, for: log_n < 0 or > 27; a required pointer NULL; max_blocks == 0; y_out
+ *              overlapping coeffs; pi_xy overlapping coeffs or table_xy. */
+/* T of the block above from the monomial SRS: x into leased scratch (130 n bytes), then sylow_hip_g1_ntt_batch over 2n points, forward, m = 1
+ * -- word for word what that call returns for x.  Once per SRS.  A SET FLAG IS AN OUTPUT, NOT AN ERROR: at log_n = 0 both entries are the
+ * identity, and a special tau gives others (T_0 = (1 + tau + .. + tau^(n-2)) G1gen is the identity for log_n = 2 and 4 when tau^3 = 1). */
+/* @shape srs_g1_xy=u64[8*2**log_n] table_xy=u64[16*2**log_n] table_inf=u8[2*2**log_n] */
+int32_t sylow_hip_kzg_open_all_prepare(const uint64_t* srs_g1_xy, int32_t log_n, uint64_t* table_xy, uint8_t* table_inf, void* stream);
+/* The proofs of m polynomials at every point of the domain, and their values there.  Per call: the forward Fr transform into y_out; (2n)^-1 f
+ * padded to 2n and its Fr transform F into scratch (the scale of the inverse transform as ONE Fr PRODUCT per coefficient, not a scalar
+ * multiplication per point); one launch for the pointwise products fused with stage 0 of the inverse transform (two scalar multiplications
+ * from the affine table per butterfly); log_n launches of the stage kernel of sylow_hip_g1_ntt_batch for the rest of it; one launch for
+ * stage 0 of the forward transform of n points, which reads h where the inverse left it and takes h_(n-1) as the identity; log_n - 1 stage
+ * launches and the closing launch without a scale: one Fp inversion per proof.  Nothing between F and the affine proofs leaves the device or
+ * projective form.  About 1.5 n log_n scalar multiplications per polynomial: 2n + (n (log_n - 1) + 1) + ((n / 2)(log_n - 2) + 1).
+ * Scratch: two projective buffers of 192 n m bytes each (F lies in one of them), twiddle tables of 48 n bytes, window tables of 1 KB per
+ * RESIDENT lane (128 MB by default).  log_n = 0: the one proof is the identity, y_j0 = f_j0 mod r.  A zero or constant polynomial has every
+ * proof flagged. */
+/* @shape table_xy=u64[16*2**log_n] table_inf=u8[2*2**log_n]? coeffs=u64[4*2**log_n*m] y_out=u64[4*2**log_n*m]? pi_xy=u64[8*2**log_n*m] pi_inf=u8[2**log_n*m] */
+int32_t sylow_hip_kzg_open_all_batch(const uint64_t* table_xy, const uint8_t* table_inf, const uint64_t* coeffs, int32_t log_n, size_t m,
+                                     uint64_t* y_out, uint64_t* pi_xy, uint8_t* pi_inf, void* stream);
+/* The same with the blocks of a multiplying launch capped, as sylow_hip_g1_ntt_batch_tuned: max_blocks >= 1 (at most 4096; more is 4096),
+ * < 0 = the default (512).  The values do not depend on it. */
+/* @shape table_xy=u64[16*2**log_n] table_inf=u8[2*2**log_n]? coeffs=u64[4*2**log_n*m] y_out=u64[4*2**log_n*m]? pi_xy=u64[8*2**log_n*m] pi_inf=u8[2**log_n*m] */
+int32_t sylow_hip_kzg_open_all_batch_tuned(const uint64_t* table_xy, const uint8_t* table_inf, const uint64_t* coeffs, int32_t log_n, size_t m,
+                                           int64_t max_blocks, uint64_t* y_out, uint64_t* pi_xy, uint8_t* pi_inf, void* stream);
+
 /* ---- Groth16, the prover's side: R1CS products, the quotient and the proof under ONE proving key (groth16_prove.hip; lanes per row, grids,
  * scratch and chunks in groth16_prove_plan.hpp) ------------------------------------------------------------------------------------------
  * Conventions of the calls below (those of the transforms and of the KZG prover block):

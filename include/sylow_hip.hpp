@@ -9,6 +9,7 @@
 // sylow_hip_aos_to_soa / _soa_to_aos, so no host loop touches the limbs.
 #pragma once
 #include <cstdint>
+#include <memory>
 #include <stdexcept>
 #include <string>
 #include <utility>
@@ -607,6 +608,49 @@ class KzgProver {
     for (const uint8_t f : inf) if (f) throw Error("KzgProver::lagrange_srs: tau lies in the domain, the Lagrange-basis SRS is unusable");
     return from_device_soa<G1Affine>(dout, len_);
   }
+  // The proofs of every f_j at ALL len() = 2^log_n points w_n^i of its domain at once, in n log n (sylow_hip_kzg_open_all_batch_tuned, the
+  // Feist-Khovratovich construction): pi[j][i], word for word open(f_j, w_n^i); *y (if given) receives y[j][i] = f_j(w_n^i) = fr::ntt(polys)
+  // and *infinity the identity flags per polynomial (every proof of a constant polynomial).  The table that depends on the SRS alone
+  // (sylow_hip_kzg_open_all_prepare) is built on first use and kept on the device.  max_blocks >= 1 caps the blocks of a multiplying launch;
+  // the values do not depend on it.
+  std::vector<std::vector<G1Affine>> open_all(const std::vector<std::vector<Fp>>& polys, std::vector<std::vector<Fp>>* y = nullptr,
+                                              std::vector<std::vector<uint8_t>>* infinity = nullptr, int64_t max_blocks = -1) const {
+    const size_t m = polys.size(), n = len_;
+    int32_t log_n = 0;
+    while (((size_t)1 << log_n) < n) ++log_n;
+    if (n != (size_t)1 << log_n || log_n > 27) throw Error("KzgProver::open_all: the SRS holds a power of two of points, at most 2^27");
+    if (!all_xy_) {
+      std::unique_ptr<DeviceBuffer> txy(new DeviceBuffer(2 * n * sizeof(G1Affine) + 8)), tinf(new DeviceBuffer(2 * n + 8));
+      check(sylow_hip_kzg_open_all_prepare(srs_.as<uint64_t>(), log_n, txy->as<uint64_t>(), tinf->as<uint8_t>(), nullptr), "sylow_hip_kzg_open_all_prepare");
+      all_xy_ = std::move(txy);
+      all_inf_ = std::move(tinf);
+    }
+    DeviceBuffer dc = upload("KzgProver::open_all", polys);
+    DeviceBuffer dy(4 * n * m * sizeof(uint64_t) + 8), dpi(8 * n * m * sizeof(uint64_t) + 8), dinf(n * m + 8);
+    check(sylow_hip_kzg_open_all_batch_tuned(all_xy_->as<uint64_t>(), all_inf_->as<uint8_t>(), dc.as<uint64_t>(), log_n, m, max_blocks, dy.as<uint64_t>(),
+                                             dpi.as<uint64_t>(), dinf.as<uint8_t>(), nullptr), "sylow_hip_kzg_open_all_batch_tuned");
+    std::vector<uint64_t> fy(4 * n * m), fp(8 * n * m);
+    std::vector<uint8_t> fi(n * m);
+    if (m) {
+      check(sylow_hip_memcpy_d2h(fy.data(), dy.as<void>(), fy.size() * sizeof(uint64_t), nullptr), "d2h");
+      check(sylow_hip_memcpy_d2h(fp.data(), dpi.as<void>(), fp.size() * sizeof(uint64_t), nullptr), "d2h");
+      check(sylow_hip_memcpy_d2h(fi.data(), dinf.as<void>(), fi.size(), nullptr), "d2h");
+    }
+    check(sylow_hip_stream_sync(nullptr), "sync");
+    std::vector<std::vector<G1Affine>> pi(m, std::vector<G1Affine>(n));
+    if (y) y->assign(m, std::vector<Fp>(n));
+    if (infinity) infinity->assign(m, std::vector<uint8_t>(n));
+    for (size_t j = 0; j < m; ++j)
+      for (size_t k = 0; k < n; ++k) {
+        for (size_t w = 0; w < 4; ++w) {
+          pi[j][k].x.w[w] = fp[(j * 8 + w) * n + k];
+          pi[j][k].y.w[w] = fp[(j * 8 + 4 + w) * n + k];
+          if (y) (*y)[j][k].w[w] = fy[(j * 4 + w) * n + k];
+        }
+        if (infinity) (*infinity)[j][k] = fi[j * n + k];
+      }
+    return pi;
+  }
   // q_j = (f_j - f_j(z_j)) / (X - z_j), canonical words, q_j[len - 1] = 0, and y_j (sylow_hip_kzg_quotient_batch)
   std::vector<std::vector<Fp>> quotient(const std::vector<std::vector<Fp>>& polys, const std::vector<Fp>& z, std::vector<Fp>* y = nullptr) const {
     const size_t m = polys.size();
@@ -639,6 +683,7 @@ class KzgProver {
   }
   size_t len_;
   DeviceBuffer srs_;
+  mutable std::unique_ptr<DeviceBuffer> all_xy_, all_inf_;      // open_all's table [8][2 len] + [2 len], built on first use
 };
 // The prover's half of the SRS for polynomials held in EVALUATION form (sylow_hip.h, "KZG, the prover's side, from evaluations"):
 // srs_lagrange[i] = L_i(tau) G1gen for the Lagrange basis of the domain of n = 2^log_n points, kept on the device.  A polynomial is its

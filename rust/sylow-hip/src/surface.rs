@@ -1139,6 +1139,46 @@ pub fn kzg_srs_lagrange(dev: &Device, srs: &DeviceG1) -> Result<DeviceG1, HipErr
     device::check(unsafe { ffi::sylow_hip_kzg_srs_lagrange(srs.xy.as_ptr(), log_n, out.xy.as_mut_ptr(), out.inf.as_mut_ptr(), dev.stream) })?;
     Ok(out)
 }
+/// The table of `kzg_open_all` from the monomial SRS of `srs.n` = 2^log_n <= 2^27 points (`sylow_hip_kzg_open_all_prepare`): the forward
+/// G1 transform of 2n points, x_(2n-1-t) = s_t for t <= n - 2 and the identity elsewhere.  Once per SRS; a set flag is an entry that is
+/// the identity, not an error.
+pub fn kzg_open_all_prepare(dev: &Device, srs: &DeviceG1) -> Result<DeviceG1, HipError> {
+    let log_n = open_all_log(srs.n);
+    let table = DeviceG1 { xy: dev.alloc::<u64>(16 * (1 << log_n))?, inf: dev.alloc::<u8>(2 * (1 << log_n))?, n: 2 * srs.n };
+    // SAFETY: 2^log_n SRS points (no flags) in, twice as many points and flags out (distinct buffers).
+    device::check(unsafe { ffi::sylow_hip_kzg_open_all_prepare(srs.xy.as_ptr(), log_n, table.xy.as_mut_ptr(), table.inf.as_mut_ptr(), dev.stream) })?;
+    Ok(table)
+}
+/// log2 of a domain `kzg_open_all` serves: the transform of twice as many points must fit the 2^28 roots
+fn open_all_log(n: usize) -> i32 {
+    assert!(n.is_power_of_two() && n <= 1 << 27, "a radix-2 domain of at most 2^27 points");
+    n.trailing_zeros() as i32
+}
+/// The proofs of every f_j at ALL n = `p.len` = 2^log_n points w_n^i of its domain, in n log n, and its values there
+/// (`sylow_hip_kzg_open_all_batch`): (y in the layout of `p`, y_ji = f_j(w^i); pi as m arrays of n points).  pi_ji is word for word what
+/// `kzg_open` yields for f_j at w^i; `table` is what `kzg_open_all_prepare` returned for the SRS.
+pub fn kzg_open_all(dev: &Device, table: &DeviceG1, p: &KzgPolys) -> Result<(KzgPolys, G1Arrays), HipError> {
+    kzg_open_all_tuned(dev, table, p, -1)
+}
+/// The same with the blocks of a multiplying launch capped (`sylow_hip_kzg_open_all_batch_tuned`): >= 1, negative = the default; 0 is
+/// refused.  The values do not depend on it.
+pub fn kzg_open_all_tuned(dev: &Device, table: &DeviceG1, p: &KzgPolys, max_blocks: i64) -> Result<(KzgPolys, G1Arrays), HipError> {
+    let log_n = open_all_log(p.len);
+    assert!(table.n == 2 * p.len, "the table holds two entries per coefficient");
+    let y = dev.alloc::<u64>(4 * (1 << log_n) * p.m)?;
+    let pi = G1Arrays { xy: dev.alloc::<u64>(8 * (1 << log_n) * p.m)?, inf: dev.alloc::<u8>((1 << log_n) * p.m)?, n: p.len, m: p.m };
+    // SAFETY: 2 * 2^log_n table entries and their flags, m arrays of 2^log_n coefficients in, as many values, points and flags out (distinct buffers).
+    device::check(unsafe {
+        if max_blocks < 0 {
+            ffi::sylow_hip_kzg_open_all_batch(table.xy.as_ptr(), table.inf.as_ptr(), p.words.as_ptr(), log_n, p.m, y.as_mut_ptr(), pi.xy.as_mut_ptr(),
+                                              pi.inf.as_mut_ptr(), dev.stream)
+        } else {
+            ffi::sylow_hip_kzg_open_all_batch_tuned(table.xy.as_ptr(), table.inf.as_ptr(), p.words.as_ptr(), log_n, p.m, max_blocks, y.as_mut_ptr(),
+                                                    pi.xy.as_mut_ptr(), pi.inf.as_mut_ptr(), dev.stream)
+        }
+    })?;
+    Ok((KzgPolys { words: y, len: p.len, m: p.m }, pi))
+}
 /// A sparse matrix over Fr on the device, in CSR: `row_ptr` [rows + 1], `col` [nnz], `val` [4][nnz].
 pub struct CsrMatrix {
     pub row_ptr: DeviceBuf<u64>,

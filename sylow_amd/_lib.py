@@ -167,6 +167,9 @@ SIGNATURES = {
     "sylow_hip_g1_ntt_batch": [c_u64p, c_u8p, c_i32, c_sz, c_i32, c_u64p, c_u8p, c_vp],
     "sylow_hip_g1_ntt_batch_tuned": [c_u64p, c_u8p, c_i32, c_sz, c_i32, ctypes.c_int64, c_u64p, c_u8p, c_vp],
     "sylow_hip_kzg_srs_lagrange": [c_u64p, c_i32, c_u64p, c_u8p, c_vp],
+    "sylow_hip_kzg_open_all_prepare": [c_u64p, c_i32, c_u64p, c_u8p, c_vp],
+    "sylow_hip_kzg_open_all_batch": [c_u64p, c_u8p, c_u64p, c_i32, c_sz, c_u64p, c_u64p, c_u8p, c_vp],
+    "sylow_hip_kzg_open_all_batch_tuned": [c_u64p, c_u8p, c_u64p, c_i32, c_sz, ctypes.c_int64, c_u64p, c_u64p, c_u8p, c_vp],
     "sylow_hip_fr_batch_inv": [c_u64p, c_u64p, c_sz, c_vp],
     "sylow_hip_kzg_quotient_evals_batch": [c_u64p, c_i32, c_sz, c_u64p, c_u64p, c_u64p, c_vp],
     "sylow_hip_kzg_open_evals_batch": [c_u64p, c_u64p, c_i32, c_sz, c_u64p, c_u64p, c_u64p, c_u8p, c_vp],

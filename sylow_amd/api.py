@@ -644,6 +644,7 @@ class KzgProver:
         if len(srs_g1) < 1 or srs_g1.infinity.any():
             raise ValueError("KzgProver: srs_g1 holds at least G1gen and no identity")
         self.srs_g1 = srs_g1
+        self._open_all_table = None      # open_all: built on first use
 
     def _polys(self, polys):
         a = np.asarray(polys)
@@ -664,6 +665,20 @@ class KzgProver:
         y, pi_xy, pi_inf = engine().kzg_open(self.srs_g1.xy, self._polys(polys), KzgVerifier._words(z))
         return y, G1Affine(pi_xy, pi_inf)
 
+
+    def open_all(self, polys):
+        """The openings of every f_j at ALL n = len(srs_g1) = 2^log_n points of its domain at once, in n log n (sylow_hip_kzg_open_all_batch,
+        the Feist-Khovratovich construction): (y [m, n, 4] words, [G1Affine] * m) with y[j, i] = f_j(w_n^i) (= ntt(polys)) and pi_j[i] word
+        for word what open(f_j, w_n^i) yields.  The table that depends on the SRS alone is built on first use and kept on the device.
+        ValueError unless the SRS holds a power of two of points, at most 2^27."""
+        n = len(self.srs_g1)
+        if n & (n - 1) or n > 1 << 27:
+            raise ValueError("KzgProver.open_all: the SRS holds a power of two of points, at most 2^27")
+        a = self._polys(polys)
+        if self._open_all_table is None:
+            self._open_all_table = engine().kzg_open_all_prepare(self.srs_g1.xy)
+        y, pi_xy, pi_inf = engine().kzg_open_all(self._open_all_table, a)
+        return y, [G1Affine(pi_xy[j], pi_inf[j]) for j in range(a.shape[0])]
 
     def commit_evals(self, evals) -> G1Affine:
         """The same commitments from the VALUES of the polynomials on the domain of len(srs_g1) = 2^log_n points, evals[j][i] = f_j(w_n^i)

@@ -10,6 +10,7 @@
 // Geometry, ping-pong, grids and scratch: g1_ntt_plan.hpp -- nothing here decides one.
 #include "host.hpp"
 #include "g1_ntt_plan.hpp"
+#include "g1_ntt_dev.hpp"
 
 namespace g1ntt {
 using namespace g1_ntt_plan;
@@ -19,26 +20,6 @@ static_assert(G1_NTT_TABLE_BYTES_PER_LANE == G1_TABLE_BYTES_PER_LANE, "a lane's 
 struct Scalar {        // an Fr value as a kernel argument
   u64 w[4];
 };
-// An input point.  The identity is a flagged point, whatever its words hold, or the pair (0, 1) that every call of this library writes for
-// it (no point of the curve: 1 != 3) with or without its flag.  It joins as the canonical (0 : 1 : 0).
-BN_DEV G1P load_input(const u64* xy, const uint8_t* inf, size_t n, size_t i) {
-  G1P p = load_g1_flagged(xy, inf, n, i);                 // a flagged point comes back as (0 : 1 : 0): the test below holds for it too
-  p.z = fp_select(p.z, fp_zero(), fp_is_zero(p.x) && fp_eq(p.y, fp_one()));
-  return p;
-}
-BN_DEV G1W to_core(const G1P& p) { return G1W{f29_from_fp_reduced(p.x), f29_from_fp_reduced(p.y), f29_from_fp_reduced(p.z)}; }
-// Every intermediate with Z = 0 is stored as (0 : 1 : 0): the complete formulas keep Z = 0 only for that representative across consecutive
-// additions (bn254_pairing.hpp: g1_scalar_mul_t), and U - V with U = V makes identities that feed the later stages
-BN_DEV void store_canonical(u64* a, size_t stride, size_t i, const G1W& r) {
-  const bool inf = OpsF29::is_zero(r.z);
-  g1w_store_proj(a, stride, i, G1W{OpsF29::select(r.x, OpsF29::zero(), inf), OpsF29::select(r.y, OpsF29::one(), inf), r.z});
-}
-BN_DEV void butterfly_store(u64* dst, size_t stride, size_t o0, size_t o1, const G1W& u, G1W v, bool v_inf) {
-  store_canonical(dst, stride, o0, proj_add_lazy<OpsF29>(u, v));
-  v.y = OpsF29::select(OpsF29::neg(v.y), OpsF29::one(), v_inf);
-  store_canonical(dst, stride, o1, proj_add_lazy<OpsF29>(u, v));
-}
-
 // Stage 0 over items (array, butterfly): U = in[j], V = in[j + n/2] from the caller's affine arrays [m][8][n] + [m][n], out[2j] = U + V,
 // out[2j + 1] = U - V into a projective buffer [12][stride], array a at columns a n ...
 __global__ void __launch_bounds__(BLOCK) k_g1_ntt_first(const u64* pxy, const uint8_t* pinf, u64* dst, int log_n, size_t total, size_t stride) {
@@ -130,6 +111,25 @@ static int32_t transform(const uint64_t* p_xy, const uint8_t* p_inf, int log_n, 
   return host::finish(rc, ws);
 }
 }  // namespace g1ntt
+
+namespace g1ntth {
+// For a unit that runs part of a transform on projective buffers of its own (kzg_open_all.hip): the launches of transform() above, one at a
+// time, with the caller's geometry.  Arrays of 2^log_n points, array a at columns a 2^log_n of a buffer [12][stride]; `tables` holds a window
+// table for every lane of g1_ntt_plan::stage_grid(log_n, m, max_blocks) blocks.
+int32_t stage(const uint64_t* src, uint64_t* dst, int log_n, size_t m, size_t stride, int stage, bool inverse, const uint64_t* twiddles, uint8_t* tables,
+              long long max_blocks, void* stream) {
+  using namespace g1_ntt_plan;
+  g1ntt::k_g1_ntt_stage<<<dim3((unsigned)stage_grid(log_n, m, max_blocks)), dim3(BLOCK), 0, (hipStream_t)stream>>>(src, dst, log_n, stage, butterflies(log_n, m), stride,
+                                                                                                                 twiddles, inverse ? 1 : 0, tables);
+  LAUNCHED();
+}
+int32_t close(const uint64_t* src, int log_n, size_t m, size_t stride, uint64_t* out_xy, uint8_t* out_inf, long long max_blocks, void* stream) {
+  using namespace g1_ntt_plan;
+  g1ntt::k_g1_ntt_close<false><<<dim3((unsigned)closing_grid(log_n, m, max_blocks)), dim3(BLOCK), 0, (hipStream_t)stream>>>(src, nullptr, 0, out_xy, out_inf, log_n,
+                                                                                                                          points(log_n, m), stride, g1ntt::Scalar{}, nullptr);
+  LAUNCHED();
+}
+}  // namespace g1ntth
 
 extern "C" {
 int32_t sylow_hip_g1_ntt_batch_tuned(const uint64_t* p_xy, const uint8_t* p_inf, int32_t log_n, size_t m, int32_t inverse, int64_t max_blocks,

@@ -129,6 +129,13 @@ int32_t commit_canonical(const uint64_t* srs_g1_xy, const uint64_t* coeffs, size
 namespace ntth {        // ntt.hip: the twiddle table of the Fr transform, w_n^e for e < n / 2 as [4][n / 2] canonical words; log_n >= 1
 int32_t build_table(int log_n, uint64_t* table, void* stream);
 }  // namespace ntth
+namespace g1ntth {      // g1_ntt.hip: ONE launch of its transform on a caller's projective buffers [12][stride], m arrays of 2^log_n points, array a at
+// columns a 2^log_n: stage `stage` >= 1 (log_n >= 2; twiddles: ntth::build_table(log_n); tables: G1_TABLE_BYTES_PER_LANE bytes per lane of
+// g1_ntt_plan::stage_grid(log_n, m, max_blocks) blocks), and the closing kernel without a scale: affine + flags into [m][8][n] + [m][n]
+int32_t stage(const uint64_t* src, uint64_t* dst, int log_n, size_t m, size_t stride, int stage, bool inverse, const uint64_t* twiddles, uint8_t* tables,
+              long long max_blocks, void* stream);
+int32_t close(const uint64_t* src, int log_n, size_t m, size_t stride, uint64_t* out_xy, uint8_t* out_inf, long long max_blocks, void* stream);
+}  // namespace g1ntth
 namespace kzgh {        // kzg.hip: F_i = C_i - y_i G1gen + z_i pi_i (affine SoA + flags, stride n) and, when neg_xy is given, -pi_i beside it: one launch
 int32_t fold(const uint64_t* c_xy, const uint8_t* c_inf, const uint64_t* z, const uint64_t* y, const uint64_t* pi_xy, const uint8_t* pi_inf,
              uint64_t* out_xy, uint8_t* out_inf, uint64_t* neg_xy, uint8_t* neg_inf, size_t n, void* stream);

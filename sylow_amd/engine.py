@@ -1161,6 +1161,43 @@ class Engine:
         self._call("sylow_hip_kzg_srs_lagrange", ds.ptr, log_n, do.ptr, doi.ptr)
         return self.from_device_soa(do), doi.download()
 
+    # ---- KZG proofs at every point of the domain.  The table T is kept ON THE DEVICE: (DeviceArray [8, 2n] words, DeviceArray [2n] flags) ----
+    def kzg_open_all_prepare(self, srs_g1):
+        """The table of kzg_open_all from the monomial SRS, srs_g1 [n, 8] = tau^k G1gen, n = 2^log_n <= 2^27 (sylow_hip_kzg_open_all_prepare):
+        the forward G1 transform of 2n points, x_(2n-1-t) = s_t for t <= n - 2 and the identity elsewhere.  Device arrays ([8, 2n] words,
+        [2n] flags), built once per SRS; a set flag is an entry that is the identity, not an error."""
+        srs = _aos(srs_g1, 8)
+        n = srs.shape[0]
+        log_n = n.bit_length() - 1
+        assert n >= 1 and n == 1 << log_n, n
+        ds, dt, dti = self.to_device_soa(srs, 8), self.empty((8, 2 * n)), self.empty((2 * n,), np.uint8)
+        self._call("sylow_hip_kzg_open_all_prepare", ds.ptr, log_n, dt.ptr, dti.ptr)
+        self.sync()                      # ds is released when this frame returns
+        return dt, dti
+
+    def kzg_open_all(self, table, polys, max_blocks=-1, want_y=True):
+        """The proofs of every f_j at ALL n points w_n^i of its domain and its values there (sylow_hip_kzg_open_all_batch): (y [m, n, 4] or
+        None, pi [m, n, 8] affine words, pi flags [m, n]).  table: what kzg_open_all_prepare returned, or host arrays ([2n, 8] words,
+        [2n] flags or None).  polys [m, n, 4].  max_blocks >= 1 caps the blocks of a multiplying launch (sylow_hip_kzg_open_all_batch_tuned);
+        the values do not depend on it."""
+        a = self._kzg_polys(polys)
+        m, n = a.shape[0], a.shape[1]
+        log_n = n.bit_length() - 1
+        assert n == 1 << log_n, n
+        txy, tinf = table
+        dt = txy if isinstance(txy, DeviceArray) else self.to_device_soa(_aos(txy, 8), 8)
+        dti = tinf if tinf is None or isinstance(tinf, DeviceArray) else self.to_device(np.ascontiguousarray(tinf, dtype=np.uint8).reshape(-1))
+        assert dt.shape == (8, 2 * n) and (dti is None or dti.shape == (2 * n,)), (dt.shape, n)
+        dc = self._kzg_polys_up(a)
+        dy = self.empty((max(m, 1), 4, n)) if want_y else None
+        dp, dpi = self.empty((max(m, 1), 8, n)), self.empty((max(m, 1), n), np.uint8)
+        if max_blocks < 0:
+            self._call("sylow_hip_kzg_open_all_batch", dt.ptr, self._ptr(dti), self._ptr(dc), log_n, m, self._ptr(dy), dp.ptr, dpi.ptr)
+        else:
+            self._call("sylow_hip_kzg_open_all_batch_tuned", dt.ptr, self._ptr(dti), self._ptr(dc), log_n, m, int(max_blocks), self._ptr(dy), dp.ptr, dpi.ptr)
+        y = np.ascontiguousarray(dy.download()[:m].transpose(0, 2, 1)) if want_y else None
+        return y, np.ascontiguousarray(dp.download()[:m].transpose(0, 2, 1)), dpi.download()[:m]
+
     # ---- Groth16, the prover's side.  A sparse matrix is CSR: (row_ptr [rows + 1], col [nnz], val [nnz, 4]); Fr batches are [m, n, 4] on the
     # host and [m][4][n] on the device; any 256-bit words, taken mod r ----
     def _csr_up(self, csr):

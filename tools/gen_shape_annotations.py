@@ -142,6 +142,9 @@ S["kzg_open_evals_batch"] = f"srs_lagrange_xy=u64[8*2**log_n] evals={EVALS} z=u6
 G1PTS = "u64[8*2**log_n*m]"               # m arrays of n = 2^log_n affine G1 points, and their flags
 S["g1_ntt_batch"] = S["g1_ntt_batch_tuned"] = f"p_xy={G1PTS} p_inf=u8[2**log_n*m]? out_xy={G1PTS} out_inf=u8[2**log_n*m]"
 S["kzg_srs_lagrange"] = "srs_g1_xy=u64[8*2**log_n] out_xy=u64[8*2**log_n] out_inf=u8[2**log_n]"
+S["kzg_open_all_prepare"] = "srs_g1_xy=u64[8*2**log_n] table_xy=u64[16*2**log_n] table_inf=u8[2*2**log_n]"
+S["kzg_open_all_batch"] = S["kzg_open_all_batch_tuned"] = (f"table_xy=u64[16*2**log_n] table_inf=u8[2*2**log_n]? coeffs={EVALS} y_out={EVALS}? "
+                                                           f"pi_xy={G1PTS} pi_inf=u8[2**log_n*m]")
 CSR = lambda x, rows, nnz: f"{x}row_ptr=u64[{rows}+1] {x}col=u64[{nnz}]? {x}val=u64[4*{nnz}]?"      # col / val may be NULL when nnz = 0
 S["fr_spmv_batch"] = S["fr_spmv_batch_tuned"] = CSR("", "rows", "nnz") + " w=u64[4*n_cols*m]? out=u64[4*n_out*m]"
 S["groth16_quotient_batch"] = f"a={EVALS} b={EVALS} c={EVALS} h_out={EVALS}"
