@@ -978,6 +978,80 @@ int32_t sylow_hip_kzg_open_all_batch(const uint64_t* table_xy, const uint8_t* ta
 int32_t sylow_hip_kzg_open_all_batch_tuned(const uint64_t* table_xy, const uint8_t* table_inf, const uint64_t* coeffs, int32_t log_n, size_t m,
                                            int64_t max_blocks, uint64_t* y_out, uint64_t* pi_xy, uint8_t* pi_inf, void* stream);
 
+/* ---- KZG, folded openings: many polynomials opened at one point under ONE proof (kzg_multi.hip; tiles, grids, the flush length, scratch and
+ * the chunks of the combined commitments in kzg_multi_plan.hpp) ---------------------------------------------------------------------------
+ * What a PLONK-style prover sends: at the evaluation challenge it opens a dozen polynomials, at a shifted point one or two more, and it sends
+ * ONE proof per point, formed from the polynomials folded under a challenge gamma.  The m polynomials fall into G GROUPS of consecutive
+ * polynomials; group g holds the polynomials group_start[g] .. group_start[g + 1] - 1, is opened at z_g and folded under gamma_g.  With
+ * i = j - group_start[g] the index of polynomial j inside its group, and 0^0 = 1:
+ *     F_g = sum_j gamma_g^i f_j        y_j = f_j(z_g)        pi_g = commit((F_g - F_g(z_g)) / (X - z_g))
+ *     C_F,g = sum_j gamma_g^i C_j      y_F,g = sum_j gamma_g^i y_j
+ * and (C_F,g, z_g, y_F,g, pi_g) is a row of the verifiers of the KZG block above.  An empty group gives F = 0, y_F = 0, C_F = the identity
+ * ((0, 1) + its flag) and pi = the identity.
+ * Conventions (those of the KZG prover blocks above):
+ *   polynomials: coeffs [m][4][len], or evals [m][4][n] with n = 2^log_n, as in those blocks.
+ *   group_start: a HOST array of G + 1 uint64_t -- the host plans scratch, padded layouts and per-group routes from it, and no call of this
+ *              library synchronises a stream to read an argument.  Non-decreasing, group_start[0] = 0, group_start[G] = m; anything else is
+ *              SYLOW_HIP_E_ARG before anything is enqueued.  An empty group is legal.  IT IS READ BEFORE THE CALL RETURNS and may be freed or
+ *              overwritten then: its values reach the device inside kernel arguments (256 offsets per launch of a one-block kernel that
+ *              stores them to leased scratch), and a launch copies its arguments before it returns -- no copy engine, no pinned staging
+ *              buffer, no synchronisation.
+ *   scalars:   z [4][G], gamma [4][G], weights [4][m] and y [4][m] are DEVICE arrays; ANY 256-bit words, taken mod r.  Outputs are canonical
+ *              words below r.
+ *   points:    [8][.] affine SoA words + flags, the identity as (0, 1) + its flag; taken as given; coordinate words >= p are reduced like
+ *              Fp::new, as everywhere.
+ *   calls:     stream-ordered, no host synchronisation; scratch leased per call.  G = 0 or m = 0 is the EMPTY BATCH: OK, nothing launched,
+ *              nothing written (not even the zeros of empty groups).  NULL where an array is required, or len = 0: SYLOW_HIP_E_ARG, no
+ *              launch, nothing written.
+ *   soundness: THE LIBRARY DRAWS NO CHALLENGE.  gamma_g must be drawn AFTER the commitments C_j and the claimed values y_j are fixed (a
+ *              transcript hash of them); the weights of sylow_hip_kzg_batch_verify_weighted over the folded rows must be drawn AFTER the
+ *              proofs pi_g are fixed.  A gamma known before the y_j are chosen lets a prover cancel a wrong value against another. */
+/* out [G][4][len], out_g[k] = sum_{j in group g} weights_j a_j[k] mod r for a [m][4][len]; an empty group gives zeros.  The linear
+ * combination of polynomials over Fr: the fold above with weights = the powers of gamma, a prover's linearisation polynomial with arbitrary
+ * weights.  out must NOT overlap a (the byte ranges are compared: SYLOW_HIP_E_ARG).  ONE launch over (group, tile of 256 columns) work
+ * items: a lane owns one coefficient column and walks the polynomials of its group, the four limb planes are read coalesced along k, the
+ * weight of a polynomial is fetched once per block (16 at a time through LDS), and a lane adds up to 16 products UNREDUCED in 16 limbs per
+ * Barrett reduction (the multiply-accumulate of sylow_hip_fr_spmv_batch; both factors are brought to canonical form at the load).  Group and
+ * tile counts past the grid's caps are walked with a stride. */
+/* @shape a=u64[4*len*m] weights=u64[4*m] group_start=u64[G+1] out=u64[4*len*G] */
+int32_t sylow_hip_fr_lincomb_batch(const uint64_t* a, size_t len, size_t m, const uint64_t* weights, const uint64_t* group_start, size_t G,
+                                   uint64_t* out, void* stream);
+/* out [4][m], out_j = gamma_g^i for polynomial j of group g, i = j - group_start[g]; gamma = 0 gives 1, 0, 0, ...  One lane per polynomial,
+ * square-and-multiply on i: the lanes stay independent and a lane runs at most 2 log2(i) products, where a walk along the group is serial
+ * in its length. */
+/* @shape gamma=u64[4*G] group_start=u64[G+1] out=u64[4*m] */
+int32_t sylow_hip_fr_group_powers_batch(const uint64_t* gamma, const uint64_t* group_start, size_t G, size_t m, uint64_t* out, void* stream);
+/* y_out [4][m] and pi [8][G] + flags [G] of the block above, from coefficients under the monomial SRS srs_g1_xy [8][len].  The powers and z_g
+ * spread to its polynomials (one small launch); y through sylow_hip_kzg_quotient_batch with q_out = NULL; the linear combination into leased
+ * scratch (32 G len bytes); then sylow_hip_kzg_open_batch over the G folded polynomials: pi_g is word for word what that call yields for
+ * F_g.  A group whose F_g is constant -- an empty group and a fold that cancels to zero included -- gives the flagged identity. */
+/* @shape srs_g1_xy=u64[8*len] coeffs=u64[4*len*m] group_start=u64[G+1] z=u64[4*G] gamma=u64[4*G] y_out=u64[4*m] pi_xy=u64[8*G] pi_inf=u8[G] */
+int32_t sylow_hip_kzg_open_multi_batch(const uint64_t* srs_g1_xy, const uint64_t* coeffs, size_t len, size_t m, const uint64_t* group_start, size_t G,
+                                       const uint64_t* z, const uint64_t* gamma, uint64_t* y_out, uint64_t* pi_xy, uint8_t* pi_inf, void* stream);
+/* The same from evaluation form under the Lagrange-basis SRS srs_lagrange_xy [8][n]: y through sylow_hip_kzg_quotient_evals_batch with
+ * q_out = NULL (points inside the domain included), the same linear combination over the VALUES (the fold is linear), then
+ * sylow_hip_kzg_open_evals_batch over the G folded rows.  The words are those sylow_hip_kzg_open_multi_batch yields for the interpolated
+ * coefficients under the monomial SRS of the same tau.  log_n < 0 or > 28: SYLOW_HIP_E_ARG. */
+/* @shape srs_lagrange_xy=u64[8*2**log_n] evals=u64[4*2**log_n*m] group_start=u64[G+1] z=u64[4*G] gamma=u64[4*G] y_out=u64[4*m] pi_xy=u64[8*G] pi_inf=u8[G] */
+int32_t sylow_hip_kzg_open_multi_evals_batch(const uint64_t* srs_lagrange_xy, const uint64_t* evals, int32_t log_n, size_t m, const uint64_t* group_start,
+                                             size_t G, const uint64_t* z, const uint64_t* gamma, uint64_t* y_out, uint64_t* pi_xy, uint8_t* pi_inf,
+                                             void* stream);
+/* The verifier's half: cf_xy [8][G] + cf_inf [G] = C_F and yf [4][G] = y_F from the commitments c_xy [8][m] (+ optional flags) and the claimed
+ * values y [4][m].  The powers; the m terms laid out term-major, every group padded to the longest with (identity, scalar 0), through ONE
+ * sylow_hip_g1_scalar_mul_batch and a segmented sum, in chunks of whole groups that fit sylow_hip_set_scratch_limit at about 1.3 KB per
+ * padded slot; a group at or above sylow_hip_g1_msm's crossover (or too long for the limit on its own) goes through sylow_hip_g1_msm.  The
+ * words are the canonical affine words of one group element: the same on every route and for every chunking.  y_F is a modular sum from one
+ * small launch (a block per group). */
+/* @shape c_xy=u64[8*m] c_inf=u8[m]? y=u64[4*m] group_start=u64[G+1] gamma=u64[4*G] cf_xy=u64[8*G] cf_inf=u8[G] yf=u64[4*G] */
+int32_t sylow_hip_kzg_combine_openings_batch(const uint64_t* c_xy, const uint8_t* c_inf, const uint64_t* y, size_t m, const uint64_t* group_start, size_t G,
+                                             const uint64_t* gamma, uint64_t* cf_xy, uint8_t* cf_inf, uint64_t* yf, void* stream);
+/* ok [G]: sylow_hip_kzg_combine_openings_batch into leased scratch, then sylow_hip_kzg_verify_batch over the G rows (C_F,g, z_g, y_F,g, pi_g).
+ * The one-boolean form needs no call of its own: combine, then sylow_hip_kzg_batch_verify_weighted over the G rows. */
+/* @shape tau_g2_xy=u64[16] c_xy=u64[8*m] c_inf=u8[m]? y=u64[4*m] group_start=u64[G+1] z=u64[4*G] gamma=u64[4*G] pi_xy=u64[8*G] pi_inf=u8[G]? ok=u8[G] */
+int32_t sylow_hip_kzg_verify_multi_batch(const uint64_t* tau_g2_xy, const uint64_t* c_xy, const uint8_t* c_inf, const uint64_t* y, size_t m,
+                                         const uint64_t* group_start, size_t G, const uint64_t* z, const uint64_t* gamma, const uint64_t* pi_xy,
+                                         const uint8_t* pi_inf, uint8_t* ok, void* stream);
+
 /* ---- Groth16, the prover's side: R1CS products, the quotient and the proof under ONE proving key (groth16_prove.hip; lanes per row, grids,
  * scratch and chunks in groth16_prove_plan.hpp) ------------------------------------------------------------------------------------------
  * Conventions of the calls below (those of the transforms and of the KZG prover block):

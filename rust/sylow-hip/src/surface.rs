@@ -1054,6 +1054,116 @@ pub fn kzg_open_evals(dev: &Device, srs_lagrange: &DeviceG1, evals: &KzgPolys, z
     })?;
     Ok((dev.download_aos::<4>(&y, evals.m)?, pi))
 }
+/// Groups of consecutive polynomials for the folded openings: `offsets` holds G + 1 values, non-decreasing, from 0 to m; group g holds the
+/// polynomials offsets[g] .. offsets[g + 1] - 1 (an empty group is legal).  A HOST array: the library reads it before a call returns.
+pub struct KzgGroups {
+    pub offsets: Vec<u64>,
+}
+impl KzgGroups {
+    pub fn from_sizes(sizes: &[usize]) -> Self {
+        let mut offsets = vec![0u64];
+        for s in sizes {
+            offsets.push(offsets[offsets.len() - 1] + *s as u64);
+        }
+        KzgGroups { offsets }
+    }
+    pub fn groups(&self) -> usize {
+        self.offsets.len() - 1
+    }
+    fn fits(&self, m: usize) {
+        assert!(self.offsets[0] == 0 && self.offsets[self.groups()] == m as u64 && self.offsets.windows(2).all(|w| w[0] <= w[1]), "offsets run from 0 to m");
+    }
+}
+/// out_g = sum_{j in group g} weights_j a_j over Fr for m arrays in the layout of `KzgPolys` (`sylow_hip_fr_lincomb_batch`): G arrays.
+pub fn fr_lincomb(dev: &Device, a: &KzgPolys, weights: &[Fr], groups: &KzgGroups) -> Result<KzgPolys, HipError> {
+    groups.fits(a.m);
+    assert!(weights.len() == a.m);
+    let g = groups.groups();
+    let dw = dev.upload_soa::<4>(&fr_words(weights))?;
+    let out = dev.alloc::<u64>(4 * a.len * g)?;
+    // SAFETY: m arrays of len words x 4 in, 4 * m weight words, G + 1 host offsets, G arrays out in a buffer of their own.
+    device::check(unsafe { ffi::sylow_hip_fr_lincomb_batch(a.words.as_ptr(), a.len, a.m, dw.as_ptr(), groups.offsets.as_ptr(), g, out.as_mut_ptr(), dev.stream) })?;
+    Ok(KzgPolys { words: out, len: a.len, m: g })
+}
+/// gamma_g^i for polynomial i of group g, as [4][m] words on the host (`sylow_hip_fr_group_powers_batch`).
+pub fn fr_group_powers(dev: &Device, gamma: &[Fr], groups: &KzgGroups, m: usize) -> Result<Vec<[u64; 4]>, HipError> {
+    groups.fits(m);
+    let g = groups.groups();
+    assert!(gamma.len() == g);
+    let dg = dev.upload_soa::<4>(&fr_words(gamma))?;
+    let out = dev.alloc::<u64>(4 * m)?;
+    // SAFETY: 4 * G words of gamma, G + 1 host offsets, 4 * m words out.
+    device::check(unsafe { ffi::sylow_hip_fr_group_powers_batch(dg.as_ptr(), groups.offsets.as_ptr(), g, m, out.as_mut_ptr(), dev.stream) })?;
+    Ok(dev.download_aos::<4>(&out, m)?)
+}
+/// Every group of polynomials opened at its point z_g under ONE proof folded with gamma_g (`sylow_hip_kzg_open_multi_batch`): (y as [4][m]
+/// words, the G proofs).  gamma is drawn by the caller AFTER the commitments and the claimed values are fixed.
+pub fn kzg_open_multi(dev: &Device, srs: &DeviceG1, p: &KzgPolys, groups: &KzgGroups, z: &[Fr], gamma: &[Fr]) -> Result<(Vec<[u64; 4]>, DeviceG1), HipError> {
+    kzg_srs_fits(srs, p);
+    groups.fits(p.m);
+    let g = groups.groups();
+    assert!(z.len() == g && gamma.len() == g);
+    let (dz, dg) = (dev.upload_soa::<4>(&fr_words(z))?, dev.upload_soa::<4>(&fr_words(gamma))?);
+    let y = dev.alloc::<u64>(4 * p.m)?;
+    let pi = DeviceG1 { xy: dev.alloc::<u64>(8 * g)?, inf: dev.alloc::<u8>(g)?, n: g };
+    // SAFETY: len SRS points, m polynomials of len coefficients, G + 1 host offsets, 4 * G words of z and gamma, 4 * m words of y, G points and flags out.
+    device::check(unsafe {
+        ffi::sylow_hip_kzg_open_multi_batch(srs.xy.as_ptr(), p.words.as_ptr(), p.len, p.m, groups.offsets.as_ptr(), g, dz.as_ptr(), dg.as_ptr(), y.as_mut_ptr(),
+                                            pi.xy.as_mut_ptr(), pi.inf.as_mut_ptr(), dev.stream)
+    })?;
+    Ok((dev.download_aos::<4>(&y, p.m)?, pi))
+}
+/// The same from evaluation form under the Lagrange-basis SRS (`sylow_hip_kzg_open_multi_evals_batch`).
+pub fn kzg_open_multi_evals(dev: &Device, srs_lagrange: &DeviceG1, evals: &KzgPolys, groups: &KzgGroups, z: &[Fr], gamma: &[Fr])
+                            -> Result<(Vec<[u64; 4]>, DeviceG1), HipError> {
+    kzg_srs_fits(srs_lagrange, evals);
+    groups.fits(evals.m);
+    let g = groups.groups();
+    assert!(z.len() == g && gamma.len() == g);
+    let log_n = radix2_log(evals.len);
+    let (dz, dg) = (dev.upload_soa::<4>(&fr_words(z))?, dev.upload_soa::<4>(&fr_words(gamma))?);
+    let y = dev.alloc::<u64>(4 * evals.m)?;
+    let pi = DeviceG1 { xy: dev.alloc::<u64>(8 * g)?, inf: dev.alloc::<u8>(g)?, n: g };
+    // SAFETY: as kzg_open_multi with 2^log_n values per polynomial.
+    device::check(unsafe {
+        ffi::sylow_hip_kzg_open_multi_evals_batch(srs_lagrange.xy.as_ptr(), evals.words.as_ptr(), log_n, evals.m, groups.offsets.as_ptr(), g, dz.as_ptr(),
+                                                  dg.as_ptr(), y.as_mut_ptr(), pi.xy.as_mut_ptr(), pi.inf.as_mut_ptr(), dev.stream)
+    })?;
+    Ok((dev.download_aos::<4>(&y, evals.m)?, pi))
+}
+/// The verifier's folded rows (`sylow_hip_kzg_combine_openings_batch`): C_F,g = sum_j gamma_g^i C_j and y_F,g = sum_j gamma_g^i y_j as
+/// [4][G] device words -- with z and the proofs, the rows `kzg_verify_once` and `kzg_batch_verify_weighted` take.
+pub fn kzg_combine_openings(dev: &Device, c: &DeviceG1, y: &[Fr], groups: &KzgGroups, gamma: &[Fr]) -> Result<(DeviceG1, DeviceBuf<u64>), HipError> {
+    let m = c.n;
+    groups.fits(m);
+    let g = groups.groups();
+    assert!(y.len() == m && gamma.len() == g);
+    let (dy, dg) = (dev.upload_soa::<4>(&fr_words(y))?, dev.upload_soa::<4>(&fr_words(gamma))?);
+    let cf = DeviceG1 { xy: dev.alloc::<u64>(8 * g)?, inf: dev.alloc::<u8>(g)?, n: g };
+    let yf = dev.alloc::<u64>(4 * g)?;
+    // SAFETY: m points with flags, 4 * m words of y, G + 1 host offsets, 4 * G words of gamma, G points, flags and values out.
+    device::check(unsafe {
+        ffi::sylow_hip_kzg_combine_openings_batch(c.xy.as_ptr(), c.inf.as_ptr(), dy.as_ptr(), m, groups.offsets.as_ptr(), g, dg.as_ptr(), cf.xy.as_mut_ptr(),
+                                                  cf.inf.as_mut_ptr(), yf.as_mut_ptr(), dev.stream)
+    })?;
+    Ok((cf, yf))
+}
+/// ok[g] for every folded row (`sylow_hip_kzg_verify_multi_batch`): the combination, then the per-opening check over the G rows.
+pub fn kzg_verify_multi(dev: &Device, tau_g2: &DeviceG2, c: &DeviceG1, y: &[Fr], groups: &KzgGroups, z: &[Fr], gamma: &[Fr], pi: &DeviceG1)
+                        -> Result<Vec<bool>, HipError> {
+    let m = c.n;
+    groups.fits(m);
+    let g = groups.groups();
+    assert!(tau_g2.n == 1 && y.len() == m && z.len() == g && gamma.len() == g && pi.n == g);
+    let (dy, dz, dg) = (dev.upload_soa::<4>(&fr_words(y))?, dev.upload_soa::<4>(&fr_words(z))?, dev.upload_soa::<4>(&fr_words(gamma))?);
+    let ok = dev.alloc::<u8>(g)?;
+    // SAFETY: one G2 point; m points with flags, 4 * m words of y, G + 1 host offsets, 4 * G words of z and gamma, G proofs with flags, G flags out.
+    device::check(unsafe {
+        ffi::sylow_hip_kzg_verify_multi_batch(tau_g2.xy.as_ptr(), c.xy.as_ptr(), c.inf.as_ptr(), dy.as_ptr(), m, groups.offsets.as_ptr(), g, dz.as_ptr(), dg.as_ptr(),
+                                              pi.xy.as_ptr(), pi.inf.as_ptr(), ok.as_mut_ptr(), dev.stream)
+    })?;
+    Ok(dev.download(&ok)?.into_iter().map(|v| v != 0).collect())
+}
 /// log2 of a radix-2 domain's size (at most 2^28 points: r - 1 = 2^28 * odd)
 fn radix2_log(n: usize) -> i32 {
     assert!(n.is_power_of_two() && n <= 1 << 28, "a radix-2 domain of at most 2^28 points");

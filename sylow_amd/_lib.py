@@ -173,6 +173,12 @@ SIGNATURES = {
     "sylow_hip_fr_batch_inv": [c_u64p, c_u64p, c_sz, c_vp],
     "sylow_hip_kzg_quotient_evals_batch": [c_u64p, c_i32, c_sz, c_u64p, c_u64p, c_u64p, c_vp],
     "sylow_hip_kzg_open_evals_batch": [c_u64p, c_u64p, c_i32, c_sz, c_u64p, c_u64p, c_u64p, c_u8p, c_vp],
+    "sylow_hip_fr_lincomb_batch": [c_u64p, c_sz, c_sz, c_u64p, c_u64p, c_sz, c_u64p, c_vp],
+    "sylow_hip_fr_group_powers_batch": [c_u64p, c_u64p, c_sz, c_sz, c_u64p, c_vp],
+    "sylow_hip_kzg_open_multi_batch": [c_u64p, c_u64p, c_sz, c_sz, c_u64p, c_sz, c_u64p, c_u64p, c_u64p, c_u64p, c_u8p, c_vp],
+    "sylow_hip_kzg_open_multi_evals_batch": [c_u64p, c_u64p, c_i32, c_sz, c_u64p, c_sz, c_u64p, c_u64p, c_u64p, c_u64p, c_u8p, c_vp],
+    "sylow_hip_kzg_combine_openings_batch": [c_u64p, c_u8p, c_u64p, c_sz, c_u64p, c_sz, c_u64p, c_u64p, c_u8p, c_u64p, c_vp],
+    "sylow_hip_kzg_verify_multi_batch": [c_u64p, c_u64p, c_u8p, c_u64p, c_sz, c_u64p, c_sz, c_u64p, c_u64p, c_u64p, c_u8p, c_u8p, c_vp],
     "sylow_hip_fr_spmv_batch": [c_u64p, c_u64p, c_u64p, c_sz, c_sz, c_u64p, c_sz, c_sz, c_sz, c_u64p, c_vp],
     "sylow_hip_fr_spmv_batch_tuned": [c_u64p, c_u64p, c_u64p, c_sz, c_sz, c_u64p, c_sz, c_sz, c_sz, c_i32, c_u64p, c_vp],
     "sylow_hip_groth16_quotient_batch": [c_u64p, c_u64p, c_u64p, c_i32, c_sz, c_u64p, c_vp],

@@ -635,6 +635,37 @@ class KzgVerifier:
         return engine().kzg_batch_verify_weighted(self.tau_g2.xy, c.xy, self._words(z), self._words(y), pi.xy, self._words(weights), c.infinity, pi.infinity)[1]
 
 
+    def combine(self, c: G1Affine, y, groups, gamma):
+        """The folded rows of openings that share a point: with the m commitments `c` and claimed values `y` in G groups of consecutive
+        polynomials (`groups`: the group SIZES, see group_offsets) and one challenge gamma_g per group, (C_F: G1Affine of G points, y_F [G, 4])
+        with C_F,g = sum_j gamma_g^i C_j and y_F,g = sum_j gamma_g^i y_j, i the index inside the group
+        (sylow_hip_kzg_combine_openings_batch).  (C_F, z, y_F, pi) is then the tuple verify / verify_weighted take.  gamma must have been
+        drawn AFTER c and y were fixed; the library draws no challenge."""
+        cf_xy, cf_inf, yf = engine().kzg_combine_openings(c.xy, self._words(y), group_offsets(groups, len(c)), self._words(gamma), c.infinity)
+        return G1Affine(cf_xy, cf_inf), yf
+
+    def verify_multi(self, c: G1Affine, y, groups, z, gamma, pi: G1Affine) -> np.ndarray:
+        """ok[g] for every group: the folded row (C_F,g, z_g, y_F,g, pi_g) checked under tau_g2 (sylow_hip_kzg_verify_multi_batch); `groups`
+        are the group SIZES, z and gamma hold one value per group, pi one proof per group (KzgProver.open_multi)."""
+        return engine().kzg_verify_multi(self.tau_g2.xy, c.xy, self._words(y), group_offsets(groups, len(c)), self._words(z), self._words(gamma),
+                                         pi.xy, c.infinity, pi.infinity).astype(bool)
+
+    def verify_multi_weighted(self, c: G1Affine, y, groups, z, gamma, pi: G1Affine, weights) -> bool:
+        """"are ALL the folded rows valid?" as ONE boolean: combine, then verify_weighted over the G rows.  One weight per group, drawn AFTER
+        the proofs pi are fixed (and gamma after c and y)."""
+        cf, yf = self.combine(c, y, groups, gamma)
+        return self.verify_weighted((cf, self._words(z), yf, pi), weights)
+
+
+def group_offsets(groups, m: int) -> np.ndarray:
+    """`groups` in this module is the list of group SIZES (e.g. [12, 2]: twelve polynomials opened at the first point, two at the second; a
+    size of 0 is legal); the C ABI and the Engine take the G + 1 OFFSETS, which this returns.  ValueError unless the sizes add up to m."""
+    sizes = [int(x) for x in groups]
+    if any(x < 0 for x in sizes) or sum(sizes) != m:
+        raise ValueError(f"groups: non-negative group sizes that add up to the {m} polynomials")
+    return np.cumsum([0] + sizes).astype(np.uint64)
+
+
 class KzgProver:
     """The prover's half of a BN254 KZG SRS: srs_g1 = (tau^k G1gen) for k = 0 .. len - 1.  `polys` below is [m, len, 4] words or m lists of
     Python ints (lowest degree first, padded with zeros to the length of the SRS by the caller if shorter) -- any 256-bit values, taken mod
@@ -665,6 +696,14 @@ class KzgProver:
         y, pi_xy, pi_inf = engine().kzg_open(self.srs_g1.xy, self._polys(polys), KzgVerifier._words(z))
         return y, G1Affine(pi_xy, pi_inf)
 
+    def open_multi(self, polys, groups, z, gamma):
+        """(y [m, 4] words, pi: G1Affine of G points): the polynomials in G groups of consecutive ones (`groups`: the group SIZES, see
+        group_offsets), group g opened at z_g under ONE proof folded with gamma_g -- y_j = f_j(z_g) and pi_g the proof of
+        F_g = sum_j gamma_g^i f_j at z_g, word for word open(F_g, z_g) (sylow_hip_kzg_open_multi_batch).  gamma must be drawn AFTER the
+        commitments and the y_j are fixed.  (commit(polys), y, groups, z, gamma, pi) is what KzgVerifier.verify_multi takes."""
+        a = self._polys(polys)
+        y, pi_xy, pi_inf = engine().kzg_open_multi(self.srs_g1.xy, a, group_offsets(groups, a.shape[0]), KzgVerifier._words(z), KzgVerifier._words(gamma))
+        return y, G1Affine(pi_xy, pi_inf)
 
     def open_all(self, polys):
         """The openings of every f_j at ALL n = len(srs_g1) = 2^log_n points of its domain at once, in n log n (sylow_hip_kzg_open_all_batch,
@@ -745,6 +784,14 @@ class KzgEvalProver:
         y, pi_xy, pi_inf = engine().kzg_open_evals(self.srs_lagrange.xy, self._evals(evals), KzgVerifier._words(z))
         return y, G1Affine(pi_xy, pi_inf)
 
+    def open_multi(self, evals, groups, z, gamma):
+        """KzgProver.open_multi from evaluation form (sylow_hip_kzg_open_multi_evals_batch): the same words as for the interpolated
+        coefficients under the monomial SRS of the same tau; z_g inside the domain or not.  `groups`: the group SIZES."""
+        a = self._evals(evals)
+        y, pi_xy, pi_inf = engine().kzg_open_multi_evals(self.srs_lagrange.xy, a, group_offsets(groups, a.shape[0]), KzgVerifier._words(z),
+                                                         KzgVerifier._words(gamma))
+        return y, G1Affine(pi_xy, pi_inf)
+
 
 def _fr_arrays(values):
     """a numpy uint64 array is words ([m, n, 4] or [n, 4]); anything else is Python ints, [m][n] or [n]"""
@@ -755,6 +802,16 @@ def _fr_arrays(values):
         raise ValueError("ntt: ints as [n] or [m][n], words as a uint64 array [n, 4] or [m, n, 4]")
     words = fp(list(a.reshape(-1)))
     return words.reshape(a.shape + (4,))
+
+
+def fr_lincomb(arrays, weights, groups) -> np.ndarray:
+    """out_g = sum_{j in group g} weights_j a_j over Fr: `arrays` [m, len, 4] words or m lists of Python ints, one weight per array, `groups`
+    the group SIZES (see group_offsets); [G, len, 4] canonical words, zeros for an empty group (sylow_hip_fr_lincomb_batch).  The fold of a
+    KZG multi-opening with weights = the powers of gamma, a linearisation polynomial with arbitrary weights."""
+    a = _fr_arrays(arrays)
+    if a.ndim != 3:
+        raise ValueError("fr_lincomb: m arrays of one length")
+    return engine().fr_lincomb(a, KzgVerifier._words(weights), group_offsets(groups, a.shape[0]))
 
 
 def ntt(values, shift=None, inverse: bool = False, stages: int = -1) -> np.ndarray:

@@ -4,6 +4,7 @@
 //   and stream-ordered group calls, in chunks of whole witnesses.
 // Lanes per row, grids, scratch and chunks: groth16_prove_plan.hpp -- nothing here decides one.
 #include "host.hpp"
+#include "bn254_fr_acc.hpp"
 #include "bn254_groth16_zinv.hpp"
 #include "groth16_prove_plan.hpp"
 
@@ -19,24 +20,6 @@ BN_DEV Fp from_scalar(const Scalar& s) {
   return fp_from_limbs((u32)s.w[0], (u32)(s.w[0] >> 32), (u32)s.w[1], (u32)(s.w[1] >> 32), (u32)s.w[2], (u32)(s.w[2] >> 32), (u32)s.w[3], (u32)(s.w[3] >> 32));
 }
 
-// acc += a b, no reduction.  THE BOUND: a and b are canonical, below r < 2^254, so a product is below r^2 < 2^508, and so is a residue the
-// accumulator was folded to (r < r^2).  The caller adds at most SPMV_FLUSH = 16 such terms between two folds: acc < 16 r^2 < 2^512, which is
-// what 16 limbs hold and what fr_reduce_wide takes.  Hence the top limb takes the last carry without a carry out, and the column sums below
-// stay in the 64 + 32 bits of (c, ovf): a column has at most 8 products and one limb of acc.
-BN_DEV void mul_acc(u32 (&acc)[16], const Fp& a, const Fp& b) {
-  u64 c = 0;
-  u32 ovf = 0;
-#pragma unroll
-  for (int k = 0; k < 15; ++k) {
-    c += acc[k];                                              // c < 2^36 here: the carry of the column before
-#pragma unroll
-    for (int i = (k > 7 ? k - 7 : 0); i <= (k < 7 ? k : 7); ++i) mac(c, ovf, a.v[i], b.v[k - i]);
-    acc[k] = (u32)c;
-    c = (c >> 32) | ((u64)ovf << 32);
-    ovf = 0;
-  }
-  acc[15] += (u32)c;
-}
 BN_DEV Fp shfl_xor_fp(const Fp& a, int off) {
   Fp r;
 #pragma unroll

@@ -1107,6 +1107,96 @@ class Engine:
         self._call("sylow_hip_kzg_open_evals_batch", ds.ptr, self._ptr(dc), log_n, m, self._ptr(dz), dy.ptr, dp.ptr, dpi.ptr)
         return self.from_device_soa(dy)[:m], self.from_device_soa(dp)[:m], dpi.download()[:m]
 
+    # ---- KZG, folded openings.  groups: the G + 1 OFFSETS of the groups of consecutive polynomials (0 .. m, non-decreasing; a host array, read
+    # before the call returns); z, gamma [G, 4]; the polynomials as in the prover's calls above ----
+    @staticmethod
+    def _kzg_groups(groups, m):
+        gs = np.ascontiguousarray([int(x) for x in groups], dtype=np.uint64)
+        if gs.ndim != 1 or gs.size < 1 or int(gs[0]) != 0 or int(gs[-1]) != m or (gs[1:] < gs[:-1]).any():
+            raise ValueError(f"groups: G + 1 non-decreasing offsets from 0 to m = {m}")
+        return gs, gs.size - 1
+
+    def fr_lincomb(self, a, weights, groups):
+        """out_g = sum_{j in group g} weights_j a_j over Fr for a [m, len, 4] and weights [m, 4]: [G, len, 4] canonical words
+        (sylow_hip_fr_lincomb_batch); an empty group gives zeros."""
+        a, w = self._kzg_polys(a), _aos(weights, 4)
+        m, ln = a.shape[0], a.shape[1]
+        gs, G = self._kzg_groups(groups, m)
+        assert w.shape[0] == m
+        if not m or not G:
+            return np.zeros((G, ln, 4), dtype=np.uint64)
+        da, dw, do = self._kzg_polys_up(a), self.to_device_soa(w, 4), self.empty((G, 4, ln))
+        self._call("sylow_hip_fr_lincomb_batch", da.ptr, ln, m, dw.ptr, gs.ctypes.data, G, do.ptr)
+        return np.ascontiguousarray(do.download().transpose(0, 2, 1))
+
+    def fr_group_powers(self, gamma, groups, m):
+        """[m, 4] words: gamma_g^i for polynomial i of group g (sylow_hip_fr_group_powers_batch); 0^0 = 1."""
+        gamma = _aos(gamma, 4)
+        gs, G = self._kzg_groups(groups, m)
+        assert gamma.shape[0] == G
+        if not m or not G:
+            return np.zeros((m, 4), dtype=np.uint64)
+        dg, do = self.to_device_soa(gamma, 4), self.empty((4, m))
+        self._call("sylow_hip_fr_group_powers_batch", dg.ptr, gs.ctypes.data, G, m, do.ptr)
+        return self.from_device_soa(do)
+
+    def _kzg_open_multi(self, name, srs, a, size_arg, groups, z, gamma):
+        srs, z, gamma = _aos(srs, 8), _aos(z, 4), _aos(gamma, 4)
+        m, ln = a.shape[0], a.shape[1]
+        gs, G = self._kzg_groups(groups, m)
+        assert srs.shape[0] == ln and z.shape[0] == G and gamma.shape[0] == G
+        identity = np.zeros((G, 8), dtype=np.uint64)
+        identity[:, 4] = 1
+        if not m or not G:                                     # the empty batch: every group is empty
+            return np.zeros((m, 4), dtype=np.uint64), identity, np.ones(G, dtype=np.uint8)
+        dc, ds, dz, dg = self._kzg_polys_up(a), self.to_device_soa(srs, 8), self.to_device_soa(z, 4), self.to_device_soa(gamma, 4)
+        dy, dp, dpi = self.empty((4, m)), self.empty((8, G)), self.empty((G,), np.uint8)
+        self._call(name, ds.ptr, dc.ptr, size_arg, m, gs.ctypes.data, G, dz.ptr, dg.ptr, dy.ptr, dp.ptr, dpi.ptr)
+        return self.from_device_soa(dy), self.from_device_soa(dp), dpi.download()
+
+    def kzg_open_multi(self, srs_g1, polys, groups, z, gamma):
+        """Every group of polynomials opened at z_g under ONE proof folded with gamma_g (sylow_hip_kzg_open_multi_batch): (y [m, 4] with
+        y_j = f_j(z_g), pi [G, 8] affine words, pi flags [G]); pi_g is word for word kzg_open of F_g = sum_j gamma_g^i f_j."""
+        a = self._kzg_polys(polys)
+        return self._kzg_open_multi("sylow_hip_kzg_open_multi_batch", srs_g1, a, a.shape[1], groups, z, gamma)
+
+    def kzg_open_multi_evals(self, srs_lagrange, evals, groups, z, gamma):
+        """The same from evaluation form under the Lagrange-basis SRS (sylow_hip_kzg_open_multi_evals_batch)."""
+        a, m, n, log_n = self._kzg_evals(evals)
+        return self._kzg_open_multi("sylow_hip_kzg_open_multi_evals_batch", srs_lagrange, a, log_n, groups, z, gamma)
+
+    def _kzg_combine_args(self, c_xy, c_inf, y, groups, gamma):
+        c_xy, y, gamma = _aos(c_xy, 8), _aos(y, 4), _aos(gamma, 4)
+        m = c_xy.shape[0]
+        gs, G = self._kzg_groups(groups, m)
+        assert y.shape[0] == m and gamma.shape[0] == G
+        up = lambda x, w: self.to_device_soa(x, w) if x.shape[0] else None
+        return m, gs, G, (up(c_xy, 8), self._flags(c_inf, m) if m else None, up(y, 4), up(gamma, 4))
+
+    def kzg_combine_openings(self, c_xy, y, groups, gamma, c_inf=None):
+        """The verifier's folded rows (sylow_hip_kzg_combine_openings_batch): (C_F [G, 8] affine words, C_F flags [G], y_F [G, 4]) with
+        C_F,g = sum_j gamma_g^i C_j and y_F,g = sum_j gamma_g^i y_j; an empty group gives the identity and 0."""
+        m, gs, G, (dc, dci, dy, dg) = self._kzg_combine_args(c_xy, c_inf, y, groups, gamma)
+        if not m or not G:
+            identity = np.zeros((G, 8), dtype=np.uint64)
+            identity[:, 4] = 1
+            return identity, np.ones(G, dtype=np.uint8), np.zeros((G, 4), dtype=np.uint64)
+        dcf, dcfi, dyf = self.empty((8, G)), self.empty((G,), np.uint8), self.empty((4, G))
+        self._call("sylow_hip_kzg_combine_openings_batch", dc.ptr, self._ptr(dci), dy.ptr, m, gs.ctypes.data, G, dg.ptr, dcf.ptr, dcfi.ptr, dyf.ptr)
+        return self.from_device_soa(dcf), dcfi.download(), self.from_device_soa(dyf)
+
+    def kzg_verify_multi(self, tau_g2, c_xy, y, groups, z, gamma, pi_xy, c_inf=None, pi_inf=None):
+        """ok [G]: the folded row (C_F,g, z_g, y_F,g, pi_g) of every group checked under tau_g2 (sylow_hip_kzg_verify_multi_batch).  An empty
+        batch (m = 0) returns no flags."""
+        tau_g2, z, pi_xy = _aos(tau_g2, 16), _aos(z, 4), _aos(pi_xy, 8)
+        m, gs, G, (dc, dci, dy, dg) = self._kzg_combine_args(c_xy, c_inf, y, groups, gamma)
+        assert tau_g2.shape[0] == 1 and z.shape[0] == G and pi_xy.shape[0] == G
+        if not m or not G:
+            return np.zeros(0, dtype=np.uint8)
+        dtau, dz, dp, dpi, dok = self.to_device_soa(tau_g2, 16), self.to_device_soa(z, 4), self.to_device_soa(pi_xy, 8), self._flags(pi_inf, G), self.empty((G,), np.uint8)
+        self._call("sylow_hip_kzg_verify_multi_batch", dtau.ptr, dc.ptr, self._ptr(dci), dy.ptr, m, gs.ctypes.data, G, dz.ptr, dg.ptr, dp.ptr, self._ptr(dpi), dok.ptr)
+        return dok.download()
+
     # ---- Fr transforms on radix-2 domains.  values [m, n, 4] (or [n, 4]: one array), n = 2^log_n <= 2^28, any 256-bit words taken mod r ----
     def fr_ntt(self, values, inverse=False, shift=None, stages=-1):
         """forward: out_i = sum_k a_k (g w_n^i)^k; inverse: out_k = n^-1 g^-k sum_i a_i w_n^(-ik), natural order both ways, per array

@@ -145,6 +145,15 @@ S["kzg_srs_lagrange"] = "srs_g1_xy=u64[8*2**log_n] out_xy=u64[8*2**log_n] out_in
 S["kzg_open_all_prepare"] = "srs_g1_xy=u64[8*2**log_n] table_xy=u64[16*2**log_n] table_inf=u8[2*2**log_n]"
 S["kzg_open_all_batch"] = S["kzg_open_all_batch_tuned"] = (f"table_xy=u64[16*2**log_n] table_inf=u8[2*2**log_n]? coeffs={EVALS} y_out={EVALS}? "
                                                            f"pi_xy={G1PTS} pi_inf=u8[2**log_n*m]")
+GROUPS = "group_start=u64[G+1]"              # a HOST array: the offsets of the G groups of consecutive polynomials
+FOLDED = "z=u64[4*G] gamma=u64[4*G] y_out=u64[4*m] pi_xy=u64[8*G] pi_inf=u8[G]"
+S["fr_lincomb_batch"] = f"a=u64[4*len*m] weights=u64[4*m] {GROUPS} out=u64[4*len*G]"
+S["fr_group_powers_batch"] = f"gamma=u64[4*G] {GROUPS} out=u64[4*m]"
+S["kzg_open_multi_batch"] = f"srs_g1_xy=u64[8*len] {POLYS} {GROUPS} {FOLDED}"
+S["kzg_open_multi_evals_batch"] = f"srs_lagrange_xy=u64[8*2**log_n] evals={EVALS} {GROUPS} {FOLDED}"
+COMBINE = f"c_xy=u64[8*m] c_inf=u8[m]? y=u64[4*m] {GROUPS}"
+S["kzg_combine_openings_batch"] = COMBINE + " gamma=u64[4*G] cf_xy=u64[8*G] cf_inf=u8[G] yf=u64[4*G]"
+S["kzg_verify_multi_batch"] = "tau_g2_xy=u64[16] " + COMBINE + " z=u64[4*G] gamma=u64[4*G] pi_xy=u64[8*G] pi_inf=u8[G]? ok=u8[G]"
 CSR = lambda x, rows, nnz: f"{x}row_ptr=u64[{rows}+1] {x}col=u64[{nnz}]? {x}val=u64[4*{nnz}]?"      # col / val may be NULL when nnz = 0
 S["fr_spmv_batch"] = S["fr_spmv_batch_tuned"] = CSR("", "rows", "nnz") + " w=u64[4*n_cols*m]? out=u64[4*n_out*m]"
 S["groth16_quotient_batch"] = f"a={EVALS} b={EVALS} c={EVALS} h_out={EVALS}"
