@@ -188,8 +188,11 @@ def test_fp_pow_sqrt_is_square_vs_oracle(engine, coracle):
 
 def test_is_square_and_sqrt_structured_inputs(engine):
     """The Jacobi symbol steps on as many limbs as the wavefront still needs and the square-root chain fetches its window-table entries
-    ahead of use: inputs that exercise every limb count from the first step on (values below 2^32 .. 2^256), powers of two and their
-    neighbours, p - 2^b, guaranteed squares -- against Python's big-integer power (fp.rs:611-631)."""
+    ahead of use: VALUES below 2^32 .. 2^256, powers of two and their neighbours, p - 2^b, guaranteed squares -- against Python's
+    big-integer power (fp.rs:611-631).  The structure is in the value, not in what the kernel iterates on: load_fp turns each into its
+    Montgomery representative v 2^256 mod p, an ordinary 254-bit word (257 .. 381 Jacobi steps for the powers of two, like random
+    input), so the symbol always starts on eight limbs here.  tests/test_gpu_tails.py steers by representative and reaches the small
+    and sparse operands and the 507-step tail."""
     import random
     rnd = random.Random(4242)
     vals = [0, 1, 2, 3, 4, 5, 7, 8, P - 1, P - 2, P - 3, (P - 1) // 2, (P + 1) // 2, (P + 1) // 4]
