@@ -24,6 +24,11 @@
  *      G2 affine    : W = 16 (x.c0, x.c1, y.c0, y.c1) + uint8 infinity flag array
  *      G1 projective: W = 12 (x, y, z);  G2 projective: W = 24
  *    The canonical affine encoding of the identity is (0, 1, inf=1) (groups/group.rs:271-277).
+ *  - Memory: a call reads and writes only the extents the `@shape` line in front of its prototype gives (name=type[elements], `?` = may
+ *    be NULL): it never touches a byte outside them, so a neighbouring buffer is safe (alignment aside: only pointers as aligned as
+ *    hipMalloc's are tested).  On success every element of every output array is written, whatever
+ *    the buffer held before: flags and status bytes that are 0, identity rows as (0, 1), outputs of rows that failed.  Arrays declared
+ *    `const` are not modified.  (tests/test_gpu_memory_contract.py runs every entry point between guard bands under two fill patterns.)
  *  - `stream` is a hipStream_t passed as void* (NULL = the default stream).  Calls are
  *    asynchronous on that stream; use sylow_hip_stream_sync or your own events.
  *  - Threads: entry points may be called concurrently from several host threads and on several streams.  The
