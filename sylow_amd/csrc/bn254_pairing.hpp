@@ -116,7 +116,8 @@ BN_DEV Proj<typename O::F> proj_add(const Proj<typename O::F>& p, const Proj<typ
 // difference of two of them is a legal product operand as it stands (|limbs| < 2^29): the three cross terms of the addition come from
 // (a_i - a_j)(b_i - b_j) = t_i + t_j - (a_i b_j + a_j b_i) with no carry pass on the operands, sums of products get ONE carry pass, and values that
 // only feed products stay un-normalised where the leaf's bound (|limbs| products summing under 2.5 * 2^58 per column) allows.  Same group element
-// as proj_add / proj_double limb for limb after the canonical reduction (tests/test_gpu_group.py, test_gpu_small_rows.py compare affine results).
+// as proj_add / proj_double limb for limb after the canonical reduction (tests/test_gpu_group_law_bounds.py, test_gpu_small_rows.py compare affine results;
+// tests/test_group_law_model.py replays both formulas on the limb-exact host model at the bounds stated here).
 // Policy extras: lsub / ladd (no carry pass), norm, norm_x8 (8 a), norm_sub3 (a - 3 b), mul_b3_lazy (operand limbs up to 2^30 in magnitude).
 template <class O>
 BN_DEV Proj<typename O::F> proj_double_lazy(const Proj<typename O::F>& p) {

@@ -8,18 +8,13 @@ import numpy as np
 
 from helpers import M29, P, RP_INV, TOP_BOUND, crafted_fp12_rows, crafted_g1_points, crafted_g2_points, crafted_g2_projective, \
     crafted_values, fp_cbrt
+from group_law_model import internal_digits
 from oracle import coracle
 from oracle import pyref as R
 from test_gpu_multi_pairing import G1, G2
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
 import f29_model as M  # noqa: E402
-
-
-def internal_digits(x):
-    """the nine limbs the device holds for the canonical x: reduce(from_fp(x 2^256 mod p)), as w2_from_s2 / f29_from_fp + f29_reduce"""
-    words = M.int_to_words(x * (1 << 256) % P)
-    return M.reduce_terms([M.from_fp(words)], [1])
 
 
 def test_crafted_values_have_extreme_digits():
