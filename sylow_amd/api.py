@@ -657,6 +657,37 @@ class KzgVerifier:
         return self.verify_weighted((cf, self._words(z), yf, pi), weights)
 
 
+class KzgPointsVerifier:
+    """The verifier's key for openings of one polynomial at k points under one proof: srs_g1 = (tau^i G1gen) for i < k and srs_g2 =
+    (tau^i G2gen) for i <= k, in G2 proper; longer arrays are cut to what a call's k needs.  The library draws no challenge and takes the SRS
+    as given: the key is trusted input, and the points z are the caller's."""
+
+    def __init__(self, srs_g1: G1Affine, srs_g2: G2Affine):
+        if len(srs_g1) < 1 or len(srs_g2) != len(srs_g1) + 1 or srs_g1.infinity.any() or srs_g2.infinity.any():
+            raise ValueError("KzgPointsVerifier: k >= 1 powers in G1, k + 1 powers in G2, no identity among them")
+        self.srs_g1, self.srs_g2 = srs_g1, srs_g2
+
+    @staticmethod
+    def _rows(v):
+        a = np.asarray(v)
+        if a.dtype == object or a.ndim == 2:
+            rows = [list(r) for r in v]
+            a = fp([int(x) for r in rows for x in r]).reshape(len(rows), -1, 4) if rows else np.zeros((0, 1, 4), dtype=np.uint64)
+        if a.ndim != 3 or a.shape[2] != 4 or a.shape[1] < 1:
+            raise ValueError("z, y: [n, k, 4] words or n rows of k integers, k >= 1")
+        return a
+
+    def verify(self, c: G1Affine, z, y, pi: G1Affine) -> np.ndarray:
+        """ok[j] = [ e(C_j - R_j(tau) G1gen, G2gen) e(-pi_j, Z_j(tau) G2gen) == 1 ] and the k points of row j are distinct mod r, with
+        Z_j = prod_i (X - z[j, i]) and R_j the interpolant of the y[j, i] (sylow_hip_kzg_verify_points_batch).  A flagged pi (a zero
+        quotient) is legal: the row is then valid iff C_j = R_j(tau) G1gen.  Points are taken as given."""
+        z, y = self._rows(z), self._rows(y)
+        k = z.shape[1]
+        if k > len(self.srs_g1):
+            raise ValueError(f"KzgPointsVerifier: the key holds {len(self.srs_g1)} powers, the rows have {k} points")
+        return engine().kzg_verify_points(self.srs_g1.xy[:k], self.srs_g2.xy[:k + 1], c.xy, z, y, pi.xy, c.infinity, pi.infinity).astype(bool)
+
+
 def group_offsets(groups, m: int) -> np.ndarray:
     """`groups` in this module is the list of group SIZES (e.g. [12, 2]: twelve polynomials opened at the first point, two at the second; a
     size of 0 is legal); the C ABI and the Engine take the G + 1 OFFSETS, which this returns.  ValueError unless the sizes add up to m."""
@@ -703,6 +734,14 @@ class KzgProver:
         commitments and the y_j are fixed.  (commit(polys), y, groups, z, gamma, pi) is what KzgVerifier.verify_multi takes."""
         a = self._polys(polys)
         y, pi_xy, pi_inf = engine().kzg_open_multi(self.srs_g1.xy, a, group_offsets(groups, a.shape[0]), KzgVerifier._words(z), KzgVerifier._words(gamma))
+        return y, G1Affine(pi_xy, pi_inf)
+
+    def open_points(self, polys, z):
+        """(y [m, k, 4] words, pi: G1Affine of m points): every f_j opened at ITS k points z[j] under ONE proof -- y[j, i] = f_j(z[j, i]) and
+        pi_j the commitment to f_j div prod_i (X - z[j, i]) (sylow_hip_kzg_open_points_batch); z is [m, k, 4] words or m lists of k Python
+        ints, 1 <= k <= 64, the points of a row distinct mod r.  pi_j is the identity when the quotient is zero (len <= k).  The library draws
+        no challenge and takes the SRS as given.  (commit(polys), z, y, pi) is what KzgPointsVerifier.verify takes."""
+        y, pi_xy, pi_inf = engine().kzg_open_points(self.srs_g1.xy, self._polys(polys), KzgPointsVerifier._rows(z))
         return y, G1Affine(pi_xy, pi_inf)
 
     def open_all(self, polys):

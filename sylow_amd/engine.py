@@ -1197,6 +1197,82 @@ class Engine:
         self._call("sylow_hip_kzg_verify_multi_batch", dtau.ptr, dc.ptr, self._ptr(dci), dy.ptr, m, gs.ctypes.data, G, dz.ptr, dg.ptr, dp.ptr, self._ptr(dpi), dok.ptr)
         return dok.download()
 
+    # ---- KZG, one polynomial at several points under one proof (include/sylow_hip_kzg_points.h).  z, y [m, k, 4]: k points per row,
+    # 1 <= k <= 64, any 256-bit words taken mod r; the device layout is [4][m k] with (row j, point i) at j k + i.  The library draws no
+    # challenge and takes the SRS as given ----
+    @staticmethod
+    def _kzg_rows(z):
+        z = np.ascontiguousarray(z, dtype=np.uint64)
+        assert z.ndim == 3 and z.shape[2] == 4 and z.shape[1] >= 1, z.shape
+        return z
+
+    def _kzg_rows_up(self, z):
+        return self.to_device_soa(z.reshape(-1, 4), 4) if z.shape[0] else None
+
+    def _kzg_rows_down(self, d, m, k):
+        return self.from_device_soa(d)[:m * k].reshape(m, k, 4)
+
+    def kzg_points_weights(self, z):
+        """The barycentric weights a[j, i] = 1 / prod_{l != i} (z[j, i] - z[j, l]) as [m, k, 4] canonical words, inv(0) = 0, and distinct [m]:
+        1 iff the k points of row j are distinct mod r (sylow_hip_kzg_points_weights_batch)."""
+        z = self._kzg_rows(z)
+        m, k = z.shape[0], z.shape[1]
+        dz, da, dd = self._kzg_rows_up(z), self.empty((4, max(m * k, 1))), self.empty((max(m, 1),), np.uint8)
+        self._call("sylow_hip_kzg_points_weights_batch", self._ptr(dz), k, m, da.ptr, dd.ptr)
+        return self._kzg_rows_down(da, m, k), dd.download()[:m]
+
+    def kzg_quotient_points(self, polys, z, want_q=True, want_y=True):
+        """q_j = sum_i a[j, i] (f_j - f_j(z[j, i])) / (X - z[j, i]) as [m, len, 4] canonical words -- f_j div prod_i (X - z[j, i]) for
+        distinct points -- and y[j, i] = f_j(z[j, i]) as [m, k, 4] (sylow_hip_kzg_quotient_points_batch); an output that is not wanted is
+        None.  A row with points repeated mod r gives what the formula gives under inv(0) = 0: not a valid opening."""
+        a, z = self._kzg_polys(polys), self._kzg_rows(z)
+        m, ln, k = a.shape[0], a.shape[1], z.shape[1]
+        assert z.shape[0] == m and (want_q or want_y)
+        dc, dz = self._kzg_polys_up(a), self._kzg_rows_up(z)
+        dq = self.empty((max(m, 1), 4, ln)) if want_q else None
+        dy = self.empty((4, max(m * k, 1))) if want_y else None
+        self._call("sylow_hip_kzg_quotient_points_batch", self._ptr(dc), ln, m, self._ptr(dz), k, self._ptr(dq), self._ptr(dy))
+        q = np.ascontiguousarray(dq.download()[:m].transpose(0, 2, 1)) if want_q else None
+        return q, (self._kzg_rows_down(dy, m, k) if want_y else None)
+
+    def kzg_open_points(self, srs_g1, polys, z):
+        """The opening of every f_j at its k points under ONE proof (sylow_hip_kzg_open_points_batch): (y [m, k, 4], pi [m, 8] affine words,
+        pi flags [m]); pi_j is the identity exactly when the quotient is zero (len <= k, or f_j of degree below k)."""
+        a, srs, z = self._kzg_polys(polys), _aos(srs_g1, 8), self._kzg_rows(z)
+        m, ln, k = a.shape[0], a.shape[1], z.shape[1]
+        assert srs.shape[0] == ln and z.shape[0] == m
+        dc, ds, dz = self._kzg_polys_up(a), self.to_device_soa(srs, 8), self._kzg_rows_up(z)
+        dy, dp, dpi = self.empty((4, max(m * k, 1))), self.empty((8, max(m, 1))), self.empty((max(m, 1),), np.uint8)
+        self._call("sylow_hip_kzg_open_points_batch", ds.ptr, self._ptr(dc), ln, m, self._ptr(dz), k, dy.ptr, dp.ptr, dpi.ptr)
+        return self._kzg_rows_down(dy, m, k), self.from_device_soa(dp)[:m], dpi.download()[:m]
+
+    def kzg_points_polys(self, z, y):
+        """The verifier's Fr half (sylow_hip_kzg_points_polys_batch): (Z [n, k + 1, 4] with Z_j = prod_i (X - z[j, i]), monic,
+        R [n, k, 4] with R_j the interpolant of the y[j, i] at the z[j, i], distinct [n]); coefficients lowest degree first."""
+        z, y = self._kzg_rows(z), self._kzg_rows(y)
+        n, k = z.shape[0], z.shape[1]
+        assert y.shape == z.shape
+        dz, dy = self._kzg_rows_up(z), self._kzg_rows_up(y)
+        dzp, drp, dd = self.empty((max(n, 1), 4, k + 1)), self.empty((max(n, 1), 4, k)), self.empty((max(n, 1),), np.uint8)
+        self._call("sylow_hip_kzg_points_polys_batch", self._ptr(dz), self._ptr(dy), k, n, dzp.ptr, drp.ptr, dd.ptr)
+        return (np.ascontiguousarray(dzp.download()[:n].transpose(0, 2, 1)), np.ascontiguousarray(drp.download()[:n].transpose(0, 2, 1)),
+                dd.download()[:n])
+
+    def kzg_verify_points(self, srs_g1, srs_g2, c_xy, z, y, pi_xy, c_inf=None, pi_inf=None):
+        """ok [n]: e(C_j - R_j(tau) G1gen, G2gen) e(-pi_j, Z_j(tau) G2gen) == 1 and the points of row j distinct mod r
+        (sylow_hip_kzg_verify_points_batch).  srs_g1 [k, 8] = tau^i G1gen, i < k; srs_g2 [k + 1, 16] = tau^i G2gen, i <= k: the verifier's
+        key, taken as given."""
+        srs_g1, srs_g2, c_xy, pi_xy = _aos(srs_g1, 8), _aos(srs_g2, 16), _aos(c_xy, 8), _aos(pi_xy, 8)
+        z, y = self._kzg_rows(z), self._kzg_rows(y)
+        n, k = z.shape[0], z.shape[1]
+        assert y.shape == z.shape and c_xy.shape[0] == n and pi_xy.shape[0] == n and srs_g1.shape[0] == k and srs_g2.shape[0] == k + 1
+        if not n:
+            return np.zeros(0, dtype=np.uint8)
+        d1, d2, dc, dp = self.to_device_soa(srs_g1, 8), self.to_device_soa(srs_g2, 16), self.to_device_soa(c_xy, 8), self.to_device_soa(pi_xy, 8)
+        dci, dpi, dz, dy, dok = self._flags(c_inf, n), self._flags(pi_inf, n), self._kzg_rows_up(z), self._kzg_rows_up(y), self.empty((n,), np.uint8)
+        self._call("sylow_hip_kzg_verify_points_batch", d1.ptr, d2.ptr, dc.ptr, self._ptr(dci), dz.ptr, dy.ptr, k, n, dp.ptr, self._ptr(dpi), dok.ptr)
+        return dok.download()
+
     # ---- Fr transforms on radix-2 domains.  values [m, n, 4] (or [n, 4]: one array), n = 2^log_n <= 2^28, any 256-bit words taken mod r ----
     def fr_ntt(self, values, inverse=False, shift=None, stages=-1):
         """forward: out_i = sum_k a_k (g w_n^i)^k; inverse: out_k = n^-1 g^-k sum_i a_i w_n^(-ik), natural order both ways, per array
