@@ -688,6 +688,62 @@ class KzgPointsVerifier:
         return engine().kzg_verify_points(self.srs_g1.xy[:k], self.srs_g2.xy[:k + 1], c.xy, z, y, pi.xy, c.infinity, pi.infinity).astype(bool)
 
 
+class KzgCosetVerifier:
+    """The verifier's key for openings of one polynomial on a coset of l = 2^log_l points of its domain of n = 2^(log_c + log_l) under one
+    proof (KzgProver.open_cosets): srs_g1_prefix = (tau^k G1gen) for k < l (a longer array is cut) and tau_l_g2 = tau^l G2gen, one point of
+    G2 proper.  A row is (C, idx, cell, pi): the cell holds the l values of the polynomial committed in C on coset idx < c, in the order
+    w_n^(idx + c t).  Each row reduces to a single-point opening (C - R(tau) G1gen, v^idx, 0, pi) under tau_l_g2, R the interpolant of the
+    cell, so ONE G2 point and one line table serve the whole batch.  The key is trusted input; the library makes no G2 powers."""
+
+    def __init__(self, srs_g1_prefix: G1Affine, tau_l_g2: G2Affine, log_c: int, log_l: int):
+        log_c, log_l = int(log_c), int(log_l)
+        if log_c < 0 or log_l < 0 or log_c + log_l > 27:
+            raise ValueError("KzgCosetVerifier: log_c >= 0, log_l >= 0, log_c + log_l <= 27")
+        if len(srs_g1_prefix) < 1 << log_l or srs_g1_prefix.infinity[:1 << log_l].any():
+            raise ValueError("KzgCosetVerifier: 2^log_l powers in G1, no identity among them")
+        self.srs_g1 = G1Affine(srs_g1_prefix.xy[:1 << log_l], srs_g1_prefix.infinity[:1 << log_l])
+        self._single = KzgVerifier(tau_l_g2)          # the single-point verifier under tau^l G2gen, with its cached line table
+        self.log_c, self.log_l = log_c, log_l
+
+    def _cells(self, idx, cells):
+        idx = np.ascontiguousarray([int(i) for i in np.asarray(idx, dtype=object).reshape(-1)], dtype=np.uint64)
+        a = np.asarray(cells)
+        if a.dtype == object or a.ndim == 2:
+            rows = [list(r) for r in cells]
+            a = fp([int(x) for r in rows for x in r]).reshape(len(rows), -1, 4) if rows else np.zeros((0, 1 << self.log_l, 4), dtype=np.uint64)
+        if a.ndim != 3 or a.shape != (idx.shape[0], 1 << self.log_l, 4):
+            raise ValueError("cells: [rows, 2^log_l, 4] words or rows of 2^log_l integers, one row per index")
+        return idx, a
+
+    def reduce(self, c: G1Affine, idx, cells):
+        """(C - R(tau) G1gen: G1Affine, z [rows, 4] = v^idx, in_range [rows] bool): the rows KzgVerifier(tau_l_g2) takes with y = 0
+        (sylow_hip_kzg_cosets_reduce_batch); words as for idx mod c where idx >= c, and in_range False there."""
+        idx, a = self._cells(idx, cells)
+        xy, inf, z, ok = engine().kzg_cosets_reduce(self.srs_g1.xy, c.xy, idx, a, self.log_c, self.log_l, c.infinity)
+        return G1Affine(xy, inf), z, ok.astype(bool)
+
+    def verify(self, c: G1Affine, idx, cells, pi: G1Affine) -> np.ndarray:
+        """ok[j] = [ e(C_j - R_j(tau) G1gen, G2gen) e(-pi_j, tau^l G2gen - v^idx_j G2gen) == 1 ] and idx_j < c
+        (sylow_hip_kzg_verify_cosets_batch).  A flagged pi (a zero quotient) is legal: the row is then valid iff C_j = R_j(tau) G1gen."""
+        idx, a = self._cells(idx, cells)
+        return engine().kzg_verify_cosets(self.srs_g1.xy, self._single.tau_g2.xy, c.xy, idx, a, pi.xy, self.log_c, self.log_l, c.infinity, pi.infinity).astype(bool)
+
+    def verify_line_table(self, c: G1Affine, idx, cells, pi: G1Affine) -> np.ndarray:
+        """The same flags over the cached line table of tau^l G2gen: reduce, then sylow_hip_kzg_verify_line_table_batch."""
+        cred, z, ok = self.reduce(c, idx, cells)
+        return self._single.verify((cred, z, np.zeros_like(z), pi)) & ok
+
+    def verify_weighted(self, c: G1Affine, idx, cells, pi: G1Affine, weights) -> bool:
+        """"are ALL the rows valid?" as ONE boolean: reduce, then the small-exponent test of KzgVerifier.verify_weighted on the reduced
+        rows; one weight per row, drawn AFTER the rows are fixed.  False when a row with a non-zero weight (mod r) names no coset."""
+        cred, z, ok = self.reduce(c, idx, cells)
+        w = KzgVerifier._words(weights)
+        live = np.array([x % R_ORDER != 0 for x in _ints(w)], dtype=bool)
+        if (live & ~ok).any():
+            return False
+        return self._single.verify_weighted((cred, z, np.zeros_like(z), pi), w)
+
+
 def group_offsets(groups, m: int) -> np.ndarray:
     """`groups` in this module is the list of group SIZES (e.g. [12, 2]: twelve polynomials opened at the first point, two at the second; a
     size of 0 is legal); the C ABI and the Engine take the G + 1 OFFSETS, which this returns.  ValueError unless the sizes add up to m."""
@@ -707,6 +763,7 @@ class KzgProver:
             raise ValueError("KzgProver: srs_g1 holds at least G1gen and no identity")
         self.srs_g1 = srs_g1
         self._open_all_table = None      # open_all: built on first use
+        self._open_cosets_tables = {}    # open_cosets: one table per log_l, built on first use
 
     def _polys(self, polys):
         a = np.asarray(polys)
@@ -757,6 +814,23 @@ class KzgProver:
             self._open_all_table = engine().kzg_open_all_prepare(self.srs_g1.xy)
         y, pi_xy, pi_inf = engine().kzg_open_all(self._open_all_table, a)
         return y, [G1Affine(pi_xy[j], pi_inf[j]) for j in range(a.shape[0])]
+
+    def open_cosets(self, polys, log_l: int):
+        """Every f_j opened on ALL c cosets of its domain of n = len(srs_g1) = c l points, l = 2^log_l, ONE proof per coset, in n log n
+        (sylow_hip_kzg_open_cosets_batch, the multi-proof form of Feist-Khovratovich): (cells [m, c, l, 4] words, [G1Affine of c points] * m).
+        Coset i is { w_n^(i + c t) : t < l }, cells[j, i, t] = f_j(w_n^(i + c t)) (= ntt(polys)[j, i + c t]) and pi_j[i] the commitment to
+        f_j div (X^l - w_n^(l i)).  The table that depends on the SRS and log_l alone is built on first use and kept on the device.
+        (commit(polys)[j], i, cells[j, i], pi_j[i]) is a row KzgCosetVerifier takes.  ValueError unless n = 2^log_n <= 2^27 and l divides n."""
+        n, log_l = len(self.srs_g1), int(log_l)
+        if n & (n - 1) or n > 1 << 27 or log_l < 0 or (1 << log_l) > n:
+            raise ValueError("KzgProver.open_cosets: the SRS holds a power of two of points, at most 2^27, and 2^log_l of them make a coset")
+        a = self._polys(polys)
+        if log_l not in self._open_cosets_tables:
+            self._open_cosets_tables[log_l] = engine().kzg_open_cosets_prepare(self.srs_g1.xy, log_l)
+        y, pi_xy, pi_inf = engine().kzg_open_cosets(self._open_cosets_tables[log_l], a, log_l)
+        l, m = 1 << log_l, a.shape[0]
+        cells = np.ascontiguousarray(y.reshape(m, l, n >> log_l, 4).transpose(0, 2, 1, 3))
+        return cells, [G1Affine(pi_xy[j], pi_inf[j]) for j in range(m)]
 
     def commit_evals(self, evals) -> G1Affine:
         """The same commitments from the VALUES of the polynomials on the domain of len(srs_g1) = 2^log_n points, evals[j][i] = f_j(w_n^i)

@@ -136,6 +136,10 @@ int32_t stage(const uint64_t* src, uint64_t* dst, int log_n, size_t m, size_t st
               long long max_blocks, void* stream);
 int32_t close(const uint64_t* src, int log_n, size_t m, size_t stride, uint64_t* out_xy, uint8_t* out_inf, long long max_blocks, void* stream);
 }  // namespace g1ntth
+namespace kzoah {       // kzg_open_all.hip: stage 0 of the forward transform of 2^log_n points (log_n >= 1) that reads h_b of array a at column a 2^(log_n+1) + b
+// of src, takes h_(n-1) as the identity, and writes array a at columns a 2^log_n of dst; both buffers [12][stride] (kzg_open_all_plan.hpp: fwd_*)
+int32_t fwd_first(const uint64_t* src, uint64_t* dst, int log_n, size_t m, size_t stride, long long max_blocks, void* stream);
+}  // namespace kzoah
 namespace kzgh {        // kzg.hip: F_i = C_i - y_i G1gen + z_i pi_i (affine SoA + flags, stride n) and, when neg_xy is given, -pi_i beside it: one launch
 int32_t fold(const uint64_t* c_xy, const uint8_t* c_inf, const uint64_t* z, const uint64_t* y, const uint64_t* pi_xy, const uint8_t* pi_inf,
              uint64_t* out_xy, uint8_t* out_inf, uint64_t* neg_xy, uint8_t* neg_inf, size_t n, void* stream);

@@ -132,15 +132,22 @@ static int32_t open_all(const uint64_t* txy, const uint8_t* tinf, const uint64_t
     k_open_all_first<<<dim3((unsigned)first_grid(log_n, m, max_blocks)), dim3(BLOCK), 0, st>>>(txy, tinf, f, buf[inv_dst(0)], log_n, first_items(log_n, m), str, tables);
   for (int s = 1; s < inv_stages(log_n) && rc == SYLOW_HIP_OK; ++s)
     rc = g1ntth::stage(buf[inv_src(s)], buf[inv_dst(s)], L, m, str, s, /*inverse=*/true, tw_wide, tables, max_blocks, stream);
-  if (rc == SYLOW_HIP_OK)
-    k_open_all_fwd_first<<<dim3((unsigned)fwd_grid(log_n, m, max_blocks)), dim3(BLOCK), 0, st>>>(buf[fwd_src(log_n, 0)], buf[fwd_dst(log_n, 0)], log_n,
-                                                                                                 fwd_items(log_n, m), str);
+  if (rc == SYLOW_HIP_OK) rc = kzoah::fwd_first(buf[fwd_src(log_n, 0)], buf[fwd_dst(log_n, 0)], log_n, m, str, max_blocks, stream);
   for (int s = 1; s < fwd_stages(log_n) && rc == SYLOW_HIP_OK; ++s)
     rc = g1ntth::stage(buf[fwd_src(log_n, s)], buf[fwd_dst(log_n, s)], log_n, m, str, s, /*inverse=*/false, tw, tables, max_blocks, stream);
   if (rc == SYLOW_HIP_OK) rc = g1ntth::close(buf[close_src(log_n)], log_n, m, str, pi_xy, pi_inf, max_blocks, stream);
   return host::finish(rc, ws);
 }
 }  // namespace kzoa
+
+namespace kzoah {
+// For kzg_cosets.hip, whose forward transform of c points reads h the same way: the launch of open_all() above with the caller's geometry
+int32_t fwd_first(const uint64_t* src, uint64_t* dst, int log_n, size_t m, size_t stride, long long max_blocks, void* stream) {
+  using namespace kzg_open_all_plan;
+  kzoa::k_open_all_fwd_first<<<dim3((unsigned)fwd_grid(log_n, m, max_blocks)), dim3(BLOCK), 0, (hipStream_t)stream>>>(src, dst, log_n, fwd_items(log_n, m), stride);
+  LAUNCHED();
+}
+}  // namespace kzoah
 
 extern "C" {
 int32_t sylow_hip_kzg_open_all_prepare(const uint64_t* srs_g1_xy, int32_t log_n, uint64_t* table_xy, uint8_t* table_inf, void* stream) {

@@ -1364,6 +1364,89 @@ class Engine:
         y = np.ascontiguousarray(dy.download()[:m].transpose(0, 2, 1)) if want_y else None
         return y, np.ascontiguousarray(dp.download()[:m].transpose(0, 2, 1)), dpi.download()[:m]
 
+    # ---- KZG proofs on every coset of the domain (include/sylow_hip_kzg_cosets.h): n = c l, c = 2^log_c cosets of l = 2^log_l points.  The
+    # table is kept ON THE DEVICE: (DeviceArray [l, 8, 2c] words, DeviceArray [l, 2c] flags) ----
+    def kzg_open_cosets_prepare(self, srs_g1, log_l):
+        """The table of kzg_open_cosets from the monomial SRS, srs_g1 [n, 8] = tau^k G1gen, n = 2^(log_c + log_l) <= 2^27
+        (sylow_hip_kzg_open_cosets_prepare): array a < l is the forward G1 transform of 2c points, x_(2c-1-u) = s_(a + l u) for u <= c - 2 and
+        the identity elsewhere.  Built once per (SRS, log_l); a set flag is an entry that is the identity, not an error."""
+        srs = _aos(srs_g1, 8)
+        n = srs.shape[0]
+        log_c = n.bit_length() - 1 - log_l
+        assert n >= 1 and log_l >= 0 and log_c >= 0 and n == 1 << (log_c + log_l), (n, log_l)
+        l, cc = 1 << log_l, 2 << log_c
+        ds, dt, dti = self.to_device_soa(srs, 8), self.empty((l, 8, cc)), self.empty((l, cc), np.uint8)
+        self._call("sylow_hip_kzg_open_cosets_prepare", ds.ptr, log_c, log_l, dt.ptr, dti.ptr)
+        self.sync()                      # ds is released when this frame returns
+        return dt, dti
+
+    def kzg_open_cosets(self, table, polys, log_l, want_y=True, max_blocks=-1, planes_log=-1):
+        """The proofs of every f_j on ALL c cosets of its domain and its values there (sylow_hip_kzg_open_cosets_batch): (y [m, n, 4] or None,
+        pi [m, c, 8] affine words, pi flags [m, c]); value j of cell i is y[i + c j].  table: what kzg_open_cosets_prepare returned, or host
+        arrays ([l, 2c, 8] words, [l, 2c] flags or None).  polys [m, n, 4].  max_blocks >= 1 caps the blocks of a multiplying launch and
+        planes_log in 0 .. log_l pins the planes of the product-sums (sylow_hip_kzg_open_cosets_batch_tuned); the values do not depend on
+        either."""
+        a = self._kzg_polys(polys)
+        m, n = a.shape[0], a.shape[1]
+        log_c = n.bit_length() - 1 - log_l
+        assert log_l >= 0 and log_c >= 0 and n == 1 << (log_c + log_l), (n, log_l)
+        l, c = 1 << log_l, 1 << log_c
+        txy, tinf = table
+        dt = txy if isinstance(txy, DeviceArray) else self.to_device(np.ascontiguousarray(np.asarray(txy, dtype=np.uint64).reshape(l, 2 * c, 8).transpose(0, 2, 1)))
+        dti = tinf if tinf is None or isinstance(tinf, DeviceArray) else self.to_device(np.ascontiguousarray(tinf, dtype=np.uint8).reshape(l, 2 * c))
+        assert dt.shape == (l, 8, 2 * c) and (dti is None or dti.shape == (l, 2 * c)), (dt.shape, l, c)
+        dc = self._kzg_polys_up(a)
+        dy = self.empty((max(m, 1), 4, n)) if want_y else None
+        dp, dpi = self.empty((max(m, 1), 8, c)), self.empty((max(m, 1), c), np.uint8)
+        if max_blocks < 0 and planes_log < 0:
+            self._call("sylow_hip_kzg_open_cosets_batch", dt.ptr, self._ptr(dti), self._ptr(dc), log_c, log_l, m, self._ptr(dy), dp.ptr, dpi.ptr)
+        else:
+            self._call("sylow_hip_kzg_open_cosets_batch_tuned", dt.ptr, self._ptr(dti), self._ptr(dc), log_c, log_l, m, int(max_blocks), int(planes_log),
+                       self._ptr(dy), dp.ptr, dpi.ptr)
+        y = np.ascontiguousarray(dy.download()[:m].transpose(0, 2, 1)) if want_y else None
+        return y, np.ascontiguousarray(dp.download()[:m].transpose(0, 2, 1)), dpi.download()[:m]
+
+    def _kzg_cells_up(self, idx, cells, log_l):
+        cells = np.ascontiguousarray(cells, dtype=np.uint64)
+        idx = np.ascontiguousarray(idx, dtype=np.uint64).reshape(-1)
+        rows = idx.shape[0]
+        assert cells.shape == (rows, 1 << log_l, 4), (cells.shape, rows, log_l)
+        return rows, (self.to_device(idx) if rows else None), self._kzg_polys_up(cells)
+
+    def kzg_coset_interp(self, idx, cells, log_c, log_l):
+        """R_j = the polynomial of degree below l with the values cells [rows, l, 4] on coset idx_j mod c (sylow_hip_kzg_coset_interp_batch):
+        (R [rows, l, 4] canonical words, lowest degree first, in_range [rows] = idx_j < c)."""
+        rows, di, dv = self._kzg_cells_up(idx, cells, log_l)
+        dr, dg = self.empty((max(rows, 1), 4, 1 << log_l)), self.empty((max(rows, 1),), np.uint8)
+        self._call("sylow_hip_kzg_coset_interp_batch", self._ptr(dv), self._ptr(di), log_c, log_l, rows, dr.ptr, dg.ptr)
+        return np.ascontiguousarray(dr.download()[:rows].transpose(0, 2, 1)), dg.download()[:rows]
+
+    def kzg_cosets_reduce(self, srs_g1, c_xy, idx, cells, log_c, log_l, c_inf=None):
+        """The rows the single-point verifiers take with y = 0 under tau^l G2gen (sylow_hip_kzg_cosets_reduce_batch): (C_j - R_j(tau) G1gen
+        as [rows, 8] affine words, its flags [rows], z_j = v^idx_j as [rows, 4], in_range [rows]).  srs_g1 [l, 8] = tau^k G1gen, k < l."""
+        srs, c_xy = _aos(srs_g1, 8), _aos(c_xy, 8)
+        rows, di, dv = self._kzg_cells_up(idx, cells, log_l)
+        assert srs.shape[0] == 1 << log_l and c_xy.shape[0] == rows
+        if not rows:
+            return np.zeros((0, 8), np.uint64), np.zeros(0, np.uint8), np.zeros((0, 4), np.uint64), np.zeros(0, np.uint8)
+        ds, dc, dci = self.to_device_soa(srs, 8), self.to_device_soa(c_xy, 8), self._flags(c_inf, rows)
+        do, doi, dz, dg = self.empty((8, rows)), self.empty((rows,), np.uint8), self.empty((4, rows)), self.empty((rows,), np.uint8)
+        self._call("sylow_hip_kzg_cosets_reduce_batch", ds.ptr, dc.ptr, self._ptr(dci), di.ptr, dv.ptr, log_c, log_l, rows, do.ptr, doi.ptr, dz.ptr, dg.ptr)
+        return self.from_device_soa(do), doi.download(), self.from_device_soa(dz), dg.download()
+
+    def kzg_verify_cosets(self, srs_g1, tau_l_g2, c_xy, idx, cells, pi_xy, log_c, log_l, c_inf=None, pi_inf=None):
+        """ok [rows]: e(C_j - R_j(tau) G1gen, G2gen) e(-pi_j, tau^l G2gen - v^idx_j G2gen) == 1 and idx_j < c
+        (sylow_hip_kzg_verify_cosets_batch).  srs_g1 [l, 8] = tau^k G1gen, k < l; tau_l_g2 [1, 16] = tau^l G2gen, taken as given."""
+        srs, tau, c_xy, pi_xy = _aos(srs_g1, 8), _aos(tau_l_g2, 16), _aos(c_xy, 8), _aos(pi_xy, 8)
+        rows, di, dv = self._kzg_cells_up(idx, cells, log_l)
+        assert srs.shape[0] == 1 << log_l and tau.shape[0] == 1 and c_xy.shape[0] == rows and pi_xy.shape[0] == rows
+        if not rows:
+            return np.zeros(0, dtype=np.uint8)
+        ds, dtau, dc, dp = self.to_device_soa(srs, 8), self.to_device_soa(tau, 16), self.to_device_soa(c_xy, 8), self.to_device_soa(pi_xy, 8)
+        dci, dpi, dok = self._flags(c_inf, rows), self._flags(pi_inf, rows), self.empty((rows,), np.uint8)
+        self._call("sylow_hip_kzg_verify_cosets_batch", ds.ptr, dtau.ptr, dc.ptr, self._ptr(dci), di.ptr, dv.ptr, log_c, log_l, rows, dp.ptr, self._ptr(dpi), dok.ptr)
+        return dok.download()
+
     # ---- Groth16, the prover's side.  A sparse matrix is CSR: (row_ptr [rows + 1], col [nnz], val [nnz, 4]); Fr batches are [m, n, 4] on the
     # host and [m][4][n] on the device; any 256-bit words, taken mod r ----
     def _csr_up(self, csr):
