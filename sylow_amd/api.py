@@ -744,6 +744,44 @@ class KzgCosetVerifier:
         return self._single.verify_weighted((cred, z, np.zeros_like(z), pi), w)
 
 
+class KzgCellRecovery:
+    """A blob -- a polynomial of degree below n / 2 on a domain of n = 2^(log_c + log_l) points cut into c = 2^log_c cells of l = 2^log_l
+    values, the cells of KzgProver.open_cosets -- from ANY c / 2 of its cells (sylow_hip_kzg_recover_batch).  It needs no SRS.  The
+    extension is fixed at 2x, and the cost of the vanishing values is quadratic in c: log_c <= 12."""
+
+    def __init__(self, log_c: int, log_l: int):
+        log_c, log_l = int(log_c), int(log_l)
+        if log_c < 0 or log_l < 0 or log_c > 12 or not 1 <= log_c + log_l <= 27:
+            raise ValueError("KzgCellRecovery: 0 <= log_c <= 12, log_l >= 0, 1 <= log_c + log_l <= 27")
+        self.log_c, self.log_l = log_c, log_l
+
+    def _rows(self, idx, cells):
+        """-> (y [m, n, 4], present [m, c]) from the indices of ONE blob or a list of index lists, and the matching rows of l values"""
+        c, l = 1 << self.log_c, 1 << self.log_l
+        idx = list(idx)
+        if not idx or not isinstance(idx[0], (list, tuple, np.ndarray)):
+            idx, cells = [idx], [cells]
+        if len(cells) != len(idx):
+            raise ValueError("KzgCellRecovery: one set of cells per set of indices")
+        y, present = np.zeros((len(idx), l, c, 4), dtype=np.uint64), np.zeros((len(idx), c), dtype=np.uint8)
+        form = KzgCosetVerifier._cells
+        for j, (ix, rows) in enumerate(zip(idx, cells)):
+            ix, a = form(self, ix, rows)
+            if (ix >= c).any() or len(set(ix.tolist())) != len(ix):
+                raise ValueError("KzgCellRecovery: cell indices below c = 2^log_c, each at most once per blob")
+            present[j, ix.astype(np.int64)] = 1
+            y[j, :, ix.astype(np.int64)] = a                                   # value t of cell i at y[i + c t]
+        return y.reshape(len(idx), l * c, 4), present
+
+    def recover(self, idx, cells):
+        """(polys [m, n, 4] words, status [m]): idx is the list of the cell indices held of ONE blob, or a list of such lists for m blobs;
+        `cells` the matching rows of l values ([rows, l, 4] words or rows of l integers).  status 0: polys[j] is the blob (upper half
+        zero); 1: fewer than c / 2 cells (zero row); 2: the cells are not the values of a polynomial of degree below n / 2."""
+        y, present = self._rows(idx, cells)
+        coeffs, _, status = engine().kzg_recover(y, present, self.log_c, self.log_l, want_y=False)
+        return coeffs, status
+
+
 def group_offsets(groups, m: int) -> np.ndarray:
     """`groups` in this module is the list of group SIZES (e.g. [12, 2]: twelve polynomials opened at the first point, two at the second; a
     size of 0 is legal); the C ABI and the Engine take the G + 1 OFFSETS, which this returns.  ValueError unless the sizes add up to m."""
@@ -831,6 +869,23 @@ class KzgProver:
         l, m = 1 << log_l, a.shape[0]
         cells = np.ascontiguousarray(y.reshape(m, l, n >> log_l, 4).transpose(0, 2, 1, 3))
         return cells, [G1Affine(pi_xy[j], pi_inf[j]) for j in range(m)]
+
+    def recover_cells_and_proofs(self, idx, cells, log_l: int):
+        """Every cell and every cell proof of blobs of which at least half the cells are held: KzgCellRecovery.recover, then open_cosets on
+        the rows it recovered.  idx, cells as KzgCellRecovery.recover takes them.  (status [m], cells [m, c, l, 4] words, proofs: a list of
+        m G1Affine of c points); a row whose status is not 0 has zero cells and None for its proofs."""
+        n, log_l = len(self.srs_g1), int(log_l)
+        if n & (n - 1) or n > 1 << 27 or log_l < 0 or (1 << log_l) > n:
+            raise ValueError("KzgProver.recover_cells_and_proofs: the SRS holds a power of two of points, at most 2^27, and 2^log_l of them make a cell")
+        polys, status = KzgCellRecovery(n.bit_length() - 1 - log_l, log_l).recover(idx, cells)
+        good = np.flatnonzero(status == 0)
+        out = np.zeros((polys.shape[0], n >> log_l, 1 << log_l, 4), dtype=np.uint64)
+        proofs = [None] * polys.shape[0]
+        if good.size:
+            out[good], pis = self.open_cosets(polys[good], log_l)
+            for j, pi in zip(good, pis):
+                proofs[j] = pi
+        return status, out, proofs
 
     def commit_evals(self, evals) -> G1Affine:
         """The same commitments from the VALUES of the polynomials on the domain of len(srs_g1) = 2^log_n points, evals[j][i] = f_j(w_n^i)

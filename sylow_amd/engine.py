@@ -1447,6 +1447,43 @@ class Engine:
         self._call("sylow_hip_kzg_verify_cosets_batch", ds.ptr, dtau.ptr, dc.ptr, self._ptr(dci), di.ptr, dv.ptr, log_c, log_l, rows, dp.ptr, self._ptr(dpi), dok.ptr)
         return dok.download()
 
+    # ---- a KZG polynomial of degree below n / 2 from any half of its cells (include/sylow_hip_kzg_recover.h): present [m, c] bytes,
+    # non-zero = the cell is held; y [m, n, 4] in the layout of kzg_open_cosets' y (value j of cell i at y[i + c j]) ----
+    def _kzg_present_up(self, present, log_c):
+        p = np.ascontiguousarray(present, dtype=np.uint8)
+        p = p[None] if p.ndim == 1 else p
+        assert p.ndim == 2 and p.shape[1] == 1 << log_c, (p.shape, log_c)
+        return p.shape[0], (self.to_device(p) if p.shape[0] else None)
+
+    def kzg_recover_vanish(self, present, log_c, log_l):
+        """The values of Z = prod_(i missing) (X^l - v^i) on the domain and on the coset 5 <w_n>, c of each per row
+        (sylow_hip_kzg_recover_vanish_batch): (zd [m, c, 4], zc [m, c, 4], status [m]); status 1 = more than c / 2 cells missing (zd = 0,
+        zc = 1)."""
+        m, dp = self._kzg_present_up(present, log_c)
+        c = 1 << log_c
+        dzd, dzc, dst = self.empty((max(m, 1), 4, c)), self.empty((max(m, 1), 4, c)), self.empty((max(m, 1),), np.uint8)
+        self._call("sylow_hip_kzg_recover_vanish_batch", self._ptr(dp), log_c, log_l, m, dzd.ptr, dzc.ptr, dst.ptr)
+        if not m:
+            return np.zeros((0, c, 4), np.uint64), np.zeros((0, c, 4), np.uint64), np.zeros(0, np.uint8)
+        return np.ascontiguousarray(dzd.download().transpose(0, 2, 1)), np.ascontiguousarray(dzc.download().transpose(0, 2, 1)), dst.download()
+
+    def kzg_recover(self, y, present, log_c, log_l, want_y=True):
+        """The polynomials of degree below n / 2 whose values on the held cells are those of y (sylow_hip_kzg_recover_batch): (coeffs
+        [m, n, 4], y [m, n, 4] with every cell restored or None, status [m]).  Words of y in cells that are not held are never part of the
+        result.  status 0 = recovered, 1 = more than c / 2 cells missing (zero rows), 2 = the held cells are not the values of such a
+        polynomial (coeffs is then what the five steps yield, its upper half not zero)."""
+        a = self._kzg_polys(y)
+        m, n = a.shape[0], a.shape[1]
+        assert n == 1 << (log_c + log_l), (n, log_c, log_l)
+        mp, dp = self._kzg_present_up(present, log_c)
+        assert mp == m, (mp, m)
+        dy = self._kzg_polys_up(a)
+        dc, dst = self.empty((max(m, 1), 4, n)), self.empty((max(m, 1),), np.uint8)
+        dyo = self.empty((max(m, 1), 4, n)) if want_y else None
+        self._call("sylow_hip_kzg_recover_batch", self._ptr(dy), self._ptr(dp), log_c, log_l, m, dc.ptr, self._ptr(dyo), dst.ptr)
+        coeffs = np.ascontiguousarray(dc.download()[:m].transpose(0, 2, 1))
+        return coeffs, (np.ascontiguousarray(dyo.download()[:m].transpose(0, 2, 1)) if want_y else None), dst.download()[:m]
+
     # ---- Groth16, the prover's side.  A sparse matrix is CSR: (row_ptr [rows + 1], col [nnz], val [nnz, 4]); Fr batches are [m, n, 4] on the
     # host and [m][4][n] on the device; any 256-bit words, taken mod r ----
     def _csr_up(self, csr):
