@@ -13,6 +13,7 @@ HEADER = os.path.join(os.path.dirname(_HERE), "include", "sylow_hip.h")
 HEADER_KZG_POINTS = os.path.join(os.path.dirname(_HERE), "include", "sylow_hip_kzg_points.h")      # the extension header: same grammar
 HEADER_KZG_COSETS = os.path.join(os.path.dirname(_HERE), "include", "sylow_hip_kzg_cosets.h")
 HEADER_KZG_RECOVER = os.path.join(os.path.dirname(_HERE), "include", "sylow_hip_kzg_recover.h")
+HEADER_KZG_CELLS = os.path.join(os.path.dirname(_HERE), "include", "sylow_hip_kzg_cells.h")
 ITEMSIZE = {"u64": 8, "i64": 8, "u8": 1, "i32": 4, "void": 1}
 _EXPR_OK = re.compile(r"^[\w\s+*()]+$")
 
@@ -61,7 +62,8 @@ def table():
     global _TABLE
     if _TABLE is None:
         try:
-            _TABLE = {**parse(), **parse(HEADER_KZG_POINTS), **parse(HEADER_KZG_COSETS), **parse(HEADER_KZG_RECOVER)}
+            _TABLE = {**parse(), **parse(HEADER_KZG_POINTS), **parse(HEADER_KZG_COSETS), **parse(HEADER_KZG_RECOVER),
+                      **parse(HEADER_KZG_CELLS)}
         except OSError:            # the package deployed without the repo's include/ directory: no table, nothing to check
             _TABLE = {}
     return _TABLE

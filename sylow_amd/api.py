@@ -744,6 +744,51 @@ class KzgCosetVerifier:
         return self._single.verify_weighted((cred, z, np.zeros_like(z), pi), w)
 
 
+class KzgCellBatchVerifier:
+    """The sampling node's question -- "are these N cells of B blobs, B << N, all valid?" -- answered ONCE over shared commitments
+    (include/sylow_hip_kzg_cells.h).  The key is KzgCosetVerifier's: srs_g1_prefix = (tau^k G1gen) for k < l and tau_l_g2 = tau^l G2gen.
+    Row k is (com_idx[k] < len(commitments), idx[k] < c, cells[k], pi[k], weights[k]); the weighted sums are taken in Fr before anything
+    touches the curve: one commitment of l terms for the whole batch where KzgCosetVerifier.verify_weighted commits l terms per row.
+    Weights are drawn by the caller AFTER the rows are fixed; the library draws none.  A weight of 0 removes a row, so a bad cell is
+    localised by masking weights.  A row that names no cell or no commitment adds nothing and fails the check unless its weight is 0."""
+
+    def __init__(self, srs_g1_prefix: G1Affine, tau_l_g2: G2Affine, log_c: int, log_l: int):
+        self._coset = KzgCosetVerifier(srs_g1_prefix, tau_l_g2, log_c, log_l)      # the same key, checked the same way
+        self.srs_g1, self._single, self.log_c, self.log_l = self._coset.srs_g1, self._coset._single, self._coset.log_c, self._coset.log_l
+
+    def _rows(self, com_idx, idx, cells, weights):
+        idx, a = self._coset._cells(idx, cells)
+        com_idx = np.ascontiguousarray([int(i) for i in np.asarray(com_idx, dtype=object).reshape(-1)], dtype=np.uint64)
+        w = KzgVerifier._words(weights) if len(idx) else np.zeros((0, 4), dtype=np.uint64)
+        if com_idx.shape[0] != idx.shape[0] or w.shape != (idx.shape[0], 4):
+            raise ValueError("KzgCellBatchVerifier: one commitment index and one weight per row")
+        return com_idx, idx, a, w
+
+    def fold(self, n_com: int, com_idx, idx, cells, weights):
+        """(W [n_com, 4], A [l, 4], r [rows, 4], rz [rows, 4], in_range: bool): the Fr half (sylow_hip_kzg_cells_fold_batch)."""
+        com_idx, idx, a, w = self._rows(com_idx, idx, cells, weights)
+        return engine().kzg_cells_fold(idx, com_idx, a, w, self.log_c, self.log_l, n_com)
+
+    def reduce(self, commitments: G1Affine, com_idx, idx, cells, pi: G1Affine, weights):
+        """(F: G1Affine, P: G1Affine, in_range: bool): the batch as the one row (F, 0, 0, P) of KzgVerifier(tau_l_g2)
+        (sylow_hip_kzg_cells_reduce_batch)."""
+        com_idx, idx, a, w = self._rows(com_idx, idx, cells, weights)
+        f, fi, p, pi_f, ok = engine().kzg_cells_reduce(self.srs_g1.xy, commitments.xy, idx, com_idx, a, pi.xy, w, self.log_c, self.log_l, commitments.infinity, pi.infinity)
+        return G1Affine(f, fi), G1Affine(p, pi_f), ok
+
+    def verify(self, commitments: G1Affine, com_idx, idx, cells, pi: G1Affine, weights) -> bool:
+        """ONE boolean for the whole batch (sylow_hip_kzg_cells_verify_weighted): two Miller loops and one final exponentiation."""
+        com_idx, idx, a, w = self._rows(com_idx, idx, cells, weights)
+        return engine().kzg_cells_verify_weighted(self.srs_g1.xy, self._single.tau_g2.xy, commitments.xy, idx, com_idx, a, pi.xy, w, self.log_c, self.log_l,
+                                                  commitments.infinity, pi.infinity)[1]
+
+    def verify_line_table(self, commitments: G1Affine, com_idx, idx, cells, pi: G1Affine, weights) -> bool:
+        """The same boolean over the cached line table of tau^l G2gen: reduce, then the one row through KzgVerifier.verify."""
+        f, p, ok = self.reduce(commitments, com_idx, idx, cells, pi, weights)
+        zero = np.zeros((1, 4), dtype=np.uint64)
+        return bool(self._single.verify((f, zero, zero, p))[0]) and ok
+
+
 class KzgCellRecovery:
     """A blob -- a polynomial of degree below n / 2 on a domain of n = 2^(log_c + log_l) points cut into c = 2^log_c cells of l = 2^log_l
     values, the cells of KzgProver.open_cosets -- from ANY c / 2 of its cells (sylow_hip_kzg_recover_batch).  It needs no SRS.  The

@@ -1484,6 +1484,64 @@ class Engine:
         coeffs = np.ascontiguousarray(dc.download()[:m].transpose(0, 2, 1))
         return coeffs, (np.ascontiguousarray(dyo.download()[:m].transpose(0, 2, 1)) if want_y else None), dst.download()[:m]
 
+    # ---- many cells of many KZG blobs as one boolean over shared commitments (include/sylow_hip_kzg_cells.h): row k is (idx_k < c,
+    # com_idx_k < n_com, cells[k] [l, 4], weights[k] [4]); a row out of range adds nothing and clears the flag unless its weight is 0 mod r ----
+    def _kzg_cell_rows_up(self, idx, com_idx, cells, weights, log_l):
+        rows, di, dv = self._kzg_cells_up(idx, cells, log_l)
+        com_idx = np.ascontiguousarray(com_idx, dtype=np.uint64).reshape(-1)
+        weights = _aos(weights, 4)
+        assert com_idx.shape[0] == rows and weights.shape[0] == rows, (com_idx.shape, weights.shape, rows)
+        return rows, di, (self.to_device(com_idx) if rows else None), dv, (self.to_device_soa(weights, 4) if rows else None)
+
+    def kzg_cells_fold(self, idx, com_idx, cells, weights, log_c, log_l, n_com, route=-1, max_blocks=-1):
+        """The Fr half of the check (sylow_hip_kzg_cells_fold_batch): (W [n_com, 4] = the weights summed per commitment, A [l, 4] = the
+        coefficients of sum_k r_k R_k, r [rows, 4] = the weights mod r, rz [rows, 4] = r_k v^idx_k, in_range: bool); r and rz are 0 for a
+        dropped row.  route 0 / 1 pins the row / column route and max_blocks >= 1 caps the blocks of a launch
+        (sylow_hip_kzg_cells_fold_batch_tuned); the words depend on neither."""
+        rows, di, dci, dv, dw = self._kzg_cell_rows_up(idx, com_idx, cells, weights, log_l)
+        n_com = int(n_com)
+        dwo, dao = self.empty((4, max(n_com, 1))), self.empty((4, 1 << log_l))
+        dr, drz, dg = self.empty((4, max(rows, 1))), self.empty((4, max(rows, 1))), self.empty((1,), np.uint8)
+        ins = [self._ptr(di), self._ptr(dci), self._ptr(dv), self._ptr(dw), log_c, log_l, rows, n_com]
+        outs = [dwo.ptr, dao.ptr, dr.ptr, drz.ptr, dg.ptr]
+        if route < 0 and max_blocks < 0:
+            self._call("sylow_hip_kzg_cells_fold_batch", *ins, *outs)
+        else:
+            self._call("sylow_hip_kzg_cells_fold_batch_tuned", *ins, int(route), int(max_blocks), *outs)
+        return (self.from_device_soa(dwo)[:n_com], self.from_device_soa(dao), self.from_device_soa(dr)[:rows], self.from_device_soa(drz)[:rows],
+                bool(dg.download()[0]))
+
+    def _kzg_cells_points_up(self, srs_g1, c_xy, pi_xy, c_inf, pi_inf, rows, log_l):
+        srs, c_xy, pi_xy = _aos(srs_g1, 8), _aos(c_xy, 8), _aos(pi_xy, 8)
+        n_com = c_xy.shape[0]
+        assert srs.shape[0] == 1 << log_l and pi_xy.shape[0] == rows, (srs.shape, pi_xy.shape, rows, log_l)
+        return n_com, (self.to_device_soa(srs, 8), self.to_device_soa(c_xy, 8) if n_com else None, self._flags(c_inf, n_com) if n_com else None,
+                       self.to_device_soa(pi_xy, 8) if rows else None, self._flags(pi_inf, rows) if rows else None)
+
+    def kzg_cells_reduce(self, srs_g1, c_xy, idx, com_idx, cells, pi_xy, weights, log_c, log_l, c_inf=None, pi_inf=None):
+        """The whole batch as ONE row of the single-point verifiers under tau^l G2gen (sylow_hip_kzg_cells_reduce_batch): (F [1, 8],
+        F flag [1], P [1, 8], P flag [1], in_range: bool) with F = sum_b W_b C_b + sum_k (r_k v^idx_k) pi_k - A(tau) G1gen and
+        P = sum_k r_k pi_k; the row is (F, z = 0, y = 0, P).  srs_g1 [l, 8] = tau^k G1gen, k < l; c_xy [n_com, 8]; pi_xy [rows, 8]."""
+        rows, di, dci, dv, dw = self._kzg_cell_rows_up(idx, com_idx, cells, weights, log_l)
+        n_com, (ds, dc, dcf, dp, dpf) = self._kzg_cells_points_up(srs_g1, c_xy, pi_xy, c_inf, pi_inf, rows, log_l)
+        df, dfi, dpo, dpi, dg = self.empty((8, 1)), self.empty((1,), np.uint8), self.empty((8, 1)), self.empty((1,), np.uint8), self.empty((1,), np.uint8)
+        self._call("sylow_hip_kzg_cells_reduce_batch", ds.ptr, self._ptr(dc), self._ptr(dcf), self._ptr(di), self._ptr(dci), self._ptr(dv), self._ptr(dp),
+                   self._ptr(dpf), self._ptr(dw), log_c, log_l, rows, n_com, df.ptr, dfi.ptr, dpo.ptr, dpi.ptr, dg.ptr)
+        return self.from_device_soa(df), dfi.download(), self.from_device_soa(dpo), dpi.download(), bool(dg.download()[0])
+
+    def kzg_cells_verify_weighted(self, srs_g1, tau_l_g2, c_xy, idx, com_idx, cells, pi_xy, weights, log_c, log_l, c_inf=None, pi_inf=None):
+        """"are ALL the cells valid?" as ONE Gt (sylow_hip_kzg_cells_verify_weighted): (Gt words [1, 48], is_one AND in_range: bool,
+        in_range: bool).  weights [rows, 4] drawn by the caller AFTER the rows are fixed (any 256-bit words, taken mod r; 0 removes a row).
+        tau_l_g2 [1, 16] = tau^l G2gen, taken as given."""
+        tau = _aos(tau_l_g2, 16)
+        assert tau.shape[0] == 1
+        rows, di, dci, dv, dw = self._kzg_cell_rows_up(idx, com_idx, cells, weights, log_l)
+        n_com, (ds, dc, dcf, dp, dpf) = self._kzg_cells_points_up(srs_g1, c_xy, pi_xy, c_inf, pi_inf, rows, log_l)
+        dtau, dgt, dis, dg = self.to_device_soa(tau, 16), self.empty((48, 1)), self.empty((1,), np.uint8), self.empty((1,), np.uint8)
+        self._call("sylow_hip_kzg_cells_verify_weighted", ds.ptr, dtau.ptr, self._ptr(dc), self._ptr(dcf), self._ptr(di), self._ptr(dci), self._ptr(dv),
+                   self._ptr(dp), self._ptr(dpf), self._ptr(dw), log_c, log_l, rows, n_com, dgt.ptr, dis.ptr, dg.ptr)
+        return self.from_device_soa(dgt), bool(dis.download()[0]), bool(dg.download()[0])
+
     # ---- Groth16, the prover's side.  A sparse matrix is CSR: (row_ptr [rows + 1], col [nnz], val [nnz, 4]); Fr batches are [m, n, 4] on the
     # host and [m][4][n] on the device; any 256-bit words, taken mod r ----
     def _csr_up(self, csr):
