@@ -11,15 +11,14 @@
 #include "host.hpp"
 #include "g1_ntt_plan.hpp"
 #include "g1_ntt_dev.hpp"
+#include "bn254_fr_dev.hpp"
 
 namespace g1ntt {
 using namespace g1_ntt_plan;
 static_assert(G1_NTT_BLOCK == BLOCK, "the kernels run blocks of BLOCK lanes");
 static_assert(G1_NTT_TABLE_BYTES_PER_LANE == G1_TABLE_BYTES_PER_LANE, "a lane's window table");
 
-struct Scalar {        // an Fr value as a kernel argument
-  u64 w[4];
-};
+struct Scalar : FrArg {};      // a kernel names its parameter types in its symbol: this one stays a type of this namespace so that the symbol does not move
 // Stage 0 over items (array, butterfly): U = in[j], V = in[j + n/2] from the caller's affine arrays [m][8][n] + [m][n], out[2j] = U + V,
 // out[2j + 1] = U - V into a projective buffer [12][stride], array a at columns a n ...
 __global__ void __launch_bounds__(BLOCK) k_g1_ntt_first(const u64* pxy, const uint8_t* pinf, u64* dst, int log_n, size_t total, size_t stride) {

@@ -1,7 +1,9 @@
-// g1_ntt_dev.hpp -- the device helpers the units that run butterflies over G1 points share (g1_ntt.hip, kzg_open_all.hip): how an input
-// point is read, and how a butterfly's two sums are stored.  Each unit compiles its own kernels around them (no relocatable device code).
+// g1_ntt_dev.hpp -- the device helpers the units that run butterflies over G1 points share (g1_ntt.hip, kzg_open_all.hip, kzg_cosets.hip):
+// how an input point is read, how the identity and a butterfly's two sums are stored.  Each unit compiles its own kernels around them (no
+// relocatable device code).
 #pragma once
 #include "common.hpp"
+#include "g1_ntt_plan.hpp"
 
 namespace g1ntt {
 // An input point.  The identity is a flagged point, whatever its words hold, or the pair (0, 1) that every call of this library writes for
@@ -10,6 +12,12 @@ BN_DEV G1P load_input(const u64* xy, const uint8_t* inf, size_t n, size_t i) {
   G1P p = load_g1_flagged(xy, inf, n, i);                 // a flagged point comes back as (0 : 1 : 0): the test below holds for it too
   p.z = fp_select(p.z, fp_zero(), fp_is_zero(p.x) && fp_eq(p.y, fp_one()));
   return p;
+}
+// the identity as every call of this library writes it: the words (0, 1) and the flag; affine SoA of stride n
+BN_DEV void store_identity(u64* xy, uint8_t* inf, size_t n, size_t i) {
+#pragma unroll
+  for (int w = 0; w < (int)g1_ntt_plan::G1_NTT_AFFINE_WORDS; ++w) xy[(size_t)w * n + i] = w == 4 ? 1 : 0;
+  inf[i] = 1;
 }
 BN_DEV G1W to_core(const G1P& p) { return G1W{f29_from_fp_reduced(p.x), f29_from_fp_reduced(p.y), f29_from_fp_reduced(p.z)}; }
 // Every intermediate with Z = 0 is stored as (0 : 1 : 0): the complete formulas keep Z = 0 only for that representative across consecutive

@@ -5,9 +5,11 @@
 #include "ntt_plan.hpp"
 
 namespace g1_ntt_plan {
-using ntt_plan::SAT;
-using ntt_plan::add_sat;
-using ntt_plan::mul_sat;
+using plan_base::SAT;
+using plan_base::add_sat;
+using plan_base::elems;
+using plan_base::max_blocks_ok;
+using plan_base::mul_sat;
 constexpr int G1_NTT_LOG_N_MAX = ntt_plan::NTT_LOG_N_MAX;
 constexpr int G1_NTT_BLOCK = 256;                        // == BLOCK of common.hpp (g1_ntt.hip asserts it)
 // A lane that multiplies keeps a window table of 1 KB in global memory (bn254_pairing.hpp: G1TableGlobal).  The tables are leased per RESIDENT
@@ -19,8 +21,6 @@ constexpr size_t G1_NTT_TABLE_BYTES_PER_LANE = 1024;     // == G1_TABLE_BYTES_PE
 constexpr size_t G1_NTT_PROJ_WORDS = 12, G1_NTT_AFFINE_WORDS = 8;
 
 constexpr bool log_n_ok(int log_n) { return log_n >= 0 && log_n <= G1_NTT_LOG_N_MAX; }
-constexpr bool max_blocks_ok(long long max_blocks) { return max_blocks != 0; }
-constexpr size_t elems(int log_n) { return (size_t)1 << log_n; }
 constexpr size_t half(int log_n) { return log_n ? (size_t)1 << (log_n - 1) : 0; }
 // points of the batch, m n, and the bytes of the caller's arrays (saturated): [m][8][n] words and [m][n] flags
 constexpr size_t points(int log_n, size_t m) { return mul_sat(elems(log_n), m); }

@@ -5,6 +5,7 @@
 // Lanes per row, grids, scratch and chunks: groth16_prove_plan.hpp -- nothing here decides one.
 #include "host.hpp"
 #include "bn254_fr_acc.hpp"
+#include "bn254_fr_dev.hpp"
 #include "bn254_groth16_zinv.hpp"
 #include "groth16_prove_plan.hpp"
 
@@ -13,19 +14,7 @@ using namespace g16_plan;
 static_assert(G16_BLOCK == BLOCK, "the kernels run blocks of BLOCK lanes");
 static_assert(BLOCK >> SPMV_LANES_LOG_MAX >= 1 && (1 << SPMV_LANES_LOG_MAX) <= 64, "the lanes of a row are lanes of one wavefront");
 
-struct Scalar {        // an Fr value as a kernel argument
-  u64 w[4];
-};
-BN_DEV Fp from_scalar(const Scalar& s) {
-  return fp_from_limbs((u32)s.w[0], (u32)(s.w[0] >> 32), (u32)s.w[1], (u32)(s.w[1] >> 32), (u32)s.w[2], (u32)(s.w[2] >> 32), (u32)s.w[3], (u32)(s.w[3] >> 32));
-}
-
-BN_DEV Fp shfl_xor_fp(const Fp& a, int off) {
-  Fp r;
-#pragma unroll
-  for (int w = 0; w < 8; ++w) r.v[w] = (u32)__shfl_xor((int)a.v[w], off);
-  return r;
-}
+struct Scalar : FrArg {};      // a kernel names its parameter types in its symbol: this one stays a type of this namespace so that the symbol does not move
 
 // out_j[i] = sum_e val_e w_j[col_e] over the entries e of row i, for the rows i < n_out of the arrays j < m (the grid's y, walked with a
 // stride past G16_GRID_Y_CAP); rows from `rows` on are the padding and come out zero.  2^lg lanes share a row: lane `sub` takes the entries

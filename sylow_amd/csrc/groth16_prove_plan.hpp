@@ -3,22 +3,21 @@
 // int32_t, int64_t, uint8_t and size_t only, so that tests/cpp/groth16_prove_plan_test.cpp can compile it with g++ on a box without a GPU.
 // The launch code asks these functions and decides nothing itself.
 #pragma once
-#include <cstddef>
-#include <cstdint>
+#include "plan_base.hpp"
 
 namespace g16_plan {
+using plan_base::SAT;
+using plan_base::add_sat;
+using plan_base::elems;
+using plan_base::mul_sat;
 constexpr int32_t G16_BLOCK = 256;               // == BLOCK of common.hpp (groth16_prove.hip asserts it)
 constexpr int32_t G16_LOG_N_MAX = 28;            // the domains of ntt_plan.hpp
 constexpr size_t G16_GRID_CAP = (size_t)1 << 20; // blocks of one launch in x; more work than that is walked with a grid stride
 constexpr size_t G16_GRID_Y_CAP = 65535;         // the batch index is the grid's y; more arrays than that are walked with a stride too
 constexpr uint64_t G16_COSET_SHIFT = 5;          // g: the quotient is formed on g <w_n> (the generator arkworks and gnark shift by)
 
-constexpr size_t SAT = (size_t)-1;
-constexpr size_t mul_sat(size_t a, size_t b) { return b && a > SAT / b ? SAT : a * b; }
-constexpr size_t add_sat(size_t a, size_t b) { return a > SAT - b ? SAT : a + b; }
 constexpr size_t ceil_div(size_t a, size_t b) { return a / b + (a % b ? 1 : 0); }
 constexpr bool log_n_ok(int32_t log_n) { return log_n >= 0 && log_n <= G16_LOG_N_MAX; }
-constexpr size_t elems(int32_t log_n) { return (size_t)1 << log_n; }
 
 // ---- the sparse product out_j = M w_j: 2^k lanes share a row, k = 0 .. 6 ---------------------------------------------------------------
 // A lane multiplies its entries into ONE unreduced 16-limb accumulator and reduces it (Barrett, about 2.4 products' worth of multiply-adds)

@@ -4,6 +4,7 @@
 // launches it always live in the same .hip file.
 #pragma once
 #include "common.hpp"
+#include "plan_base.hpp"
 
 #include <cstdio>
 #include <cstdlib>
@@ -13,6 +14,11 @@
 extern thread_local char sylow_g_err[256];
 namespace host {
 int32_t fail(hipError_t e, const char* what);
+// The aliasing check of an entry point: its inputs and outputs as two tables of Range, and outputs_disjoint(in, out, test) with the range test
+// it wants -- plan_base::disjoint, or plan_base::disjoint_or_empty where an empty array may point anywhere.  The text is plan_base.hpp's, so
+// that a host-only test can compile it.
+using plan_base::Range;
+using plan_base::outputs_disjoint;
 
 // Scratch workspace (runtime.hip).  A Lease hands out one device block for the duration of ONE entry-point call: blocks are
 // keyed per device, a block whose previous user ran on the same stream is reused in stream order, a block last used on another

@@ -9,6 +9,7 @@
 // Route, keys, teams, staging, slices, chunks, grids and scratch: kzg_cells_plan.hpp -- nothing here decides one.
 #include "host.hpp"
 #include "bn254_fr_acc.hpp"
+#include "bn254_fr_dev.hpp"
 #include "bn254_fr_roots.hpp"
 #include "kzg_cells_plan.hpp"
 #include "../../include/sylow_hip_kzg_cells.h"
@@ -21,36 +22,6 @@ static_assert(SYLOW_HIP_KZG_CELLS_LOG_N_MAX == CELLS_LOG_N_MAX, "the header's bo
 static_assert(CELLS_LOG_N_MAX <= SYLOW_HIP_KZG_COSETS_LOG_N_MAX && CELLS_LOG_N_MAX <= ntt_plan::NTT_LOG_N_MAX, "the domains of the calls the fold makes");
 typedef unsigned long long ull;
 static_assert(sizeof(ull) == sizeof(u64), "the atomics take the counts as they are");
-
-BN_DEV Fp fr_zero() { return fp_from_limbs(0, 0, 0, 0, 0, 0, 0, 0); }
-BN_DEV Fp fr_one() { return fp_from_limbs(1, 0, 0, 0, 0, 0, 0, 0); }
-BN_DEV Fp lds_get(const u32 (*a)[8], int i) { return fp_from_limbs(a[i][0], a[i][1], a[i][2], a[i][3], a[i][4], a[i][5], a[i][6], a[i][7]); }
-BN_DEV void lds_put(u32 (*a)[8], int i, const Fp& v) {
-#pragma unroll
-  for (int w = 0; w < 8; ++w) a[i][w] = v.v[w];
-}
-// v^i for i < c from the table of the transform of c points: v^(e + c / 2) = -v^e; 1 at c = 1, where there is no table
-BN_DEV Fp root(const u64* roots, int log_c, size_t i) {
-  if (log_c < 1) return fr_one();
-  const Fp p = load_plain(roots, elems(log_c - 1), root_slot(i, log_c), 0);
-  return root_negated(i, log_c) ? fr_neg(p) : p;
-}
-// b^e by squaring; e below 2^27
-BN_DEV Fp fr_pow(Fp b, u64 e) {
-  Fp p = fr_one();
-#pragma unroll 1
-  for (; e; e >>= 1) {
-    if (e & 1) p = fr_mul(p, b);
-    b = fr_mul(b, b);
-  }
-  return p;
-}
-BN_DEV Fp shfl_xor_fp(const Fp& a, int off) {
-  Fp r;
-#pragma unroll
-  for (int w = 0; w < 8; ++w) r.v[w] = __shfl_xor(a.v[w], off);
-  return r;
-}
 
 // One row per lane: the range test, the weight mod r, r v^i, the row's keys and their counts.  A row takes part when it is in range and
 // its weight is not 0 mod r; one that is out of range with a live weight clears the flag (every such lane stores the same 0).
@@ -66,7 +37,7 @@ __global__ void __launch_bounds__(BLOCK) k_cells_rows(const u64* idx, const u64*
     const bool zero = fp_is_zero(w), part = inside && !zero;
     if (!inside && !zero) in_range_flag[0] = 0;
     store_plain(r_out, rows, k, 0, part ? w : fr_zero());
-    store_plain(rz_out, rows, k, 0, part ? fr_mul(w, root(roots, log_c, (size_t)id)) : fr_zero());
+    store_plain(rz_out, rows, k, 0, part ? fr_mul(w, fr_root_from_half_table(roots, log_c, (size_t)id)) : fr_zero());
     if (route == ROUTE_COLUMNS) {
       keys[k] = part ? id : none;
       if (part) atomicAdd((ull*)cnt + id, 1ull);
@@ -195,6 +166,7 @@ __global__ void __launch_bounds__(BLOCK) k_cells_join(const u64* part, size_t ke
 // A wave holds whole items-of-a-t, and a wave past the last item holds none.
 __global__ void __launch_bounds__(BLOCK) k_cells_horner(const u64* a, int log_c, int log_l, size_t items, u64* out) {
   const size_t l = elems(log_l), lanes = (size_t)gridDim.x * BLOCK, chunk = horner_chunk(log_c);
+  // w_n by ntt_plan::root_squarings squarings, spelt out: behind a function the compiler closes this loop with the opposite branch
   Fp w = fp_from_limbs(BN_FR_ROOT28);
 #pragma unroll 1
   for (int i = 0; i < ntt_plan::root_squarings(log_n(log_c, log_l)); ++i) w = fr_mul(w, w);
@@ -296,21 +268,6 @@ static int32_t fold(const uint64_t* idx, const uint64_t* com_idx, const uint64_t
   return host::finish(rc, ws);
 }
 
-struct Range {
-  uintptr_t p;
-  size_t bytes;
-};
-// every output against every input and against the outputs after it
-template <size_t NI, size_t NO> static bool outputs_disjoint(const Range (&in)[NI], const Range (&out)[NO]) {
-  for (size_t o = 0; o < NO; ++o) {
-    if (!out[o].p) continue;
-    for (size_t i = 0; i < NI; ++i)
-      if (in[i].p && !disjoint(in[i].p, in[i].bytes, out[o].p, out[o].bytes)) return false;
-    for (size_t k = o + 1; k < NO; ++k)
-      if (out[k].p && !disjoint(out[k].p, out[k].bytes, out[o].p, out[o].bytes)) return false;
-  }
-  return true;
-}
 static bool sizes_ok(int log_c, int log_l, size_t rows, size_t n_com) {
   return vals_bytes(log_l, rows) != SAT && point_bytes(terms(rows, n_com)) != SAT && scratch_ok(fold_scratch_bytes(ROUTE_ROWS, log_c, log_l, rows, n_com)) &&
          scratch_ok(fold_scratch_bytes(ROUTE_COLUMNS, log_c, log_l, rows, n_com)) && scratch_ok(reduce_scratch_bytes(log_l, rows, n_com));
@@ -326,11 +283,11 @@ int32_t sylow_hip_kzg_cells_fold_batch_tuned(const uint64_t* idx, const uint64_t
   ARGCHK(a_out && in_range_out && (w_out || !n_com));
   ARGCHK(!rows || (idx && com_idx && vals && weights && r_out && rz_out));
   ARGCHK(kzce::sizes_ok(log_c, log_l, rows, n_com));
-  const kzce::Range in[4] = {{(uintptr_t)idx, index_bytes(rows)}, {(uintptr_t)com_idx, index_bytes(rows)}, {(uintptr_t)vals, vals_bytes(log_l, rows)},
+  const host::Range in[4] = {{(uintptr_t)idx, index_bytes(rows)}, {(uintptr_t)com_idx, index_bytes(rows)}, {(uintptr_t)vals, vals_bytes(log_l, rows)},
                              {(uintptr_t)weights, scalar_bytes(rows)}};
-  const kzce::Range out[5] = {{(uintptr_t)w_out, scalar_bytes(n_com)}, {(uintptr_t)a_out, scalar_bytes(elems(log_l))}, {(uintptr_t)r_out, scalar_bytes(rows)},
+  const host::Range out[5] = {{(uintptr_t)w_out, scalar_bytes(n_com)}, {(uintptr_t)a_out, scalar_bytes(elems(log_l))}, {(uintptr_t)r_out, scalar_bytes(rows)},
                               {(uintptr_t)rz_out, scalar_bytes(rows)}, {(uintptr_t)in_range_out, 1}};
-  ARGCHK(kzce::outputs_disjoint(in, out));
+  ARGCHK(host::outputs_disjoint(in, out, disjoint_or_empty));
   if (!rows) {                                                 // no row: the sums are zero and the flag is set
     const hipStream_t st = (hipStream_t)stream;
     if (n_com) HIPCHK(hipMemsetAsync(w_out, 0, scalar_bytes(n_com), st));
@@ -354,11 +311,11 @@ int32_t sylow_hip_kzg_cells_reduce_batch(const uint64_t* srs_g1_xy, const uint64
   ARGCHK(srs_g1_xy && f_xy && f_inf && p_xy && p_inf && in_range_out && (c_xy || !n_com));
   ARGCHK(!rows || (idx && com_idx && vals && pi_xy && weights));
   ARGCHK(kzce::sizes_ok(log_c, log_l, rows, n_com));
-  const kzce::Range in[9] = {{(uintptr_t)srs_g1_xy, point_bytes(elems(log_l))}, {(uintptr_t)c_xy, point_bytes(n_com)}, {(uintptr_t)c_inf, n_com},
+  const host::Range in[9] = {{(uintptr_t)srs_g1_xy, point_bytes(elems(log_l))}, {(uintptr_t)c_xy, point_bytes(n_com)}, {(uintptr_t)c_inf, n_com},
                              {(uintptr_t)idx, index_bytes(rows)}, {(uintptr_t)com_idx, index_bytes(rows)}, {(uintptr_t)vals, vals_bytes(log_l, rows)},
                              {(uintptr_t)pi_xy, point_bytes(rows)}, {(uintptr_t)pi_inf, rows}, {(uintptr_t)weights, scalar_bytes(rows)}};
-  const kzce::Range out[5] = {{(uintptr_t)f_xy, point_bytes(1)}, {(uintptr_t)f_inf, 1}, {(uintptr_t)p_xy, point_bytes(1)}, {(uintptr_t)p_inf, 1}, {(uintptr_t)in_range_out, 1}};
-  ARGCHK(kzce::outputs_disjoint(in, out));
+  const host::Range out[5] = {{(uintptr_t)f_xy, point_bytes(1)}, {(uintptr_t)f_inf, 1}, {(uintptr_t)p_xy, point_bytes(1)}, {(uintptr_t)p_inf, 1}, {(uintptr_t)in_range_out, 1}};
+  ARGCHK(host::outputs_disjoint(in, out, disjoint_or_empty));
   const hipStream_t st = (hipStream_t)stream;
   const size_t l = elems(log_l), total = terms(rows, n_com);
   host::Lease ws;
@@ -385,12 +342,12 @@ int32_t sylow_hip_kzg_cells_verify_weighted(const uint64_t* srs_g1_xy, const uin
   ARGCHK((gt_out || is_one) && srs_g1_xy && tau_l_g2_xy && (c_xy || !n_com));
   ARGCHK(!rows || (idx && com_idx && vals && pi_xy && weights));
   ARGCHK(kzce::sizes_ok(log_c, log_l, rows, n_com));
-  const kzce::Range in[10] = {{(uintptr_t)srs_g1_xy, point_bytes(elems(log_l))}, {(uintptr_t)tau_l_g2_xy, G2_WORDS * sizeof(uint64_t)}, {(uintptr_t)c_xy, point_bytes(n_com)},
+  const host::Range in[10] = {{(uintptr_t)srs_g1_xy, point_bytes(elems(log_l))}, {(uintptr_t)tau_l_g2_xy, G2_WORDS * sizeof(uint64_t)}, {(uintptr_t)c_xy, point_bytes(n_com)},
                               {(uintptr_t)c_inf, n_com}, {(uintptr_t)idx, index_bytes(rows)}, {(uintptr_t)com_idx, index_bytes(rows)},
                               {(uintptr_t)vals, vals_bytes(log_l, rows)}, {(uintptr_t)pi_xy, point_bytes(rows)}, {(uintptr_t)pi_inf, rows},
                               {(uintptr_t)weights, scalar_bytes(rows)}};
-  const kzce::Range out[3] = {{(uintptr_t)gt_out, 48 * sizeof(uint64_t)}, {(uintptr_t)is_one, 1}, {(uintptr_t)in_range_out, 1}};
-  ARGCHK(kzce::outputs_disjoint(in, out));
+  const host::Range out[3] = {{(uintptr_t)gt_out, 48 * sizeof(uint64_t)}, {(uintptr_t)is_one, 1}, {(uintptr_t)in_range_out, 1}};
+  ARGCHK(host::outputs_disjoint(in, out, disjoint_or_empty));
   const hipStream_t st = (hipStream_t)stream;
   host::Lease ws;
   int32_t rc = ws.acquire(verify_scratch_bytes(), st);

@@ -7,10 +7,15 @@
 #include "ntt_plan.hpp"
 
 namespace kzg_cells_plan {
-using ntt_plan::SAT;
-using ntt_plan::add_sat;
-using ntt_plan::mul_sat;
-using ntt_plan::elems;
+using plan_base::SAT;
+using plan_base::add_sat;
+using plan_base::disjoint_or_empty;      // an empty array of the caller overlaps nothing here
+using plan_base::elems;
+using plan_base::max_blocks_ok;
+using plan_base::mul_sat;
+using ntt_plan::root_negated;
+using ntt_plan::root_slot;
+using ntt_plan::root_words;
 constexpr int CELLS_BLOCK = 256;                      // == BLOCK of common.hpp (kzg_cells.hip asserts it)
 constexpr int CELLS_BLOCK_LOG = 8;
 constexpr int CELLS_WAVE = 64;
@@ -22,8 +27,6 @@ constexpr size_t CELLS_RESIDENT_LANES = (size_t)256 * 4 * 4 * CELLS_WAVE;
 
 constexpr int log_n(int log_c, int log_l) { return log_c + log_l; }
 constexpr bool logs_ok(int log_c, int log_l) { return log_c >= 0 && log_l >= 0 && log_c <= CELLS_LOG_N_MAX && log_l <= CELLS_LOG_N_MAX && log_n(log_c, log_l) <= CELLS_LOG_N_MAX; }
-constexpr bool max_blocks_ok(long long max_blocks) { return max_blocks != 0; }
-constexpr bool disjoint(uintptr_t a, size_t a_bytes, uintptr_t b, size_t b_bytes) { return !a_bytes || !b_bytes || a + a_bytes <= b || b + b_bytes <= a; }
 constexpr size_t blocks_of(size_t lanes) { return lanes / CELLS_BLOCK + (lanes % CELLS_BLOCK ? 1 : 0); }          // no sum that could wrap
 constexpr size_t grid(size_t blocks, long long max_blocks) {
   const size_t cap = max_blocks > 0 && (unsigned long long)max_blocks < CELLS_GRID_CAP ? (size_t)max_blocks : CELLS_GRID_CAP;
@@ -57,10 +60,7 @@ constexpr bool in_range(uint64_t idx, int log_c) { return idx < ((uint64_t)1 << 
 constexpr size_t rows_grid(size_t rows, long long max_blocks) { return grid(blocks_of(rows), max_blocks); }
 constexpr size_t scatter_grid(int route, size_t rows, long long max_blocks) { return grid(blocks_of(entries(route, rows)), max_blocks); }
 constexpr size_t scan_rounds(size_t keys) { return blocks_of(keys); }
-// v^i, i < c, from the table of the transform of c points (v^e for e < c / 2): v^(e + c / 2) = -v^e; 1 at c = 1, where there is no table
-constexpr size_t root_words(int log_c) { return ntt_plan::table_words(log_c); }
-constexpr bool root_negated(size_t i, int log_c) { return log_c >= 1 && i >= elems(log_c - 1); }
-constexpr size_t root_slot(size_t i, int log_c) { return root_negated(i, log_c) ? i - elems(log_c - 1) : i; }
+// v^i, i < c, from the table of the transform of c points: root_words, root_slot and root_negated of ntt_plan.hpp
 
 // ---- the keyed multiply-accumulate: out[key][col] = sum over the rows of the key's group of r_row val_row[col], col < 2^log_cols.  The
 // work items are (key, column) FLATTENED, key-major, so that rows of 1 .. 8 columns still fill wavefronts; a block takes a tile of

@@ -10,6 +10,7 @@
 // Geometry, planes, ping-pong, grids and scratch: kzg_cosets_plan.hpp -- nothing here decides one.
 #include "host.hpp"
 #include "g1_ntt_dev.hpp"
+#include "bn254_fr_dev.hpp"
 #include "bn254_fr_roots.hpp"
 #include "kzg_cosets_plan.hpp"
 #include "../../include/sylow_hip_kzg_cosets.h"
@@ -19,23 +20,13 @@ using namespace kzg_cosets_plan;
 using g1ntt::butterfly_store;
 using g1ntt::load_input;
 using g1ntt::store_canonical;
+using g1ntt::store_identity;
 using g1ntt::to_core;
 static_assert(g1_ntt_plan::G1_NTT_BLOCK == BLOCK, "the kernels run blocks of BLOCK lanes");
 static_assert(g1_ntt_plan::G1_NTT_TABLE_BYTES_PER_LANE == G1_TABLE_BYTES_PER_LANE, "a lane's window table");
 static_assert(SYLOW_HIP_KZG_COSETS_LOG_N_MAX == COSETS_LOG_N_MAX, "the header's bound is the plan's");
 
-struct Scalar {        // an Fr value as a kernel argument
-  u64 w[4];
-};
-BN_DEV Fp from_scalar(const Scalar& s) {
-  return fp_from_limbs((u32)s.w[0], (u32)(s.w[0] >> 32), (u32)s.w[1], (u32)(s.w[1] >> 32), (u32)s.w[2], (u32)(s.w[2] >> 32), (u32)s.w[3], (u32)(s.w[3] >> 32));
-}
-// the identity as every call of this library writes it: the words (0, 1) and the flag
-BN_DEV void store_identity(u64* xy, uint8_t* inf, size_t n, size_t i) {
-#pragma unroll
-  for (int w = 0; w < (int)G1_NTT_AFFINE_WORDS; ++w) xy[(size_t)w * n + i] = w == 4 ? 1 : 0;
-  inf[i] = 1;
-}
+struct Scalar : FrArg {};      // a kernel names its parameter types in its symbol: this one stays a type of this namespace so that the symbol does not move
 
 // the l arrays x^(a) of the plan, [l][8][2c] + [l][2c]: the SRS point x_srs_index names, word for word, or the identity
 __global__ void __launch_bounds__(BLOCK) k_open_cosets_x(const u64* srs, int log_c, int log_l, size_t total, u64* xy, uint8_t* inf) {
@@ -131,25 +122,15 @@ __global__ void __launch_bounds__(BLOCK) k_open_cosets_fold(const u64* src, u64*
   }
 }
 
-BN_DEV Fp fr_one() { return fp_from_limbs(1, 0, 0, 0, 0, 0, 0, 0); }
-// b^e by squaring; e below 2^28
-BN_DEV Fp fr_pow(Fp b, u64 e) {
-  Fp p = fr_one();
-#pragma unroll 1
-  for (; e; e >>= 1) {
-    if (e & 1) p = fr_mul(p, b);
-    b = fr_mul(b, b);
-  }
-  return p;
-}
 // Item (row, lane q of 2^lanes_log): r_k <- r_k g^k for k = q, q + lanes, .. with g = w^(-idx) and a running product.  Lane 0 of the row
 // writes z = v^idx and the range flag where the caller wants them (z, in_range_out: either may be NULL).
 __global__ void __launch_bounds__(BLOCK) k_coset_twist(u64* r, const u64* idx, int log_c, int log_l, size_t total, size_t n_rows, u64* z, uint8_t* in_range_out) {
   const size_t l = elems(log_l), lanes = (size_t)gridDim.x * BLOCK;
   const int ql = twist_lanes_log(log_l);
+  // w_n by ntt_plan::root_squarings squarings, spelt out: behind a function the compiler closes this loop with the opposite branch
   Fp w = fp_from_limbs(BN_FR_ROOT28);
 #pragma unroll 1
-  for (int i = 0; i < ntt_plan::NTT_LOG_N_MAX - log_n(log_c, log_l); ++i) w = fr_mul(w, w);
+  for (int i = 0; i < ntt_plan::root_squarings(log_n(log_c, log_l)); ++i) w = fr_mul(w, w);
 #pragma unroll 1
   for (size_t i = TID; i < total; i += lanes) {
     const size_t row = i >> ql, q = i & (elems(ql) - 1);

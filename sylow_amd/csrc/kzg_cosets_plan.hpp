@@ -9,19 +9,19 @@
 
 namespace kzg_cosets_plan {
 namespace oa = kzg_open_all_plan;
-using g1_ntt_plan::SAT;
-using g1_ntt_plan::add_sat;
-using g1_ntt_plan::mul_sat;
+using plan_base::SAT;
+using plan_base::add_sat;
+using plan_base::disjoint;
+using plan_base::elems;
+using plan_base::max_blocks_ok;
+using plan_base::mul_sat;
 using g1_ntt_plan::G1_NTT_AFFINE_WORDS;
 using g1_ntt_plan::G1_NTT_PROJ_WORDS;
-using g1_ntt_plan::max_blocks_ok;
 using oa::FR_WORDS;
-using oa::disjoint;
 constexpr int COSETS_LOG_N_MAX = oa::OPEN_ALL_LOG_N_MAX;                   // the transform of 2c points must fit the 2^28 roots even at l = 1
 
 constexpr bool logs_ok(int log_c, int log_l) { return log_c >= 0 && log_l >= 0 && log_c <= COSETS_LOG_N_MAX && log_l <= COSETS_LOG_N_MAX && log_c + log_l <= COSETS_LOG_N_MAX; }
 constexpr int log_n(int log_c, int log_l) { return log_c + log_l; }
-constexpr size_t elems(int lg) { return (size_t)1 << lg; }
 constexpr int wide_log(int log_c) { return oa::wide_log(log_c); }           // the convolutions run on 2c points
 constexpr size_t wide(int log_c) { return oa::wide(log_c); }
 

@@ -7,6 +7,7 @@
 // Geometry and scratch: kzg_evals_plan.hpp -- nothing here decides one.
 #include "host.hpp"
 #include "bn254_fr_euclid.hpp"
+#include "bn254_fr_dev.hpp"
 #include "bn254_fr_roots.hpp"
 #include "kzg_evals_plan.hpp"
 #include "ntt_plan.hpp"
@@ -17,19 +18,7 @@ static_assert(EVALS_BLOCK == BLOCK, "the kernels run one chunk per block of BLOC
 static_assert(EVALS_LOG_N_MAX == ntt_plan::NTT_LOG_N_MAX, "the domains of the transform");
 constexpr int L = EVALS_LANE_ELEMS, CH = (int)EVALS_CHUNK, W_INV = EVALS_LOG_N_MAX;      // W_INV: the slot of w^-1
 
-BN_DEV Fp fr_zero() { return fp_from_limbs(0, 0, 0, 0, 0, 0, 0, 0); }
-BN_DEV Fp fr_one() { return fp_from_limbs(1, 0, 0, 0, 0, 0, 0, 0); }
-BN_DEV Fp lds_get(const u32 (*a)[8], int i) { return fp_from_limbs(a[i][0], a[i][1], a[i][2], a[i][3], a[i][4], a[i][5], a[i][6], a[i][7]); }
-BN_DEV void lds_put(u32 (*a)[8], int i, const Fp& v) {
-#pragma unroll
-  for (int w = 0; w < 8; ++w) a[i][w] = v.v[w];
-}
-struct Scalar {        // an Fr value as a kernel argument
-  u64 w[4];
-};
-BN_DEV Fp from_scalar(const Scalar& s) {
-  return fp_from_limbs((u32)s.w[0], (u32)(s.w[0] >> 32), (u32)s.w[1], (u32)(s.w[1] >> 32), (u32)s.w[2], (u32)(s.w[2] >> 32), (u32)s.w[3], (u32)(s.w[3] >> 32));
-}
+struct Scalar : FrArg {};      // a kernel names its parameter types in its symbol: this one stays a type of this namespace so that the symbol does not move
 // element k of an Fr SoA array of stride n, mod r
 BN_DEV Fp elem(const u64* a, size_t n, size_t k) { return fr_reduce_plain(load_plain(a, n, k, 0)); }
 // the inverse of ONE nonzero canonical value, for a lone lane: binary extended Euclid, no product (bn254_fr_euclid.hpp)
@@ -132,9 +121,10 @@ __global__ void __launch_bounds__(BLOCK) k_fr_batch_inv(const u64* a, u64* out, 
 __global__ void __launch_bounds__(BLOCK) k_evals_roots(int log_n, u64* roots, u64* hit, size_t m) {
   for (size_t j = TID; j < m; j += (size_t)gridDim.x * BLOCK) hit[j] = NO_HIT;
   if (blockIdx.x || threadIdx.x >= 64) return;
+  // w_n by ntt_plan::root_squarings squarings, spelt out: behind a function the compiler closes this loop with the opposite branch
   Fp p = fp_from_limbs(BN_FR_ROOT28), wi = fr_one();
 #pragma unroll 1
-  for (int i = 0; i < EVALS_LOG_N_MAX - log_n; ++i) p = fr_mul(p, p);
+  for (int i = 0; i < ntt_plan::root_squarings(log_n); ++i) p = fr_mul(p, p);
 #pragma unroll 1
   for (int s = 0; s < log_n; ++s) {
     if (threadIdx.x == 0) store_plain(roots + 4 * s, 1, 0, 0, p);

@@ -2,10 +2,13 @@
 // every size, grid, scratch and route decision between an entry point and its kernels, plain C++ so that tests/cpp/kzg_evals_plan_test.cpp
 // can compile it with g++ on a box without a GPU.  The launch code asks these functions and decides nothing itself.
 #pragma once
-#include <cstddef>
-#include <cstdint>
+#include "plan_base.hpp"
 
 namespace kzg_evals_plan {
+using plan_base::SAT;
+using plan_base::add_sat;
+using plan_base::elems;
+using plan_base::mul_sat;
 // ---- the chunk: a lane owns EVALS_LANE_ELEMS consecutive elements, a block of EVALS_BLOCK lanes a chunk of EVALS_CHUNK -------------------
 // The elements of a chunk share ONE inversion: prefix products inside a lane, a prefix and a suffix scan of the lane totals through LDS, the
 // inverse of the chunk's product on one lane (bn254_fr_euclid.hpp), and the way back.  There is no level above the chunk: every chunk pays
@@ -16,10 +19,6 @@ constexpr size_t EVALS_CHUNK = 2048;             // CH = EVALS_BLOCK * EVALS_LAN
 static_assert(EVALS_CHUNK == (size_t)EVALS_BLOCK * EVALS_LANE_ELEMS, "a chunk is a block of lanes");
 constexpr size_t EVALS_GRID_CAP = (size_t)1 << 20;       // blocks of one launch; more work than that is walked with a grid stride
 constexpr int EVALS_LOG_N_MAX = 28;              // r - 1 = 2^28 * odd, as ntt_plan.hpp
-
-constexpr size_t SAT = (size_t)-1;
-constexpr size_t mul_sat(size_t a, size_t b) { return b && a > SAT / b ? SAT : a * b; }
-constexpr size_t add_sat(size_t a, size_t b) { return a > SAT - b ? SAT : a + b; }
 
 constexpr size_t chunks(size_t n) { return n / EVALS_CHUNK + (n % EVALS_CHUNK ? 1 : 0); }
 constexpr size_t grid(size_t items) { return items < EVALS_GRID_CAP ? items : EVALS_GRID_CAP; }
@@ -45,7 +44,6 @@ constexpr size_t fr_array_bytes(size_t n) { return mul_sat(mul_sat(n, 4), sizeof
 // (polynomial, chunk): d_i^-1 into q_out, the chunk's part of sum f_i w^i / d_i, the index of a hit);  value (a block per polynomial: y);
 // and, when the quotient is wanted,  quot (a block per (polynomial, chunk): q_i over d_i^-1 in place, and for a row with a hit the chunk's
 // part of sum q_i w^i)  and  repair (a block per polynomial: q_k of a row with a hit).
-constexpr size_t elems(int log_n) { return (size_t)1 << log_n; }
 constexpr size_t poly_chunks(int log_n) { return chunks(elems(log_n)); }
 // (polynomial, chunk) pairs.  m 2^log_n is the caller's array; no product here is larger than it
 constexpr size_t items(int log_n, size_t m) { return poly_chunks(log_n) * m; }

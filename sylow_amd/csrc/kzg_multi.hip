@@ -5,20 +5,13 @@
 // Tiles, grids, the flush length, scratch and the chunks of the combined commitments: kzg_multi_plan.hpp -- nothing here decides one.
 #include "host.hpp"
 #include "bn254_fr_acc.hpp"
+#include "bn254_fr_dev.hpp"
 #include "kzg_multi_plan.hpp"
 
 namespace kzgm {
 using namespace kzgm_plan;
 static_assert(KZGM_BLOCK == BLOCK, "the kernels run blocks of BLOCK lanes");
 constexpr int T = (int)KZGM_LINCOMB_TILE, FL = KZGM_LINCOMB_FLUSH;
-
-BN_DEV Fp fr_zero() { return fp_from_limbs(0, 0, 0, 0, 0, 0, 0, 0); }
-BN_DEV Fp fr_one() { return fp_from_limbs(1, 0, 0, 0, 0, 0, 0, 0); }
-BN_DEV Fp lds_get(const u32 (*a)[8], int i) { return fp_from_limbs(a[i][0], a[i][1], a[i][2], a[i][3], a[i][4], a[i][5], a[i][6], a[i][7]); }
-BN_DEV void lds_put(u32 (*a)[8], int i, const Fp& v) {
-#pragma unroll
-  for (int w = 0; w < 8; ++w) a[i][w] = v.v[w];
-}
 
 // group_start on its way to the device: `count` offsets from the launch's own arguments to dst
 struct Offsets {

@@ -3,10 +3,10 @@
 // C++ so that tests/cpp/kzg_multi_plan_test.cpp can compile it with g++ on a box without a GPU.  The launch code asks these functions and
 // decides nothing itself.
 #pragma once
-#include <cstddef>
-#include <cstdint>
+#include "plan_base.hpp"
 
 namespace kzgm_plan {
+using plan_base::SAT;
 // ---- groups ------------------------------------------------------------------------------------------------------------------------
 // group_start is a HOST array of G + 1 offsets: non-decreasing, group_start[0] = 0, group_start[G] = m.  Empty groups are legal.
 constexpr bool groups_ok(const uint64_t* group_start, size_t G, size_t m) {
@@ -52,7 +52,6 @@ constexpr size_t lane_grid(size_t n) { return (n + KZGM_BLOCK - 1) / KZGM_BLOCK 
 constexpr size_t group_grid(size_t G) { return G < KZGM_LANE_GRID_CAP ? G : KZGM_LANE_GRID_CAP; }
 
 // ---- scratch, in u64 words; (size_t)-1 = does not fit size_t (the entry point refuses it before the lease) ----------------------------
-constexpr size_t SAT = (size_t)-1;
 constexpr size_t sat_mul(size_t a, size_t b) { return a && b > SAT / a ? SAT : a * b; }
 constexpr size_t sat_add(size_t a, size_t b) { return a > SAT - b ? SAT : a + b; }
 // the prover: the offsets, the powers [4][m], z spread [4][m], the folded polynomials [G][4][len] (32 G len bytes) and their values [4][G]

@@ -10,28 +10,19 @@
 // Geometry, ping-pong, grids and scratch: kzg_open_all_plan.hpp -- nothing here decides one.
 #include "host.hpp"
 #include "g1_ntt_dev.hpp"
+#include "bn254_fr_dev.hpp"
 #include "kzg_open_all_plan.hpp"
 
 namespace kzoa {
 using namespace kzg_open_all_plan;
 using g1ntt::butterfly_store;
 using g1ntt::load_input;
+using g1ntt::store_identity;
 using g1ntt::to_core;
 static_assert(g1_ntt_plan::G1_NTT_BLOCK == BLOCK, "the kernels run blocks of BLOCK lanes");
 static_assert(g1_ntt_plan::G1_NTT_TABLE_BYTES_PER_LANE == G1_TABLE_BYTES_PER_LANE, "a lane's window table");
 
-struct Scalar {        // an Fr value as a kernel argument
-  u64 w[4];
-};
-BN_DEV Fp from_scalar(const Scalar& s) {
-  return fp_from_limbs((u32)s.w[0], (u32)(s.w[0] >> 32), (u32)s.w[1], (u32)(s.w[1] >> 32), (u32)s.w[2], (u32)(s.w[2] >> 32), (u32)s.w[3], (u32)(s.w[3] >> 32));
-}
-// the identity as every call of this library writes it: the words (0, 1) and the flag
-BN_DEV void store_identity(u64* xy, uint8_t* inf, size_t n, size_t i) {
-#pragma unroll
-  for (int w = 0; w < (int)G1_NTT_AFFINE_WORDS; ++w) xy[(size_t)w * n + i] = w == 4 ? 1 : 0;
-  inf[i] = 1;
-}
+struct Scalar : FrArg {};      // a kernel names its parameter types in its symbol: this one stays a type of this namespace so that the symbol does not move
 
 // x of the plan over its 2n columns: the SRS point x_srs_index names, word for word, or the identity
 __global__ void __launch_bounds__(BLOCK) k_open_all_x(const u64* srs, int log_n, u64* xy, uint8_t* inf) {

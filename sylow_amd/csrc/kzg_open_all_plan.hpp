@@ -8,24 +8,24 @@
 #include "g1_ntt_plan.hpp"
 
 namespace kzg_open_all_plan {
-using g1_ntt_plan::SAT;
-using g1_ntt_plan::add_sat;
-using g1_ntt_plan::mul_sat;
+using plan_base::SAT;
+using plan_base::add_sat;
+using plan_base::disjoint;
+using plan_base::elems;
+using plan_base::max_blocks_ok;
+using plan_base::mul_sat;
 using g1_ntt_plan::G1_NTT_AFFINE_WORDS;
 using g1_ntt_plan::G1_NTT_PROJ_WORDS;
-using g1_ntt_plan::max_blocks_ok;
 constexpr int OPEN_ALL_LOG_N_MAX = g1_ntt_plan::G1_NTT_LOG_N_MAX - 1;        // the transform of 2n points must fit the 2^28 roots
 constexpr size_t FR_WORDS = 4;
 
 constexpr bool log_n_ok(int log_n) { return log_n >= 0 && log_n <= OPEN_ALL_LOG_N_MAX; }
 constexpr int wide_log(int log_n) { return log_n + 1; }                      // the convolution runs on 2n points
-constexpr size_t elems(int log_n) { return (size_t)1 << log_n; }
 constexpr size_t wide(int log_n) { return (size_t)2 << log_n; }
 // the caller's arrays, bytes, saturated: the table [8][2n] + [2n], the polynomials and y [m][4][n], the proofs [m][8][n] + [m][n]
 constexpr size_t table_xy_bytes(int log_n) { return g1_ntt_plan::xy_bytes(wide_log(log_n), 1); }
 constexpr size_t fr_bytes(int log_n, size_t m) { return mul_sat(mul_sat(elems(log_n), m), FR_WORDS * sizeof(uint64_t)); }
 constexpr size_t pi_xy_bytes(int log_n, size_t m) { return g1_ntt_plan::xy_bytes(log_n, m); }
-constexpr bool disjoint(uintptr_t a, size_t a_bytes, uintptr_t b, size_t b_bytes) { return a + a_bytes <= b || b + b_bytes <= a; }
 
 // ---- the table: T = the forward transform of x, 2n points with x_(2n-1-t) = s_t for t <= n - 2 and the identity everywhere else -------------
 // which SRS point column k < 2n of x holds, or X_IDENTITY: s_(n-1) is not used, and columns 0 .. n hold the identity

@@ -19,7 +19,6 @@ static_assert(KZGPT_BLOCK == BLOCK, "the kernels run blocks of BLOCK lanes");
 static_assert(KZGPT_MAX_POINTS == SYLOW_HIP_KZG_POINTS_MAX, "the header states the plan's limit");
 constexpr int RB = KZGPT_ROW_BLOCK, MAXK = (int)KZGPT_MAX_POINTS;
 
-BN_DEV Fp fr_one() { return fp_from_limbs(1, 0, 0, 0, 0, 0, 0, 0); }
 // element i of an Fr SoA array of stride n, mod r
 BN_DEV Fp elem(const u64* a, size_t n, size_t i) { return fr_reduce_plain(load_plain(a, n, i, 0)); }
 

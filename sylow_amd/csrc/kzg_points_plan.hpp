@@ -3,19 +3,17 @@
 // tests/cpp/kzg_points_plan_test.cpp can compile it with g++ on a box without a GPU.  The launch code asks these functions and decides nothing
 // itself.  The lane and chunk geometry of the scan is kzg_prove_plan.hpp's: the kernels here run the same scan once per point.
 #pragma once
-#include <cstddef>
-#include <cstdint>
-
 #include "kzg_prove_plan.hpp"
+#include "plan_base.hpp"
 
 namespace kzgpt_plan {
+using plan_base::SAT;                                  // "does not fit size_t": the entry point refuses it before any lease
 constexpr size_t KZGPT_MAX_POINTS = 64;                 // k of one call, at most: a data-availability cell
 constexpr int KZGPT_BLOCK = 256;                        // == BLOCK of common.hpp (kzg_points.hip asserts it)
 constexpr int KZGPT_ROW_BLOCK = 64;                     // the Fr half of the verifier: ONE wavefront per row, lane i on point i
 static_assert((size_t)KZGPT_ROW_BLOCK >= KZGPT_MAX_POINTS, "a lane per point");
 constexpr size_t KZGPT_GRID_CAP = (size_t)1 << 20;      // blocks of one launch; more work than that is walked with a grid stride
 
-constexpr size_t SAT = (size_t)-1;                      // "does not fit size_t": the entry point refuses it before any lease
 constexpr size_t sat_mul(size_t a, size_t b) { return a && b > SAT / a ? SAT : a * b; }
 constexpr size_t sat_add(size_t a, size_t b) { return a > SAT - b ? SAT : a + b; }
 constexpr bool points_ok(size_t k) { return k >= 1 && k <= KZGPT_MAX_POINTS; }

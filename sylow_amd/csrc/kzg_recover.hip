@@ -7,6 +7,7 @@
 // Rows that miss too many cells take no branch: their zd is zero, so is everything after it.
 // Items, staging, grids and scratch: kzg_recover_plan.hpp -- nothing here decides one.
 #include "host.hpp"
+#include "bn254_fr_dev.hpp"
 #include "kzg_recover_plan.hpp"
 #include "../../include/sylow_hip_kzg_recover.h"
 
@@ -16,27 +17,6 @@ static_assert(RECOVER_BLOCK == BLOCK && RECOVER_WAVES * RECOVER_WAVE == BLOCK, "
 static_assert(SYLOW_HIP_KZG_RECOVER_LOG_C_MAX == RECOVER_LOG_C_MAX && SYLOW_HIP_KZG_RECOVER_LOG_N_MAX == RECOVER_LOG_N_MAX, "the header's bounds are the plan's");
 static_assert(RECOVER_LOG_N_MAX <= ntt_plan::NTT_LOG_N_MAX, "the domains of the transform");
 static_assert(VANISH_CHUNK == BLOCK, "a staging round takes one mask byte per lane");
-
-BN_DEV Fp fr_zero() { return fp_from_limbs(0, 0, 0, 0, 0, 0, 0, 0); }
-BN_DEV Fp fr_one() { return fp_from_limbs(1, 0, 0, 0, 0, 0, 0, 0); }
-BN_DEV Fp lds_get(const u32 (*a)[8], int i) { return fp_from_limbs(a[i][0], a[i][1], a[i][2], a[i][3], a[i][4], a[i][5], a[i][6], a[i][7]); }
-BN_DEV void lds_put(u32 (*a)[8], int i, const Fp& v) {
-#pragma unroll
-  for (int w = 0; w < 8; ++w) a[i][w] = v.v[w];
-}
-// v^i for i < c from the table of the transform of c points: v^(e + c / 2) = -v^e; 1 at c = 1, where there is no table
-BN_DEV Fp root(const u64* roots, int log_c, size_t i) {
-  if (log_c < 1) return fr_one();
-  const Fp p = load_plain(roots, elems(log_c - 1), root_slot(i, log_c), 0);
-  return root_negated(i, log_c) ? fr_neg(p) : p;
-}
-
-BN_DEV Fp shfl_xor_fp(const Fp& a, int off) {
-  Fp r;
-#pragma unroll
-  for (int w = 0; w < 8; ++w) r.v[w] = __shfl_xor(a.v[w], off);
-  return r;
-}
 
 // consts: s as the transforms read their shift, then s^l by log_l squarings -- one lane, once per call
 __global__ void __launch_bounds__(BLOCK) k_recover_consts(int log_l, u64* consts) {
@@ -82,7 +62,7 @@ __global__ void __launch_bounds__(BLOCK) k_recover_vanish(const uint8_t* present
     if (vanish_k0(item, log_c) == 0 && t == 0) status[row] = refused ? 1 : 0;
     Fp pd = refused ? fr_zero() : fr_one(), pc = fr_one();
     if (!refused && missing) {
-      const Fp a = live ? root(roots, log_c, k) : fr_one(), b = fr_mul(sl, a);
+      const Fp a = live ? fr_root_from_half_table(roots, log_c, k) : fr_one(), b = fr_mul(sl, a);
 #pragma unroll 1
       for (size_t round = 0; round < vanish_rounds(log_c); ++round) {
         const size_t i = round * VANISH_CHUNK + t;
@@ -96,7 +76,7 @@ __global__ void __launch_bounds__(BLOCK) k_recover_vanish(const uint8_t* present
           base += w < wv ? waves[w] : 0u;
           staged += waves[w];
         }
-        if (miss) lds_put(list, (int)(base + (u32)__popcll(bal & (((unsigned long long)1 << lane) - 1))), root(roots, log_c, i));
+        if (miss) lds_put(list, (int)(base + (u32)__popcll(bal & (((unsigned long long)1 << lane) - 1))), fr_root_from_half_table(roots, log_c, i));
         __syncthreads();
 #pragma unroll 1
         for (u32 j = sub; j < staged; j += split) {
@@ -234,9 +214,9 @@ int32_t sylow_hip_kzg_recover_vanish_batch(const uint8_t* present, int32_t log_c
   ARGCHK(present && zd_out && zc_out && status_out);
   const size_t pb = present_bytes(log_c, m), zb = z_bytes(log_c, m), sb = status_bytes(m);
   ARGCHK(pb != SAT && zb != SAT);
-  const uintptr_t p = (uintptr_t)present, d = (uintptr_t)zd_out, c = (uintptr_t)zc_out, s = (uintptr_t)status_out;
-  ARGCHK(disjoint(p, pb, d, zb) && disjoint(p, pb, c, zb) && disjoint(p, pb, s, sb));
-  ARGCHK(disjoint(d, zb, c, zb) && disjoint(d, zb, s, sb) && disjoint(c, zb, s, sb));
+  const host::Range in[1] = {{(uintptr_t)present, pb}};
+  const host::Range out[3] = {{(uintptr_t)zd_out, zb}, {(uintptr_t)zc_out, zb}, {(uintptr_t)status_out, sb}};
+  ARGCHK(host::outputs_disjoint(in, out, disjoint));
   host::Lease ws;
   int32_t rc = ws.acquire(vanish_scratch_bytes(log_c), (hipStream_t)stream);
   if (rc != SYLOW_HIP_OK) return rc;
@@ -252,9 +232,9 @@ int32_t sylow_hip_kzg_recover_batch(const uint64_t* y, const uint8_t* present, i
   ARGCHK(y && present && coeffs_out && status_out);
   const size_t fb = fr_bytes(log_c, log_l, m), pb = present_bytes(log_c, m), sb = status_bytes(m);
   ARGCHK(fb != SAT && pb != SAT && scratch_ok(recover_scratch_bytes(log_c, log_l, m)));
-  const uintptr_t a = (uintptr_t)y, p = (uintptr_t)present, o = (uintptr_t)coeffs_out, yo = (uintptr_t)y_out, s = (uintptr_t)status_out;
-  ARGCHK(disjoint(a, fb, o, fb) && disjoint(p, pb, o, fb) && disjoint(a, fb, s, sb) && disjoint(p, pb, s, sb) && disjoint(o, fb, s, sb));
-  ARGCHK(!y_out || (disjoint(a, fb, yo, fb) && disjoint(p, pb, yo, fb) && disjoint(o, fb, yo, fb) && disjoint(s, sb, yo, fb)));
+  const host::Range in[2] = {{(uintptr_t)y, fb}, {(uintptr_t)present, pb}};
+  const host::Range out[3] = {{(uintptr_t)coeffs_out, fb}, {(uintptr_t)y_out, fb}, {(uintptr_t)status_out, sb}};      // y_out may be NULL: it is skipped
+  ARGCHK(host::outputs_disjoint(in, out, disjoint));
   return kzrc::recover(y, present, log_c, log_l, m, coeffs_out, y_out, status_out, stream);
 }
 }  // extern "C"

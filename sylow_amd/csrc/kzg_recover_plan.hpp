@@ -7,10 +7,14 @@
 #include "ntt_plan.hpp"
 
 namespace kzg_recover_plan {
-using ntt_plan::SAT;
-using ntt_plan::add_sat;
-using ntt_plan::mul_sat;
-using ntt_plan::elems;
+using plan_base::SAT;
+using plan_base::add_sat;
+using plan_base::disjoint;
+using plan_base::elems;
+using plan_base::mul_sat;
+using ntt_plan::root_negated;
+using ntt_plan::root_slot;
+using ntt_plan::root_words;
 constexpr int RECOVER_BLOCK = 256;                    // == BLOCK of common.hpp (kzg_recover.hip asserts it)
 constexpr int RECOVER_WAVE = 64;
 constexpr int RECOVER_WAVES = RECOVER_BLOCK / RECOVER_WAVE;
@@ -27,7 +31,6 @@ constexpr bool logs_ok(int log_c, int log_l) {
   return log_c >= 0 && log_l >= 0 && log_c <= RECOVER_LOG_C_MAX && log_l <= RECOVER_LOG_N_MAX && log_n(log_c, log_l) >= 1 &&
          log_n(log_c, log_l) <= RECOVER_LOG_N_MAX;
 }
-constexpr bool disjoint(uintptr_t a, size_t a_bytes, uintptr_t b, size_t b_bytes) { return a + a_bytes <= b || b + b_bytes <= a; }
 constexpr size_t max_missing(int log_c) { return elems(log_c) / 2; }                      // c / 2 rounded down: 0 at c = 1
 constexpr size_t grid(size_t items) { return ntt_plan::grid(items); }
 constexpr size_t blocks_of(size_t lanes) { return lanes / RECOVER_BLOCK + (lanes % RECOVER_BLOCK ? 1 : 0); }   // no sum that could wrap
@@ -40,10 +43,7 @@ constexpr size_t status_bytes(size_t m) { return m; }
 
 // ---- the constants of a call, [CONST_WORDS] u64: s as the transforms take their shift, then s^l = s^(2^log_l) (log_l squarings, one lane)
 constexpr size_t CONST_SHIFT = 0, CONST_SL = 4, CONST_WORDS = 8;
-// the roots v^e, e < c / 2, [4][c / 2]: the table of the transform of c points (ntt.hip builds it); v^(e + c / 2) = -v^e; none at c = 1
-constexpr size_t root_words(int log_c) { return ntt_plan::table_words(log_c); }
-constexpr bool root_negated(size_t i, int log_c) { return log_c >= 1 && i >= elems(log_c - 1); }
-constexpr size_t root_slot(size_t i, int log_c) { return root_negated(i, log_c) ? i - elems(log_c - 1) : i; }
+// the roots v^e, e < c / 2, [4][c / 2]: the table of the transform of c points, root_words(log_c) of ntt_plan.hpp; none at c = 1
 
 // ---- vanish: item (row, block of the row).  The row's mask is walked in rounds of VANISH_CHUNK indices: a round compacts the missing ones
 // among them into an LDS list of at most VANISH_CHUNK roots (a ballot per wave, the waves' counts through LDS), then the lanes multiply their

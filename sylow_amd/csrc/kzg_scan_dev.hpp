@@ -2,6 +2,7 @@
 // polynomial) and kzg_points.hip (several points per polynomial).  Both compile this text; the geometry is kzg_prove_plan.hpp's.  Included after
 // host.hpp.
 #pragma once
+#include "bn254_fr_dev.hpp"
 #include "kzg_prove_plan.hpp"
 
 namespace kzg_scan {
@@ -10,12 +11,6 @@ static_assert(KZG_POLY_BLOCK == BLOCK, "the quotient kernels run one chunk per b
 constexpr int L = KZG_POLY_LANE_COEFFS, CH = (int)KZG_POLY_CHUNK;
 constexpr int LOG_L = __builtin_ctz((unsigned)L), LOG_BLOCK = __builtin_ctz((unsigned)BLOCK);
 
-BN_DEV Fp fr_zero() { return fp_from_limbs(0, 0, 0, 0, 0, 0, 0, 0); }
-BN_DEV Fp lds_get(const u32 (*a)[8], int i) { return fp_from_limbs(a[i][0], a[i][1], a[i][2], a[i][3], a[i][4], a[i][5], a[i][6], a[i][7]); }
-BN_DEV void lds_put(u32 (*a)[8], int i, const Fp& v) {
-#pragma unroll
-  for (int w = 0; w < 8; ++w) a[i][w] = v.v[w];
-}
 // pw[s] = z^(2^(FROM + s)), s = 0 .. LOG_BLOCK - 1: the multipliers of a block scan whose elements are 2^FROM coefficients apart.  A chain of
 // squarings, so ONE wavefront walks it (the branch is wave-uniform) while the others load; the caller's next barrier publishes it.
 template <int FROM>

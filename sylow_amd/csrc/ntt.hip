@@ -5,6 +5,7 @@
 // transposed, so no pass needs a bit reversal of the array); and ONE element-wise kernel c s^k a_k for the coset shift and the inverse's scale.
 // Geometry, ping-pong and scratch: ntt_plan.hpp -- nothing here decides one.
 #include "host.hpp"
+#include "bn254_fr_dev.hpp"
 #include "bn254_fr_roots.hpp"
 #include "ntt_plan.hpp"
 
@@ -15,18 +16,7 @@ static_assert(NTT_BLOCK >= 128, "the table kernel's second wavefront forms the s
 constexpr int TILE = 1 << NTT_TILE_LOG, LOG_BLOCK = __builtin_ctz((unsigned)BLOCK);
 static_assert(TILE >= 2 * BLOCK, "a lane owns whole butterflies");
 
-BN_DEV Fp fr_one() { return fp_from_limbs(1, 0, 0, 0, 0, 0, 0, 0); }
-BN_DEV Fp lds_get(const u32 (*a)[8], int i) { return fp_from_limbs(a[i][0], a[i][1], a[i][2], a[i][3], a[i][4], a[i][5], a[i][6], a[i][7]); }
-BN_DEV void lds_put(u32 (*a)[8], int i, const Fp& v) {
-#pragma unroll
-  for (int w = 0; w < 8; ++w) a[i][w] = v.v[w];
-}
-struct Scalar {        // an Fr value as a kernel argument
-  u64 w[4];
-};
-BN_DEV Fp from_scalar(const Scalar& s) {
-  return fp_from_limbs((u32)s.w[0], (u32)(s.w[0] >> 32), (u32)s.w[1], (u32)(s.w[1] >> 32), (u32)s.w[2], (u32)(s.w[2] >> 32), (u32)s.w[3], (u32)(s.w[3] >> 32));
-}
+struct Scalar : FrArg {};      // a kernel names its parameter types in its symbol: this one stays a type of this namespace so that the symbol does not move
 
 // The table [4][half], half = n/2 = 2^(log_n - 1): block b holds the exponents from b * BLOCK * NTT_TABLE_LANE_ELEMS on, lane t those BLOCK
 // apart from its first.  ONE wavefront squares the 2^28-th root down to w_n and on to pw[s] = w_n^(2^s), s <= log_n - 2 (a chain; the

@@ -2,10 +2,13 @@
 // the ping-pong and the scratch, plain C++ so that tests/cpp/ntt_plan_test.cpp can compile it with g++ on a box without a GPU.  The launch
 // code asks these functions and decides nothing itself.
 #pragma once
-#include <cstddef>
-#include <cstdint>
+#include "plan_base.hpp"
 
 namespace ntt_plan {
+using plan_base::SAT;
+using plan_base::add_sat;
+using plan_base::elems;
+using plan_base::mul_sat;
 // r - 1 = 2^28 * odd: radix-2 domains up to 2^28
 constexpr int NTT_LOG_N_MAX = 28;
 constexpr int NTT_BLOCK = 256;                   // == BLOCK of common.hpp (ntt.hip asserts it)
@@ -23,13 +26,8 @@ constexpr int NTT_TABLE_LANE_ELEMS = 16;
 constexpr int NTT_SCALE_LANE_ELEMS = 16;
 constexpr size_t NTT_CONST_WORDS = 4;            // the shift as the element-wise kernel multiplies it in (g, or g^-1 for the inverse), formed on the device
 
-constexpr size_t SAT = (size_t)-1;
-constexpr size_t mul_sat(size_t a, size_t b) { return b && a > SAT / b ? SAT : a * b; }
-constexpr size_t add_sat(size_t a, size_t b) { return a > SAT - b ? SAT : a + b; }
-
 constexpr bool stages_ok(int stages) { return stages < 0 || (stages >= 1 && stages <= NTT_STAGES_MAX); }
 constexpr int stages_or_default(int stages) { return stages < 0 ? NTT_STAGES_DEFAULT : stages; }
-constexpr size_t elems(int log_n) { return (size_t)1 << log_n; }
 
 // ---- the passes: Stockham autosort, pass p a radix-2^s step from natural order to natural order --------------------------------------
 constexpr int passes(int log_n, int stages) { return (log_n + stages - 1) / stages; }
@@ -50,6 +48,10 @@ constexpr size_t table_words(int log_n) { return 4 * table_elems(log_n); }
 constexpr size_t table_blocks(int log_n) {
   return (table_elems(log_n) + (size_t)NTT_BLOCK * NTT_TABLE_LANE_ELEMS - 1) / ((size_t)NTT_BLOCK * NTT_TABLE_LANE_ELEMS);
 }
+// the powers past the table: w^i for i < n is w^(i - n / 2) negated from n / 2 on, and 1 at n = 1, where there is no table
+constexpr size_t root_words(int log_n) { return table_words(log_n); }
+constexpr bool root_negated(size_t i, int log_n) { return log_n >= 1 && i >= elems(log_n - 1); }
+constexpr size_t root_slot(size_t i, int log_n) { return root_negated(i, log_n) ? i - elems(log_n - 1) : i; }
 // squarings from the 2^28-th root W down to w_n
 constexpr int root_squarings(int log_n) { return NTT_LOG_N_MAX - log_n; }
 

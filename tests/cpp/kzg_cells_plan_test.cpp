@@ -24,7 +24,7 @@ static void limits() {
   EXPECT(logs_ok(0, 0) && logs_ok(7, 6) && logs_ok(27, 0) && logs_ok(0, 27) && logs_ok(13, 14), "the legal corners");
   EXPECT(!logs_ok(28, 0) && !logs_ok(0, 28) && !logs_ok(14, 14) && !logs_ok(-1, 3) && !logs_ok(3, -1) && !logs_ok(INT32_MAX, 1) && !logs_ok(1, INT32_MAX), "the illegal ones");
   EXPECT(max_blocks_ok(-1) && max_blocks_ok(1) && !max_blocks_ok(0), "a cap of no block is refused");
-  EXPECT(disjoint(0, 8, 8, 8) && !disjoint(0, 9, 8, 8) && !disjoint(4, 1, 0, 8) && disjoint(4, 0, 0, 8), "byte ranges; an empty range overlaps nothing");
+  EXPECT(disjoint_or_empty(0, 8, 8, 8) && !disjoint_or_empty(0, 9, 8, 8) && !disjoint_or_empty(4, 1, 0, 8) && disjoint_or_empty(4, 0, 0, 8), "byte ranges; an empty range overlaps nothing");
   EXPECT(grid(0, -1) == 1 && grid(5, -1) == 5 && grid(5, 2) == 2 && grid(TOP, -1) == CELLS_GRID_CAP && grid(TOP, 1) == 1 && grid(3, INT64_MAX) == 3, "grids");
   EXPECT(blocks_of(0) == 0 && blocks_of(1) == 1 && blocks_of(256) == 1 && blocks_of(257) == 2 && blocks_of(TOP) == TOP / 256 + 1, "blocks of lanes, no wrap");
   EXPECT(vals_bytes(6, 8192) == (size_t)8192 * 64 * 32 && vals_bytes(27, TOP) == SAT && point_bytes(3) == 192 && scalar_bytes(TOP) == SAT && index_bytes(TOP) == SAT, "bytes");
