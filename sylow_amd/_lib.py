@@ -239,6 +239,19 @@ SIGNATURES_KZG_CELLS = {
                                             c_u8p, c_vp],
 }
 
+# the entry points of include/sylow_hip_fr_scan.h (scans over Fr under + and *, the scan of a ratio, PLONK's permutation grand product): a
+# sixth table, bound by the same load()
+SIGNATURES_FR_SCAN = {
+    "sylow_hip_fr_scan_batch": [c_u64p, c_sz, c_sz, c_i32, c_i32, c_u64p, c_u64p, c_vp],
+    "sylow_hip_fr_scan_batch_tuned": [c_u64p, c_sz, c_sz, c_i32, c_i32, ctypes.c_int64, c_i32, c_u64p, c_u64p, c_vp],
+    "sylow_hip_fr_ratio_scan_batch": [c_u64p, c_u64p, c_sz, c_sz, c_i32, c_u64p, c_u64p, c_u8p, c_vp],
+    "sylow_hip_fr_ratio_scan_batch_tuned": [c_u64p, c_u64p, c_sz, c_sz, c_i32, ctypes.c_int64, c_i32, c_u64p, c_u64p, c_u8p, c_vp],
+    "sylow_hip_plonk_identity_batch": [c_u64p, c_i32, c_i32, c_u64p, c_vp],
+    "sylow_hip_plonk_permutation_batch": [c_u64p, c_u64p, c_u64p, c_u64p, c_u64p, c_i32, c_i32, c_sz, c_u64p, c_u64p, c_u8p, c_vp],
+    "sylow_hip_plonk_permutation_batch_tuned": [c_u64p, c_u64p, c_u64p, c_u64p, c_u64p, c_i32, c_i32, c_sz, ctypes.c_int64, c_i32, c_u64p, c_u64p, c_u8p,
+                                                c_vp],
+}
+
 # SYLOW_HIP_OPT_* of include/sylow_hip.h.  The LIBRARY reads no environment variable; this host layer does, once, when it loads the library:
 # SYLOW_HIP_<NAME>=<integer> becomes sylow_hip_set_option(<NAME>, value) -- what tests/test_gpu_routes.py and the A/B scripts under tools/ set
 OPTIONS = {"STAGGER": 0, "MULTI_TABLES": 1, "WIDE_TAIL": 2, "WIDE_PACK": 3, "AGG_FORK": 4, "SIGN_WIDE_MAX": 5, "WIDE_MAX": 6, "WIDE_VERIFY_MAX": 7,
@@ -291,7 +304,7 @@ def load():
         _preload_torch_hip_runtime()
         lib = ctypes.CDLL(LIB_PATH)
         for name, argtypes in list(SIGNATURES.items()) + list(SIGNATURES_KZG_POINTS.items()) + list(SIGNATURES_KZG_COSETS.items()) + \
-                list(SIGNATURES_KZG_RECOVER.items()) + list(SIGNATURES_KZG_CELLS.items()):
+                list(SIGNATURES_KZG_RECOVER.items()) + list(SIGNATURES_KZG_CELLS.items()) + list(SIGNATURES_FR_SCAN.items()):
             fn = getattr(lib, name)  # AttributeError if the symbol is missing
             fn.argtypes = argtypes
             fn.restype = _RESTYPE.get(name, c_i32)

@@ -14,6 +14,7 @@ HEADER_KZG_POINTS = os.path.join(os.path.dirname(_HERE), "include", "sylow_hip_k
 HEADER_KZG_COSETS = os.path.join(os.path.dirname(_HERE), "include", "sylow_hip_kzg_cosets.h")
 HEADER_KZG_RECOVER = os.path.join(os.path.dirname(_HERE), "include", "sylow_hip_kzg_recover.h")
 HEADER_KZG_CELLS = os.path.join(os.path.dirname(_HERE), "include", "sylow_hip_kzg_cells.h")
+HEADER_FR_SCAN = os.path.join(os.path.dirname(_HERE), "include", "sylow_hip_fr_scan.h")
 ITEMSIZE = {"u64": 8, "i64": 8, "u8": 1, "i32": 4, "void": 1}
 _EXPR_OK = re.compile(r"^[\w\s+*()]+$")
 
@@ -63,7 +64,7 @@ def table():
     if _TABLE is None:
         try:
             _TABLE = {**parse(), **parse(HEADER_KZG_POINTS), **parse(HEADER_KZG_COSETS), **parse(HEADER_KZG_RECOVER),
-                      **parse(HEADER_KZG_CELLS)}
+                      **parse(HEADER_KZG_CELLS), **parse(HEADER_FR_SCAN)}
         except OSError:            # the package deployed without the repo's include/ directory: no table, nothing to check
             _TABLE = {}
     return _TABLE

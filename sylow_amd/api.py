@@ -350,6 +350,9 @@ class Fr:
     def inv(self): return Fr(engine().fr_inv(self.v))
     def batch_inv(self): return Fr(engine().fr_batch_inv(self.v))   # the words of inv() (inv(0) = 0), one shared inversion per 2048 elements
     def __eq__(self, o): return (self.v == o.v).all(axis=1)
+    # running sums / products of the batch taken as ONE row (sylow_hip_fr_scan_batch); exclusive: element k holds the elements before k
+    def cumsum(self, exclusive=False): return Fr(engine().fr_scan(self.v, 0, exclusive)[0]) if len(self) else Fr(self.v)
+    def cumprod(self, exclusive=False): return Fr(engine().fr_scan(self.v, 1, exclusive)[0]) if len(self) else Fr(self.v)
 
     @classmethod
     def from_be_bytes(cls, blobs):                 # Fr::from_be_bytes (fp.rs:746-778): none for v >= r
@@ -1004,6 +1007,49 @@ class KzgEvalProver:
         y, pi_xy, pi_inf = engine().kzg_open_multi_evals(self.srs_lagrange.xy, a, group_offsets(groups, a.shape[0]), KzgVerifier._words(z),
                                                          KzgVerifier._words(gamma))
         return y, G1Affine(pi_xy, pi_inf)
+
+
+class PlonkPermutation:
+    """The copy-constraint argument of a PLONK-style prover over the domain <w_n> of n = 2^log_n points (the domain of ntt): W wire columns, the
+    identity columns shifts[j] w_n^i and the permutation columns sigma [W, n, 4], which hold the identity values permuted along the copy cycles.
+    `shifts`: W coset representatives as [W, 4] words or Python ints (k_j with the cosets k_j <w_n> disjoint, e.g. 1, 5, 7, ...).
+    THE LIBRARY DRAWS NO CHALLENGE: beta and gamma are the caller's, drawn AFTER the wire commitments are fixed."""
+
+    def __init__(self, log_n: int, shifts, sigma):
+        self.log_n, self.shifts = int(log_n), _words(shifts)
+        self.sigma = np.ascontiguousarray(sigma, dtype=np.uint64)
+        W = self.shifts.shape[0]
+        if not 0 <= self.log_n <= 28 or not 1 <= W <= 32 or self.sigma.shape != (W, 1 << self.log_n, 4):
+            raise ValueError("PlonkPermutation: log_n in 0 .. 28, 1 .. 32 columns, sigma [W, n, 4]")
+
+    @classmethod
+    def from_mapping(cls, log_n: int, shifts, mapping):
+        """sigma from a permutation of the W n positions, position j n + i being row i of column j: sigma at position p is the identity value
+        of position mapping[p].  The identity columns come from the device (sylow_hip_plonk_identity_batch); the gather runs on the host."""
+        sh = _words(shifts)
+        n, W = 1 << int(log_n), sh.shape[0]
+        mp = np.ascontiguousarray(mapping, dtype=np.int64).reshape(-1)
+        if mp.shape[0] != W * n or not np.array_equal(np.sort(mp), np.arange(W * n)):
+            raise ValueError("PlonkPermutation.from_mapping: mapping is a permutation of the W n positions")
+        ident = engine().plonk_identity(sh, int(log_n)).reshape(W * n, 4)
+        return cls(log_n, sh, ident[mp].reshape(W, n, 4))
+
+    def grand_product(self, wires, beta, gamma):
+        """(z [m, n, 4] canonical words, status [m]) for wires [m, W, n, 4] (or [W, n, 4]: one instance) and one (beta, gamma) per instance
+        (sylow_hip_plonk_permutation_batch): z[j, 0] = 1 and z[j, i + 1] = z[j, i] num_i / den_i; status 0 = the copy constraints hold, bit 0 =
+        a zero denominator, bit 1 = z does not close to 1.  z is the argument KzgProver.commit_evals takes."""
+        w = np.ascontiguousarray(wires, dtype=np.uint64)
+        w = w[None] if w.ndim == 3 else w
+        z, _, status = engine().plonk_permutation(w, self.sigma, self.shifts, _words(beta), _words(gamma))
+        return z, status
+
+
+def _words(v):
+    """[k, 4] words from words or from Python ints"""
+    a = np.asarray(v)
+    if a.dtype == np.uint64 and a.ndim >= 1 and a.shape[-1] == 4:
+        return np.ascontiguousarray(a).reshape(-1, 4)
+    return fp([int(x) for x in np.asarray(v, dtype=object).reshape(-1)])
 
 
 def _fr_arrays(values):

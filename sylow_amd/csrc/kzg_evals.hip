@@ -6,8 +6,7 @@
 //   sylow_hip_kzg_open_evals_batch       that quotient into scratch, then the commitment of kzg_prove.hip over a Lagrange-basis SRS.
 // Geometry and scratch: kzg_evals_plan.hpp -- nothing here decides one.
 #include "host.hpp"
-#include "bn254_fr_euclid.hpp"
-#include "bn254_fr_dev.hpp"
+#include "bn254_fr_block.hpp"
 #include "bn254_fr_roots.hpp"
 #include "kzg_evals_plan.hpp"
 #include "ntt_plan.hpp"
@@ -19,50 +18,7 @@ static_assert(EVALS_LOG_N_MAX == ntt_plan::NTT_LOG_N_MAX, "the domains of the tr
 constexpr int L = EVALS_LANE_ELEMS, CH = (int)EVALS_CHUNK, W_INV = EVALS_LOG_N_MAX;      // W_INV: the slot of w^-1
 
 struct Scalar : FrArg {};      // a kernel names its parameter types in its symbol: this one stays a type of this namespace so that the symbol does not move
-// element k of an Fr SoA array of stride n, mod r
-BN_DEV Fp elem(const u64* a, size_t n, size_t k) { return fr_reduce_plain(load_plain(a, n, k, 0)); }
-// the inverse of ONE nonzero canonical value, for a lone lane: binary extended Euclid, no product (bn254_fr_euclid.hpp)
-BN_NOINLINE Fp fr_inv_lone(Fp a) {
-  Fp o;
-  fr_euclid::inverse(a.v, o.v);
-  return o;
-}
-
-// Every thread of the block calls it.  Lane t < live brings T_t != 0, the product of its elements; it gets T_t^-1.  Two scans run side by
-// side through LDS -- step s multiplies the prefix by the one 2^s lanes below and the suffix by the one 2^s lanes above -- so that pre[t] =
-// T_0 .. T_t and suf[t] = T_t .. T_(live-1); the top live lane holds the chunk's product and inverts it alone; then
-// T_t^-1 = (T_0 .. T_(live-1))^-1 pre[t - 1] suf[t + 1].  Lanes from `live` on hold nothing and are never read.  The caller's next barrier
-// frees pre, suf and inv.
-BN_DEV Fp block_inverses(const Fp& T, u32 (*pre)[8], u32 (*suf)[8], u32 (*inv)[8], int live) {
-  const int t = threadIdx.x;
-  const bool on = t < live;
-  Fp P = T, S = T;
-  if (on) {
-    lds_put(pre, t, P);
-    lds_put(suf, t, S);
-  }
-  __syncthreads();
-#pragma unroll 1
-  for (int s = 0; s < scan_steps(live); ++s) {
-    const int off = 1 << s;
-    const bool lo = on && t >= off, hi = on && t + off < live;
-    if (lo) P = fr_mul(P, lds_get(pre, t - off));
-    if (hi) S = fr_mul(S, lds_get(suf, t + off));
-    __syncthreads();
-    if (lo) lds_put(pre, t, P);
-    if (hi) lds_put(suf, t, S);
-    __syncthreads();
-  }
-  if (t == live - 1) lds_put(inv, 0, fr_inv_lone(P));
-  __syncthreads();
-  Fp r = fr_one();
-  if (on) {
-    r = lds_get(inv, 0);
-    if (t > 0) r = fr_mul(r, lds_get(pre, t - 1));
-    if (t + 1 < live) r = fr_mul(r, lds_get(suf, t + 1));
-  }
-  return r;
-}
+// elem, fr_inv_lone and block_inverses -- the chunk's ONE inversion -- are bn254_fr_block.hpp's: fr_scan.hip runs the same
 // Every thread of the block calls it: lane 0 gets the sum of the block's values (the other lanes partial sums).  Ends on a barrier.
 BN_DEV Fp block_sum(Fp v, u32 (*part)[8]) {
   const int t = threadIdx.x;

@@ -1542,6 +1542,82 @@ class Engine:
                    self._ptr(dp), self._ptr(dpf), self._ptr(dw), log_c, log_l, rows, n_com, dgt.ptr, dis.ptr, dg.ptr)
         return self.from_device_soa(dgt), bool(dis.download()[0]), bool(dg.download()[0])
 
+    # ---- scans over Fr and PLONK's permutation grand product (include/sylow_hip_fr_scan.h).  Rows are [m, len, 4] on the host (or [len, 4]:
+    # one row) and [m][4][len] on the device; any 256-bit words, taken mod r; op 0 = sum, 1 = product ----
+    def _fr_rows(self, a):
+        a = np.ascontiguousarray(a, dtype=np.uint64)
+        one = a.ndim == 2
+        return one, self._kzg_polys(a[None] if one else a)
+
+    def _fr_rows_down(self, d, m, one):
+        out = np.ascontiguousarray(d.download()[:m].transpose(0, 2, 1))
+        return out[0] if one else out
+
+    def _fr_totals_down(self, d, m, one):
+        t = self.from_device_soa(d)[:m]
+        return t[0] if one else t
+
+    def fr_scan(self, a, op, exclusive=False, max_blocks=-1, totals_tile=-1):
+        """out[j, k] = a[j, 0] o .. o a[j, k] (exclusive: up to k - 1, the identity at k = 0) and the rows' totals [m, 4]
+        (sylow_hip_fr_scan_batch).  max_blocks >= 1 caps the blocks of a launch and totals_tile in 1 .. 256 pins the chunk totals the second
+        level scans per step (sylow_hip_fr_scan_batch_tuned); the words depend on neither."""
+        one, a = self._fr_rows(a)
+        m, ln = a.shape[0], a.shape[1]
+        da, do, dt = self._kzg_polys_up(a), self.empty((max(m, 1), 4, ln)), self.empty((4, max(m, 1)))
+        if max_blocks < 0 and totals_tile < 0:
+            self._call("sylow_hip_fr_scan_batch", self._ptr(da), ln, m, int(op), int(bool(exclusive)), do.ptr, dt.ptr)
+        else:
+            self._call("sylow_hip_fr_scan_batch_tuned", self._ptr(da), ln, m, int(op), int(bool(exclusive)), int(max_blocks), int(totals_tile), do.ptr, dt.ptr)
+        return self._fr_rows_down(do, m, one), self._fr_totals_down(dt, m, one)
+
+    def fr_ratio_scan(self, num, den, op, max_blocks=-1, totals_tile=-1):
+        """The exclusive scan of t = num / den, inv(0) = 0 (sylow_hip_fr_ratio_scan_batch): (out [m, len, 4] with out[j, 0] the identity and
+        out[j, k] = t[j, 0] o .. o t[j, k - 1], the totals t[j, 0] o .. o t[j, len - 1] as [m, 4], status [m]: bit 0 = a denominator of the row
+        is 0 mod r).  num None: all ones.  The denominators of a chunk share one inversion and no inverse or ratio reaches memory."""
+        one, d = self._fr_rows(den)
+        m, ln = d.shape[0], d.shape[1]
+        dn = None
+        if num is not None:
+            _, nm = self._fr_rows(num)
+            assert nm.shape == d.shape, (nm.shape, d.shape)
+            dn = self._kzg_polys_up(nm)
+        dd, do, dt, ds = self._kzg_polys_up(d), self.empty((max(m, 1), 4, ln)), self.empty((4, max(m, 1))), self.empty((max(m, 1),), np.uint8)
+        if max_blocks < 0 and totals_tile < 0:
+            self._call("sylow_hip_fr_ratio_scan_batch", self._ptr(dn), self._ptr(dd), ln, m, int(op), do.ptr, dt.ptr, ds.ptr)
+        else:
+            self._call("sylow_hip_fr_ratio_scan_batch_tuned", self._ptr(dn), self._ptr(dd), ln, m, int(op), int(max_blocks), int(totals_tile), do.ptr, dt.ptr, ds.ptr)
+        st = ds.download()[:m]
+        return self._fr_rows_down(do, m, one), self._fr_totals_down(dt, m, one), (st[0] if one else st)
+
+    def plonk_identity(self, shifts, log_n):
+        """The identity columns of the permutation argument, out[j, i] = shifts[j] w_n^i as [W, n, 4] (sylow_hip_plonk_identity_batch)."""
+        sh = _aos(shifts, 4)
+        W = sh.shape[0]
+        ds, do = self.to_device_soa(sh, 4), self.empty((W, 4, 1 << log_n))
+        self._call("sylow_hip_plonk_identity_batch", ds.ptr, int(log_n), W, do.ptr)
+        return np.ascontiguousarray(do.download().transpose(0, 2, 1))
+
+    def plonk_permutation(self, wires, sigma, shifts, beta, gamma, max_blocks=-1, totals_tile=-1):
+        """z of the copy-constraint argument for m instances over one permutation (sylow_hip_plonk_permutation_batch): wires [m, W, n, 4],
+        sigma [W, n, 4], shifts [W, 4], beta and gamma [m, 4] DRAWN AFTER THE WIRE COMMITMENTS ARE FIXED -> (z [m, n, 4] with z[j, 0] = 1,
+        z_n [m, 4], status [m]: bit 0 = a zero denominator, bit 1 = z_n != 1, 0 = the copy constraints hold)."""
+        w, sg, sh = np.ascontiguousarray(wires, dtype=np.uint64), np.ascontiguousarray(sigma, dtype=np.uint64), _aos(shifts, 4)
+        beta, gamma = _aos(beta, 4), _aos(gamma, 4)
+        assert w.ndim == 4 and w.shape[3] == 4 and sg.ndim == 3, (w.shape, sg.shape)
+        m, W, n = w.shape[0], w.shape[1], w.shape[2]
+        log_n = n.bit_length() - 1
+        assert n == 1 << log_n and sg.shape == (W, n, 4) and sh.shape[0] == W and beta.shape[0] == m and gamma.shape[0] == m, (w.shape, sg.shape, sh.shape)
+        dw = self.to_device(np.ascontiguousarray(w.transpose(0, 1, 3, 2))) if m else None
+        dsg, dsh = self.to_device(np.ascontiguousarray(sg.transpose(0, 2, 1))), self.to_device_soa(sh, 4)
+        db, dg = (self.to_device_soa(beta, 4), self.to_device_soa(gamma, 4)) if m else (None, None)
+        dz, dt, ds = self.empty((max(m, 1), 4, n)), self.empty((4, max(m, 1))), self.empty((max(m, 1),), np.uint8)
+        ins = [self._ptr(dw), dsg.ptr, dsh.ptr, self._ptr(db), self._ptr(dg), log_n, W, m]
+        if max_blocks < 0 and totals_tile < 0:
+            self._call("sylow_hip_plonk_permutation_batch", *ins, dz.ptr, dt.ptr, ds.ptr)
+        else:
+            self._call("sylow_hip_plonk_permutation_batch_tuned", *ins, int(max_blocks), int(totals_tile), dz.ptr, dt.ptr, ds.ptr)
+        return np.ascontiguousarray(dz.download()[:m].transpose(0, 2, 1)), self.from_device_soa(dt)[:m], ds.download()[:m]
+
     # ---- Groth16, the prover's side.  A sparse matrix is CSR: (row_ptr [rows + 1], col [nnz], val [nnz, 4]); Fr batches are [m, n, 4] on the
     # host and [m][4][n] on the device; any 256-bit words, taken mod r ----
     def _csr_up(self, csr):
