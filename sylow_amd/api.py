@@ -1044,6 +1044,51 @@ class PlonkPermutation:
         return z, status
 
 
+class PlonkQuotient:
+    """The quotient polynomial of a PLONK-style prover for ONE circuit over the domain <w_n>, n = 2^log_n, formed on the coset 5 <w_N> of
+    N = 2^log_e n points: t = [gate + alpha perm + alpha^2 L_1 (z - 1)] / (X^n - 1) with gate = q_M w_0 w_1 + sum_j q_j w_j + q_C + PI and perm
+    the two products of the copy-constraint argument (include/sylow_plonk.h).  `shifts` and `sigma` are PlonkPermutation's; `selectors` holds
+    the values on <w_n> of q_0 .. q_(W-1), q_M, q_C as [W + 2, n, 4] words or W + 2 lists of Python ints.  The circuit's table is built once,
+    here, and stays on the device.  THE LIBRARY DRAWS NO CHALLENGE: beta and gamma are drawn AFTER the wire commitments are fixed, alpha AFTER
+    the commitment to z is fixed."""
+
+    def __init__(self, log_n: int, shifts, sigma, selectors, log_e: int = 2):
+        perm = PlonkPermutation(log_n, shifts, sigma)                  # its validation of log_n, the shifts and sigma
+        self.log_n, self.log_e, self.shifts, self.sigma = perm.log_n, int(log_e), perm.shifts, perm.sigma
+        self.W = self.shifts.shape[0]
+        sel = _fr_nd(selectors, 2)
+        if self.W < 2 or self.log_e < 0 or self.log_n + self.log_e > 28 or sel.shape != (self.W + 2, 1 << self.log_n, 4):
+            raise ValueError("PlonkQuotient: 2 .. 32 columns, log_n + log_e <= 28, selectors [W + 2, n, 4]")
+        self.table = engine().plonk_quotient_prepare(sel, self.sigma, self.log_e)
+
+    def quotient(self, wires, z, beta, gamma, alpha, pi=None):
+        """(t [m, N, 4] canonical words, status [m]) for the COEFFICIENTS of the wires [m, W, len_w, 4] (or [W, len_w, 4]: one instance), of
+        z [m, len_z, 4] and of the public-input polynomial pi [m, n, 4] (or None), as words or as nested lists of Python ints, and one
+        (beta, gamma, alpha) per instance (sylow_plonk_quotient_batch).  len_w and len_z are free in 1 .. N: blinded polynomials are longer
+        than n.  status 0 = no coefficient of t above its degree bound; bit 0 = X^n - 1 does not divide, the constraints do not hold."""
+        w = _fr_nd(wires, 3, 2)
+        w = w[None] if w.ndim == 3 else w
+        zc = _fr_nd(z, 2, 1)
+        zc = zc[None] if zc.ndim == 2 else zc
+        pc = None
+        if pi is not None:
+            pc = _fr_nd(pi, 2, 1)
+            pc = pc[None] if pc.ndim == 2 else pc
+        return engine().plonk_quotient(self.table, w, zc, pc, self.shifts, _words(beta), _words(gamma), _words(alpha), self.log_n, self.log_e)
+
+
+def _fr_nd(values, *ndims):
+    """words [..., 4] from a uint64 array of words or from nested lists of Python ints with one of the given numbers of dimensions"""
+    if isinstance(values, np.ndarray) and values.dtype == np.uint64:
+        if values.ndim - 1 not in ndims or values.shape[-1] != 4:
+            raise ValueError(f"words as a uint64 array [..., 4] over {' or '.join(map(str, ndims))} dimensions, not {values.shape}")
+        return np.ascontiguousarray(values)
+    a = np.asarray(values, dtype=object)
+    if a.ndim not in ndims:
+        raise ValueError(f"Python ints nested {' or '.join(map(str, ndims))} deep, not {a.ndim}")
+    return fp(list(a.reshape(-1))).reshape(a.shape + (4,))
+
+
 def _words(v):
     """[k, 4] words from words or from Python ints"""
     a = np.asarray(v)

@@ -1618,6 +1618,88 @@ class Engine:
             self._call("sylow_hip_plonk_permutation_batch_tuned", *ins, int(max_blocks), int(totals_tile), dz.ptr, dt.ptr, ds.ptr)
         return np.ascontiguousarray(dz.download()[:m].transpose(0, 2, 1)), self.from_device_soa(dt)[:m], ds.download()[:m]
 
+    # ---- PLONK's quotient polynomial (include/sylow_plonk.h).  n = 2^log_n, N = 2^(log_n + log_e); the table of a circuit stays on the device:
+    # [2 W + 3][4][N] then [4][E] as one flat array of words ----
+    def plonk_quotient_prepare(self, selectors, sigma, log_e=2):
+        """The table of one circuit (sylow_plonk_quotient_prepare): selectors [W + 2, n, 4] -- the values on <w_n> of q_0 .. q_(W-1), q_M,
+        q_C -- and sigma [W, n, 4] as for plonk_permutation -> a DeviceArray of 4 N (2 W + 3) + 4 E words: the rows on the coset
+        K = 5 <w_N>, then (X^n - 1)^-1 there."""
+        sel, sg = np.ascontiguousarray(selectors, dtype=np.uint64), np.ascontiguousarray(sigma, dtype=np.uint64)
+        assert sel.ndim == 3 and sg.ndim == 3 and sel.shape[2] == 4, (sel.shape, sg.shape)
+        W, n = sg.shape[0], sg.shape[1]
+        log_n = n.bit_length() - 1
+        assert n == 1 << log_n and sel.shape == (W + 2, n, 4) and sg.shape == (W, n, 4), (sel.shape, sg.shape)
+        dsel, dsg = self.to_device(np.ascontiguousarray(sel.transpose(0, 2, 1))), self.to_device(np.ascontiguousarray(sg.transpose(0, 2, 1)))
+        table = self.empty((4 * (n << log_e) * (2 * W + 3) + 4 * (1 << log_e),))
+        self._call("sylow_plonk_quotient_prepare", dsel.ptr, dsg.ptr, log_n, int(log_e), W, table.ptr)
+        return table
+
+    def plonk_quotient_table_up(self, rows, zinv):
+        """a table from host words: rows [2 W + 3, N, 4] and zinv [E, 4] -> the DeviceArray plonk_quotient_prepare would return for them"""
+        rows, zinv = np.ascontiguousarray(rows, dtype=np.uint64), _aos(zinv, 4)
+        return self.to_device(np.concatenate([rows.transpose(0, 2, 1).reshape(-1), zinv.T.reshape(-1)]))
+
+    def plonk_quotient_table_down(self, table, W, log_n, log_e):
+        """(rows [2 W + 3, N, 4], zinv [E, 4]) of a table on the device"""
+        flat, big, E = table.download().reshape(-1), 1 << (log_n + log_e), 1 << log_e
+        rows = flat[:4 * big * (2 * W + 3)].reshape(2 * W + 3, 4, big).transpose(0, 2, 1)
+        return np.ascontiguousarray(rows), np.ascontiguousarray(flat[4 * big * (2 * W + 3):].reshape(4, E).T)
+
+    def _plonk_challenges_up(self, m, *scalars):
+        out = []
+        for v in scalars:
+            v = _aos(v, 4)
+            assert v.shape[0] == m, (v.shape, m)
+            out.append(self.to_device_soa(v, 4) if m else None)
+        return out
+
+    def plonk_quotient_evals(self, table, wires_ext, z_ext, pi_ext, shifts, beta, gamma, alpha, log_n, log_e=2, max_blocks=-1):
+        """The fused kernel alone (sylow_plonk_quotient_evals_batch): the values on K of the wires [m, W, N, 4], of z [m, N, 4] and of the
+        public inputs ([m, N, 4] or None), shifts [W, 4], one (beta, gamma, alpha) per instance as [m, 4], THE CALLER'S -> t_ext [m, N, 4],
+        (gate + alpha perm + alpha^2 boundary) / (X^n - 1) point by point.  max_blocks >= 1 caps the blocks of the launch; the words do
+        not depend on it."""
+        w, z, sh = np.ascontiguousarray(wires_ext, dtype=np.uint64), np.ascontiguousarray(z_ext, dtype=np.uint64), _aos(shifts, 4)
+        assert w.ndim == 4 and w.shape[3] == 4 and z.ndim == 3, (w.shape, z.shape)
+        m, W, big = w.shape[0], w.shape[1], 1 << (log_n + log_e)
+        assert w.shape == (m, W, big, 4) and z.shape == (m, big, 4) and sh.shape[0] == W, (w.shape, z.shape, sh.shape)
+        dw = self.to_device(np.ascontiguousarray(w.transpose(0, 1, 3, 2))) if m else None
+        dz, dpi = self._kzg_polys_up(z), None
+        if pi_ext is not None:
+            p = np.ascontiguousarray(pi_ext, dtype=np.uint64)
+            assert p.shape == z.shape, (p.shape, z.shape)
+            dpi = self._kzg_polys_up(p)
+        db, dg, da = self._plonk_challenges_up(m, beta, gamma, alpha)
+        dsh, dt = self.to_device_soa(sh, 4), self.empty((max(m, 1), 4, big))
+        ins = [table.ptr, self._ptr(dw), self._ptr(dz), self._ptr(dpi), dsh.ptr, self._ptr(db), self._ptr(dg), self._ptr(da), int(log_n), int(log_e), W, m]
+        if max_blocks < 0:
+            self._call("sylow_plonk_quotient_evals_batch", *ins, dt.ptr)
+        else:
+            self._call("sylow_plonk_quotient_evals_batch_tuned", *ins, int(max_blocks), dt.ptr)
+        return np.ascontiguousarray(dt.download()[:m].transpose(0, 2, 1))
+
+    def plonk_quotient(self, table, wires, z, pi, shifts, beta, gamma, alpha, log_n, log_e=2, max_blocks=-1):
+        """t from COEFFICIENTS (sylow_plonk_quotient_batch): wires [m, W, len_w, 4], z [m, len_z, 4], pi [m, n, 4] or None, the lengths free
+        in 1 .. N (blinded polynomials are longer than n) -> (t [m, N, 4], the coefficients of the polynomial of degree < N that equals the
+        numerator over X^n - 1 on K, status [m]: bit 0 = a coefficient above the degree bound is not 0, the constraints do not hold)."""
+        w, z, sh = np.ascontiguousarray(wires, dtype=np.uint64), np.ascontiguousarray(z, dtype=np.uint64), _aos(shifts, 4)
+        assert w.ndim == 4 and w.shape[3] == 4 and z.ndim == 3 and z.shape[2] == 4, (w.shape, z.shape)
+        m, W, len_w, len_z, n, big = w.shape[0], w.shape[1], w.shape[2], z.shape[1], 1 << log_n, 1 << (log_n + log_e)
+        assert z.shape[0] == m and sh.shape[0] == W, (w.shape, z.shape, sh.shape)
+        dw = self.to_device(np.ascontiguousarray(w.transpose(0, 1, 3, 2))) if m else None
+        dz, dpi = self._kzg_polys_up(z), None
+        if pi is not None:
+            p = np.ascontiguousarray(pi, dtype=np.uint64)
+            assert p.shape == (m, n, 4), p.shape
+            dpi = self._kzg_polys_up(p)
+        db, dg, da = self._plonk_challenges_up(m, beta, gamma, alpha)
+        dsh, dt, ds = self.to_device_soa(sh, 4), self.empty((max(m, 1), 4, big)), self.empty((max(m, 1),), np.uint8)
+        ins = [table.ptr, self._ptr(dw), len_w, self._ptr(dz), len_z, self._ptr(dpi), dsh.ptr, self._ptr(db), self._ptr(dg), self._ptr(da), int(log_n), int(log_e), W, m]
+        if max_blocks < 0:
+            self._call("sylow_plonk_quotient_batch", *ins, dt.ptr, ds.ptr)
+        else:
+            self._call("sylow_plonk_quotient_batch_tuned", *ins, int(max_blocks), dt.ptr, ds.ptr)
+        return np.ascontiguousarray(dt.download()[:m].transpose(0, 2, 1)), ds.download()[:m]
+
     # ---- Groth16, the prover's side.  A sparse matrix is CSR: (row_ptr [rows + 1], col [nnz], val [nnz, 4]); Fr batches are [m, n, 4] on the
     # host and [m][4][n] on the device; any 256-bit words, taken mod r ----
     def _csr_up(self, csr):
