@@ -8,7 +8,7 @@
  * WHY A HEADER AND A PREFIX OF ITS OWN.  The set of sylow_hip_* symbols is closed: the tests pin every exported sylow_hip_* name to one of
  * the six binding tables, those tables to their headers, and every prototype of sylow_hip.h to a row of the memory contract.  The prover
  * surface will grow (the quotient now, linearisation helpers later), so it gets the prefix sylow_plonk_ and this header, a seventh binding
- * table, and NO sylow_hip_* symbol is added.
+ * table, and NO sylow_hip_* symbol is added.  The closing rounds -- evaluations, linearisation, the two openings -- are in sylow_popen.h.
  *
  * With n = 2^log_n, E = 2^log_e, N = E n (log_n + log_e <= 28), w_N the root of sylow_hip_fr_ntt_batch for N points and w_n = w_N^E, the
  * coset K = 5 <w_N> (5: the shift of sylow_hip_groth16_quotient_batch; X^n - 1 never vanishes on K), x_i = 5 w_N^i, W wire columns w_j

@@ -263,6 +263,20 @@ SIGNATURES_PLONK = {
     "sylow_plonk_quotient_batch_tuned": [c_u64p, c_u64p, c_sz, c_u64p, c_sz] + [c_u64p] * 5 + [c_i32, c_i32, c_i32, c_sz, ctypes.c_int64, c_u64p, c_u8p, c_vp],
 }
 
+# the entry points of include/sylow_popen.h (PLONK's closing rounds: evaluations, linearisation, the two openings): an eighth table, bound by
+# the same load().  Their prefix is sylow_popen_: the sets of sylow_hip_* and of sylow_plonk_* symbols are closed (the header says why)
+_PO_EVAL = [c_u64p, c_u64p, c_sz, c_u64p, c_sz, c_u64p, c_u64p, c_i32, c_i32, c_sz]
+_PO_LIN = [c_u64p, c_u64p, c_sz, c_u64p, c_sz] + [c_u64p] * 8 + [c_i32, c_i32, c_i32, c_sz, c_sz]
+SIGNATURES_POPEN = {
+    "sylow_popen_prepare": [c_u64p, c_u64p, c_i32, c_i32, c_u64p, c_vp],
+    "sylow_popen_evaluate_batch": _PO_EVAL + [c_u64p, c_vp],
+    "sylow_popen_evaluate_batch_tuned": _PO_EVAL + [ctypes.c_int64, c_u64p, c_vp],
+    "sylow_popen_linearise_batch": _PO_LIN + [c_u64p, c_u64p, c_u8p, c_vp],
+    "sylow_popen_linearise_batch_tuned": _PO_LIN + [ctypes.c_int64, c_u64p, c_u64p, c_u8p, c_vp],
+    "sylow_popen_open_batch": [c_u64p, c_u64p, c_u64p, c_sz, c_u64p, c_sz] + [c_u64p] * 8 + [c_i32, c_i32, c_i32, c_sz, c_sz, c_u64p, c_u64p, c_u8p, c_u64p, c_u8p,
+                               c_u8p, c_vp],
+}
+
 # SYLOW_HIP_OPT_* of include/sylow_hip.h.  The LIBRARY reads no environment variable; this host layer does, once, when it loads the library:
 # SYLOW_HIP_<NAME>=<integer> becomes sylow_hip_set_option(<NAME>, value) -- what tests/test_gpu_routes.py and the A/B scripts under tools/ set
 OPTIONS = {"STAGGER": 0, "MULTI_TABLES": 1, "WIDE_TAIL": 2, "WIDE_PACK": 3, "AGG_FORK": 4, "SIGN_WIDE_MAX": 5, "WIDE_MAX": 6, "WIDE_VERIFY_MAX": 7,
@@ -315,7 +329,7 @@ def load():
         _preload_torch_hip_runtime()
         lib = ctypes.CDLL(LIB_PATH)
         for name, argtypes in list(SIGNATURES.items()) + list(SIGNATURES_KZG_POINTS.items()) + list(SIGNATURES_KZG_COSETS.items()) + \
-                list(SIGNATURES_KZG_RECOVER.items()) + list(SIGNATURES_KZG_CELLS.items()) + list(SIGNATURES_FR_SCAN.items()) + list(SIGNATURES_PLONK.items()):
+                list(SIGNATURES_KZG_RECOVER.items()) + list(SIGNATURES_KZG_CELLS.items()) + list(SIGNATURES_FR_SCAN.items()) + list(SIGNATURES_PLONK.items()) + list(SIGNATURES_POPEN.items()):
             fn = getattr(lib, name)  # AttributeError if the symbol is missing
             fn.argtypes = argtypes
             fn.restype = _RESTYPE.get(name, c_i32)

@@ -1077,6 +1077,55 @@ class PlonkQuotient:
         return engine().plonk_quotient(self.table, w, zc, pc, self.shifts, _words(beta), _words(gamma), _words(alpha), self.log_n, self.log_e)
 
 
+class PlonkOpening:
+    """The closing rounds of a PLONK-style prover for ONE circuit (include/sylow_popen.h): the evaluations at zeta, the linearisation
+    polynomial r, the fold F = r + sum_j v^(1+j) w_j + sum_j v^(W+1+j) sigma_j and the proofs W_zeta (F at zeta) and W_omega (z at
+    zeta w_n).  The arguments are PlonkQuotient's; log_e names the N = 2^log_e n coefficients of t as PlonkQuotient.quotient returns it.
+    The circuit's coefficient table is built once, here, and stays on the device; every instance reads it in place.  THE LIBRARY DRAWS NO
+    CHALLENGE: zeta is drawn AFTER the commitments to the chunks of t are fixed, v AFTER the evaluations are fixed."""
+
+    def __init__(self, log_n: int, shifts, sigma, selectors, log_e: int = 2):
+        perm = PlonkPermutation(log_n, shifts, sigma)                  # its validation of log_n, the shifts and sigma
+        self.log_n, self.log_e, self.shifts, self.sigma = perm.log_n, int(log_e), perm.shifts, perm.sigma
+        self.W = self.shifts.shape[0]
+        sel = _fr_nd(selectors, 2)
+        if self.W < 2 or self.log_e < 0 or self.log_n + self.log_e > 28 or sel.shape != (self.W + 2, 1 << self.log_n, 4):
+            raise ValueError("PlonkOpening: 2 .. 32 columns, log_n + log_e <= 28, selectors [W + 2, n, 4]")
+        self.ctable = engine().plonk_open_prepare(sel, self.sigma)
+
+    @staticmethod
+    def _batch(values, ndim):
+        if values is None:
+            return None
+        a = _fr_nd(values, ndim - 1, ndim - 2)                        # ndim: the dimensions of the batch as words, [m, .., 4]
+        return a[None] if a.ndim == ndim - 1 else a
+
+    def evaluate(self, wires, z, zeta, pi=None):
+        """evals [m, 2 W + 1, 4] canonical words for the COEFFICIENTS of the wires [m, W, len_w, 4] (or [W, len_w, 4]: one instance), of z
+        and of the public-input polynomial pi (or None), as words or nested lists of Python ints, and one zeta per instance
+        (sylow_popen_evaluate_batch): w_j(zeta), sigma_j(zeta) for j < W - 1, z(zeta w_n), PI(zeta)."""
+        return engine().plonk_open_evaluate(self.ctable, self._batch(wires, 4), self._batch(z, 3), self._batch(pi, 3), _words(zeta))
+
+    def linearise(self, wires, z, t, evals, beta, gamma, alpha, zeta, v=None):
+        """(r, F or None, status [m]) as [m, max(n, len_z[, len_w]), 4] canonical words (sylow_popen_linearise_batch): t [m, N, 4] as
+        PlonkQuotient.quotient returns it, evals as evaluate returns them.  v None: r alone.  status 0 = r(zeta) = 0 and zeta outside the
+        domain; bit 0 = r(zeta) != 0, bit 1 = zeta^n = 1."""
+        want_f = v is not None
+        return engine().plonk_open_linearise(self.ctable, self._batch(wires, 4) if want_f else None, self._batch(z, 3), self._batch(t, 3), self._batch(evals, 3),
+                                             self.shifts, _words(beta), _words(gamma), _words(alpha), _words(zeta), _words(v) if want_f else None, self.log_e,
+                                             want_f=want_f)
+
+    def open(self, prover: "KzgProver", wires, z, t, beta, gamma, alpha, zeta, v, pi=None):
+        """(evals [m, 2 W + 1, 4], w_zeta: G1Affine, w_omega: G1Affine, status [m]) under the prover's SRS, which holds at least
+        max(n, len_z, len_w) powers (sylow_popen_open_batch).  (commit(F), zeta, F(zeta), w_zeta) and (commit(z), zeta w_n, evals[:, 2 W - 1],
+        w_omega) are rows KzgVerifier.verify accepts.  v IS TAKEN BESIDE zeta: a caller whose v depends on the evaluations calls evaluate,
+        linearise and KzgProver.open instead."""
+        ev, (p1, f1), (p2, f2), status = engine().plonk_open(prover.srs_g1.xy, self.ctable, self._batch(wires, 4), self._batch(z, 3), self._batch(pi, 3),
+                                                             self._batch(t, 3), self.shifts, _words(beta), _words(gamma), _words(alpha), _words(zeta), _words(v),
+                                                             self.log_e)
+        return ev, G1Affine(p1, f1), G1Affine(p2, f2), status
+
+
 def _fr_nd(values, *ndims):
     """words [..., 4] from a uint64 array of words or from nested lists of Python ints with one of the given numbers of dimensions"""
     if isinstance(values, np.ndarray) and values.dtype == np.uint64:

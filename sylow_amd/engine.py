@@ -1700,6 +1700,106 @@ class Engine:
             self._call("sylow_plonk_quotient_batch_tuned", *ins, int(max_blocks), dt.ptr, ds.ptr)
         return np.ascontiguousarray(dt.download()[:m].transpose(0, 2, 1)), ds.download()[:m]
 
+    # ---- PLONK's closing rounds (include/sylow_popen.h): the evaluations at zeta, the linearisation polynomial, the two openings.  The
+    # coefficient table of a circuit stays on the device: [2 W + 2][4][n] ----
+    def plonk_open_prepare(self, selectors, sigma):
+        """The coefficient table of one circuit (sylow_popen_prepare): selectors [W + 2, n, 4] and sigma [W, n, 4] as for
+        plonk_quotient_prepare -> a DeviceArray [2 W + 2, 4, n]: the coefficients of q_0 .. q_(W-1), q_M, q_C, sigma_0 .. sigma_(W-1)."""
+        sel, sg = np.ascontiguousarray(selectors, dtype=np.uint64), np.ascontiguousarray(sigma, dtype=np.uint64)
+        assert sel.ndim == 3 and sg.ndim == 3 and sel.shape[2] == 4, (sel.shape, sg.shape)
+        W, n = sg.shape[0], sg.shape[1]
+        log_n = n.bit_length() - 1
+        assert n == 1 << log_n and sel.shape == (W + 2, n, 4) and sg.shape == (W, n, 4), (sel.shape, sg.shape)
+        dsel, dsg = self.to_device(np.ascontiguousarray(sel.transpose(0, 2, 1))), self.to_device(np.ascontiguousarray(sg.transpose(0, 2, 1)))
+        ctable = self.empty((2 * W + 2, 4, n))
+        self._call("sylow_popen_prepare", dsel.ptr, dsg.ptr, log_n, W, ctable.ptr)
+        return ctable
+
+    def plonk_open_ctable_up(self, rows):
+        """a coefficient table from host words: rows [2 W + 2, n, 4] -> the DeviceArray plonk_open_prepare would return for them"""
+        return self.to_device(np.ascontiguousarray(np.ascontiguousarray(rows, dtype=np.uint64).transpose(0, 2, 1)))
+
+    def plonk_open_ctable_down(self, ctable):
+        """rows [2 W + 2, n, 4] of a coefficient table on the device"""
+        return np.ascontiguousarray(ctable.download().transpose(0, 2, 1))
+
+    def _plonk_open_polys_up(self, ctable, wires, z, pi):
+        W, n = ctable.shape[0] // 2 - 1, ctable.shape[2]
+        z = np.ascontiguousarray(z, dtype=np.uint64)
+        assert z.ndim == 3 and z.shape[2] == 4 and z.shape[1] >= 1, z.shape
+        m, dw, len_w, dpi = z.shape[0], None, 1, None
+        if wires is not None:
+            w = np.ascontiguousarray(wires, dtype=np.uint64)
+            assert w.ndim == 4 and w.shape[:2] == (m, W) and w.shape[3] == 4 and w.shape[2] >= 1, (w.shape, z.shape, W)
+            len_w, dw = w.shape[2], (self.to_device(np.ascontiguousarray(w.transpose(0, 1, 3, 2))) if m else None)
+        if pi is not None:
+            p = np.ascontiguousarray(pi, dtype=np.uint64)
+            assert p.shape == (m, n, 4), p.shape
+            dpi = self._kzg_polys_up(p)
+        return W, n.bit_length() - 1, m, dw, len_w, self._kzg_polys_up(z), z.shape[1], dpi
+
+    def plonk_open_evaluate(self, ctable, wires, z, pi, zeta, max_blocks=-1):
+        """The 2 W + 1 evaluations of m instances (sylow_popen_evaluate_batch): the COEFFICIENTS of the wires [m, W, len_w, 4], of z
+        [m, len_z, 4] and of the public inputs ([m, n, 4] or None), zeta [m, 4] DRAWN AFTER THE COMMITMENTS TO t ARE FIXED -> evals
+        [m, 2 W + 1, 4]: w_j(zeta) for j < W, sigma_j(zeta) for j < W - 1, z(zeta w_n), PI(zeta).  max_blocks >= 1 caps the blocks of a
+        launch; the words do not depend on it."""
+        W, log_n, m, dw, len_w, dz, len_z, dpi = self._plonk_open_polys_up(ctable, wires, z, pi)
+        dzeta, = self._plonk_challenges_up(m, zeta)
+        de = self.empty((4, (2 * W + 1) * max(m, 1)))
+        ins = [ctable.ptr, self._ptr(dw), len_w, self._ptr(dz), len_z, self._ptr(dpi), self._ptr(dzeta), log_n, W, m]
+        if max_blocks < 0:
+            self._call("sylow_popen_evaluate_batch", *ins, de.ptr)
+        else:
+            self._call("sylow_popen_evaluate_batch_tuned", *ins, int(max_blocks), de.ptr)
+        return self.from_device_soa(de)[:(2 * W + 1) * m].reshape(m, 2 * W + 1, 4)
+
+    def plonk_open_linearise(self, ctable, wires, z, t, evals, shifts, beta, gamma, alpha, zeta, v, log_e=2, len_out=None, want_r=True, want_f=True,
+                             max_blocks=-1):
+        """r and F of m instances (sylow_popen_linearise_batch): t [m, N, 4] as plonk_quotient returns it, evals [m, 2 W + 1, 4] as
+        plonk_open_evaluate returns them, v [m, 4] DRAWN AFTER THE EVALUATIONS ARE FIXED -> (r [m, len_out, 4] or None, F [m, len_out, 4]
+        or None, status [m]: bit 0 = r(zeta) != 0, bit 1 = zeta^n = 1).  len_out None: the shortest the outputs allow.  Without want_f,
+        wires and v may be None."""
+        assert want_r or want_f
+        W, log_n, m, dw, len_w, dz, len_z, _ = self._plonk_open_polys_up(ctable, wires if want_f else None, z, None)
+        n, big = 1 << log_n, 1 << (log_n + log_e)
+        t, ev, sh = np.ascontiguousarray(t, dtype=np.uint64), np.ascontiguousarray(evals, dtype=np.uint64), _aos(shifts, 4)
+        assert t.shape == (m, big, 4) and ev.shape == (m, 2 * W + 1, 4) and sh.shape[0] == W, (t.shape, ev.shape, sh.shape)
+        if len_out is None:
+            len_out = max(n, len_z, len_w if want_f else 1)
+        dt, dev, dsh = self._kzg_polys_up(t), (self.to_device_soa(ev.reshape(-1, 4), 4) if m else None), self.to_device_soa(sh, 4)
+        db, dg, da, dzeta = self._plonk_challenges_up(m, beta, gamma, alpha, zeta)
+        dv = self._plonk_challenges_up(m, v)[0] if want_f else None
+        dr = self.empty((max(m, 1), 4, len_out)) if want_r else None
+        df = self.empty((max(m, 1), 4, len_out)) if want_f else None
+        ds = self.empty((max(m, 1),), np.uint8)
+        ins = [ctable.ptr, self._ptr(dw), len_w, self._ptr(dz), len_z, self._ptr(dt), self._ptr(dev), dsh.ptr, self._ptr(db), self._ptr(dg), self._ptr(da),
+               self._ptr(dzeta), self._ptr(dv), log_n, int(log_e), W, m, int(len_out)]
+        if max_blocks < 0:
+            self._call("sylow_popen_linearise_batch", *ins, self._ptr(dr), self._ptr(df), ds.ptr)
+        else:
+            self._call("sylow_popen_linearise_batch_tuned", *ins, int(max_blocks), self._ptr(dr), self._ptr(df), ds.ptr)
+        down = lambda d: None if d is None else np.ascontiguousarray(d.download()[:m].transpose(0, 2, 1))
+        return down(dr), down(df), ds.download()[:m]
+
+    def plonk_open(self, srs_g1, ctable, wires, z, pi, t, shifts, beta, gamma, alpha, zeta, v, log_e=2):
+        """The full route (sylow_popen_open_batch) under the monomial SRS srs_g1 [len_f, 8], len_f >= max(n, len_z, len_w): (evals
+        [m, 2 W + 1, 4], (W_zeta [m, 8], flags [m]), (W_omega [m, 8], flags [m]), status [m]).  The proofs are word for word kzg_open of F
+        at zeta and of z at zeta w_n.  v IS TAKEN BESIDE zeta: a caller whose v depends on the evaluations composes plonk_open_evaluate,
+        plonk_open_linearise and kzg_open."""
+        W, log_n, m, dw, len_w, dz, len_z, dpi = self._plonk_open_polys_up(ctable, wires, z, pi)
+        srs, t, sh = _aos(srs_g1, 8), np.ascontiguousarray(t, dtype=np.uint64), _aos(shifts, 4)
+        assert t.shape == (m, 1 << (log_n + log_e), 4) and sh.shape[0] == W, (t.shape, sh.shape)
+        dsrs, dt, dsh = self.to_device_soa(srs, 8), self._kzg_polys_up(t), self.to_device_soa(sh, 4)
+        db, dg, da, dzeta, dv = self._plonk_challenges_up(m, beta, gamma, alpha, zeta, v)
+        mm = max(m, 1)
+        de, d1, d1i, d2, d2i, ds = (self.empty((4, (2 * W + 1) * mm)), self.empty((8, mm)), self.empty((mm,), np.uint8), self.empty((8, mm)),
+                                    self.empty((mm,), np.uint8), self.empty((mm,), np.uint8))
+        self._call("sylow_popen_open_batch", dsrs.ptr, ctable.ptr, self._ptr(dw), len_w, self._ptr(dz), len_z, self._ptr(dpi), self._ptr(dt), dsh.ptr, self._ptr(db),
+                   self._ptr(dg), self._ptr(da), self._ptr(dzeta), self._ptr(dv), log_n, int(log_e), W, m, srs.shape[0], de.ptr, d1.ptr, d1i.ptr, d2.ptr, d2i.ptr,
+                   ds.ptr)
+        return (self.from_device_soa(de)[:(2 * W + 1) * m].reshape(m, 2 * W + 1, 4), (self.from_device_soa(d1)[:m], d1i.download()[:m]),
+                (self.from_device_soa(d2)[:m], d2i.download()[:m]), ds.download()[:m])
+
     # ---- Groth16, the prover's side.  A sparse matrix is CSR: (row_ptr [rows + 1], col [nnz], val [nnz, 4]); Fr batches are [m, n, 4] on the
     # host and [m][4][n] on the device; any 256-bit words, taken mod r ----
     def _csr_up(self, csr):
