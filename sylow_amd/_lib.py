@@ -277,6 +277,20 @@ SIGNATURES_POPEN = {
                                c_u8p, c_vp],
 }
 
+# the entry points of include/sylow_pverify.h (the batched PLONK verifier: term scalars, the KZG row, per-proof flags, one weighted boolean):
+# a ninth table, bound by the same load().  Their prefix is sylow_pverify_: the sets of sylow_hip_*, sylow_plonk_* and sylow_popen_* symbols
+# are closed (the header says why)
+_PV_IN = [c_u64p, c_u64p, c_sz] + [c_u64p] * 7                       # evals, pub, n_pub, shifts, beta, gamma, alpha, zeta, v, u
+_PV_PTS = [c_u64p, c_u8p, c_u64p, c_u8p]                             # vk_xy, vk_inf, proof_xy, proof_inf
+_PV_DIMS = [c_i32, c_i32, c_i32, c_sz]                               # log_n, log_e, W, m
+SIGNATURES_PVERIFY = {
+    "sylow_pverify_scalars_batch": _PV_IN + _PV_DIMS + [c_u64p, c_u64p, c_u8p, c_vp],
+    "sylow_pverify_scalars_batch_tuned": _PV_IN + _PV_DIMS + [ctypes.c_int64, c_u64p, c_u64p, c_u8p, c_vp],
+    "sylow_pverify_fold_batch": _PV_PTS + _PV_IN + _PV_DIMS + [c_u64p, c_u8p, c_u64p, c_u8p, c_u64p, c_u8p, c_vp],
+    "sylow_pverify_verify_batch": [c_u64p] + _PV_PTS + _PV_IN + _PV_DIMS + [c_u8p, c_u8p, c_vp],
+    "sylow_pverify_batch_verify_weighted": [c_u64p] + _PV_PTS + _PV_IN + [c_u64p] + _PV_DIMS + [c_u64p, c_u8p, c_u8p, c_vp],
+}
+
 # SYLOW_HIP_OPT_* of include/sylow_hip.h.  The LIBRARY reads no environment variable; this host layer does, once, when it loads the library:
 # SYLOW_HIP_<NAME>=<integer> becomes sylow_hip_set_option(<NAME>, value) -- what tests/test_gpu_routes.py and the A/B scripts under tools/ set
 OPTIONS = {"STAGGER": 0, "MULTI_TABLES": 1, "WIDE_TAIL": 2, "WIDE_PACK": 3, "AGG_FORK": 4, "SIGN_WIDE_MAX": 5, "WIDE_MAX": 6, "WIDE_VERIFY_MAX": 7,
@@ -329,7 +343,8 @@ def load():
         _preload_torch_hip_runtime()
         lib = ctypes.CDLL(LIB_PATH)
         for name, argtypes in list(SIGNATURES.items()) + list(SIGNATURES_KZG_POINTS.items()) + list(SIGNATURES_KZG_COSETS.items()) + \
-                list(SIGNATURES_KZG_RECOVER.items()) + list(SIGNATURES_KZG_CELLS.items()) + list(SIGNATURES_FR_SCAN.items()) + list(SIGNATURES_PLONK.items()) + list(SIGNATURES_POPEN.items()):
+                list(SIGNATURES_KZG_RECOVER.items()) + list(SIGNATURES_KZG_CELLS.items()) + list(SIGNATURES_FR_SCAN.items()) + list(SIGNATURES_PLONK.items()) + list(SIGNATURES_POPEN.items()) + \
+                list(SIGNATURES_PVERIFY.items()):
             fn = getattr(lib, name)  # AttributeError if the symbol is missing
             fn.argtypes = argtypes
             fn.restype = _RESTYPE.get(name, c_i32)

@@ -17,6 +17,7 @@ HEADER_KZG_CELLS = os.path.join(os.path.dirname(_HERE), "include", "sylow_hip_kz
 HEADER_FR_SCAN = os.path.join(os.path.dirname(_HERE), "include", "sylow_hip_fr_scan.h")
 HEADER_PLONK = os.path.join(os.path.dirname(_HERE), "include", "sylow_plonk.h")                    # its entry points are sylow_plonk_*
 HEADER_POPEN = os.path.join(os.path.dirname(_HERE), "include", "sylow_popen.h")                    # its entry points are sylow_popen_*
+HEADER_PVERIFY = os.path.join(os.path.dirname(_HERE), "include", "sylow_pverify.h")                # its entry points are sylow_pverify_*
 ITEMSIZE = {"u64": 8, "i64": 8, "u8": 1, "i32": 4, "void": 1}
 _EXPR_OK = re.compile(r"^[\w\s+*()]+$")
 
@@ -42,7 +43,7 @@ def parse(path: str = HEADER):
     """-> {entry point: (parameter names in order, {parameter: Shape})} for every annotated prototype"""
     text = open(path).read()
     out = {}
-    for m in re.finditer(r"/\* @shape ([^\n]*?) \*/\s*\n\s*int32_t\s+(sylow_(?:hip|plonk|popen)_\w+)\s*\(([^)]*)\)\s*;", text):
+    for m in re.finditer(r"/\* @shape ([^\n]*?) \*/\s*\n\s*int32_t\s+(sylow_(?:hip|plonk|popen|pverify)_\w+)\s*\(([^)]*)\)\s*;", text):
         params = re.sub(r"/\*.*?\*/", " ", m.group(3))                  # inline remarks like `uint8_t* out /*[n][64]*/`
         names = [p.replace("*", " ").split()[-1] for p in " ".join(params.split()).split(",")]
         shapes = {}
@@ -66,7 +67,7 @@ def table():
     if _TABLE is None:
         try:
             _TABLE = {**parse(), **parse(HEADER_KZG_POINTS), **parse(HEADER_KZG_COSETS), **parse(HEADER_KZG_RECOVER),
-                      **parse(HEADER_KZG_CELLS), **parse(HEADER_FR_SCAN), **parse(HEADER_PLONK), **parse(HEADER_POPEN)}
+                      **parse(HEADER_KZG_CELLS), **parse(HEADER_FR_SCAN), **parse(HEADER_PLONK), **parse(HEADER_POPEN), **parse(HEADER_PVERIFY)}
         except OSError:            # the package deployed without the repo's include/ directory: no table, nothing to check
             _TABLE = {}
     return _TABLE

@@ -1126,6 +1126,54 @@ class PlonkOpening:
         return ev, G1Affine(p1, f1), G1Affine(p2, f2), status
 
 
+class PlonkVerifier:
+    """The verifier of many proofs of ONE circuit (include/sylow_pverify.h): `vk` is a G1Affine of the 2 W + 2 commitments [q_0] .. [q_(W-1)],
+    [q_M], [q_C], [sigma_0] .. [sigma_(W-1)] (key_from derives them), `tau_g2` a G2Affine of one point in G2 proper, log_e names the
+    E = 2^log_e chunks of t a proof commits to.  The key and tau_g2 stay on the device.  A batch of m proofs is `proofs`, a G1Affine of
+    m (W + E + 3) points, proof-major: [w_0] .. [w_(W-1)], [z], [t_0] .. [t_(E-1)], W_zeta, W_omega of proof 0, then of proof 1;
+    `evals` [m, 2 W + 1, 4] as PlonkOpening.open returns them (slot 2 W is not read); `pub` [m, l, 4] words or m lists of l Python ints, the
+    values of PI on rows 0 .. l - 1 (None: no public inputs).  THE LIBRARY DRAWS NO CHALLENGE: beta, gamma, alpha, zeta and v are those of
+    the transcript, u is drawn AFTER W_zeta and W_omega are fixed, the weights AFTER all proofs are fixed."""
+
+    def __init__(self, log_n: int, shifts, vk: "G1Affine", tau_g2: "G2Affine", log_e: int = 2):
+        self.log_n, self.log_e, self.shifts = int(log_n), int(log_e), _words(shifts)
+        self.W = self.shifts.shape[0]
+        if not 2 <= self.W <= 32 or self.log_n < 0 or self.log_e < 0 or self.log_n + self.log_e > 28 or len(vk) != 2 * self.W + 2 or len(tau_g2) != 1:
+            raise ValueError("PlonkVerifier: 2 .. 32 columns, log_n + log_e <= 28, a key of 2 W + 2 points, one tau_g2")
+        self.vk = engine().plonk_verify_key_up(vk.xy, vk.infinity)
+        self.tau_g2 = engine().to_device_soa(tau_g2.xy, 16)
+
+    @classmethod
+    def key_from(cls, prover: "KzgProver", ctable) -> "G1Affine":
+        """The verifying key of a circuit: the commitments to the rows of a PlonkOpening's coefficient table (a DeviceArray [2 W + 2, 4, n], or
+        rows [2 W + 2, n, 4] as words) under the prover's SRS, by KzgProver.commit.  A row that is the zero polynomial gives the identity."""
+        rows = ctable if isinstance(ctable, np.ndarray) else engine().plonk_open_ctable_down(ctable)
+        n, have = rows.shape[1], len(prover.srs_g1)
+        if have < n:
+            raise ValueError("PlonkVerifier.key_from: the SRS holds fewer powers than a row has coefficients")
+        return prover.commit(np.concatenate([rows, np.zeros((rows.shape[0], have - n, 4), dtype=np.uint64)], axis=1))
+
+    def _args(self, proofs, evals, pub, challenges):
+        ev = _fr_nd(evals, 2)
+        m, slots = ev.shape[0], self.W + (1 << self.log_e) + 3
+        if ev.shape[1] != 2 * self.W + 1 or len(proofs) != m * slots:
+            raise ValueError("PlonkVerifier: evals [m, 2 W + 1, 4] and m (W + E + 3) proof points, proof-major")
+        pb = None if pub is None else _fr_nd(pub, 2)
+        return (self.vk, proofs.xy.reshape(m, slots, 8), ev, pb, self.shifts) + tuple(_words(c) for c in challenges), proofs.infinity.reshape(m, slots)
+
+    def verify(self, proofs: "G1Affine", evals, pub, beta, gamma, alpha, zeta, v, u):
+        """(ok [m] bool, status [m]): ok_i = proof i verifies (sylow_pverify_verify_batch); status bit 1 = zeta_i^n = 1, and ok_i is False."""
+        args, inf = self._args(proofs, evals, pub, (beta, gamma, alpha, zeta, v, u))
+        ok, status = engine().plonk_verify(self.tau_g2, *args, self.log_n, self.log_e, proof_inf=inf)
+        return ok.astype(bool), status
+
+    def verify_weighted(self, proofs: "G1Affine", evals, pub, beta, gamma, alpha, zeta, v, u, weights) -> bool:
+        """all m proofs as one boolean (sylow_pverify_batch_verify_weighted): a weight of 0 mod r removes a proof; a proof whose zeta lies in
+        the domain makes it False unless its weight is 0."""
+        args, inf = self._args(proofs, evals, pub, (beta, gamma, alpha, zeta, v, u))
+        return engine().plonk_batch_verify_weighted(self.tau_g2, *args, _words(weights), self.log_n, self.log_e, proof_inf=inf)[1]
+
+
 def _fr_nd(values, *ndims):
     """words [..., 4] from a uint64 array of words or from nested lists of Python ints with one of the given numbers of dimensions"""
     if isinstance(values, np.ndarray) and values.dtype == np.uint64:

@@ -1800,6 +1800,89 @@ class Engine:
         return (self.from_device_soa(de)[:(2 * W + 1) * m].reshape(m, 2 * W + 1, 4), (self.from_device_soa(d1)[:m], d1i.download()[:m]),
                 (self.from_device_soa(d2)[:m], d2i.download()[:m]), ds.download()[:m])
 
+    # ---- the batched PLONK verifier (include/sylow_pverify.h).  A key is (points, flags or None) as host words [2 W + 2, 8] / [2 W + 2] or as
+    # the pair of DeviceArrays plonk_verify_key_up returns; proofs are [m, W + E + 3, 8] words + flags [m, W + E + 3] or None on the host and
+    # slot-major on the device; evals [m, 2 W + 1, 4] exactly as plonk_open_evaluate returns them; pub [m, n_pub, 4] or None ----
+    def plonk_verify_key_up(self, vk_xy, vk_inf=None):
+        """a verifying key onto the device, once: ([8][2 W + 2] words, flags or None)"""
+        vk = _aos(vk_xy, 8)
+        return self.to_device_soa(vk, 8), self._flags(vk_inf, vk.shape[0])
+
+    def _plonk_verify_up(self, evals, pub, shifts, challenges, log_n, log_e, vk=None, proofs=None, proof_inf=None):
+        ev, sh = np.ascontiguousarray(evals, dtype=np.uint64), _aos(shifts, 4)
+        assert ev.ndim == 3 and ev.shape[2] == 4 and ev.shape[1] == 2 * sh.shape[0] + 1, (ev.shape, sh.shape)
+        m, W, E = ev.shape[0], sh.shape[0], 1 << int(log_e)
+        n_pub, dpub = 0, None
+        if pub is not None:
+            p = np.ascontiguousarray(pub, dtype=np.uint64)
+            assert p.ndim == 3 and p.shape[0] == m and p.shape[2] == 4, p.shape
+            n_pub = p.shape[1]
+            dpub = self.to_device_soa(np.ascontiguousarray(p.transpose(1, 0, 2)).reshape(-1, 4), 4) if m and n_pub else None
+        dev = self.to_device_soa(ev.reshape(-1, 4), 4) if m else None
+        ins = [self._ptr(dev), self._ptr(dpub), n_pub, self.to_device_soa(sh, 4)] + self._plonk_challenges_up(m, *challenges)
+        dims = [int(log_n), int(log_e), W, m]
+        pts = []
+        if vk is not None:
+            dvk, dvi = vk if isinstance(vk[0], DeviceArray) else self.plonk_verify_key_up(*vk)
+            assert dvk.shape == (8, 2 * W + 2), dvk.shape
+            pr = np.ascontiguousarray(proofs, dtype=np.uint64)
+            assert pr.shape == (m, W + E + 3, 8), (pr.shape, m, W, E)
+            dpr = self.to_device_soa(np.ascontiguousarray(pr.transpose(1, 0, 2)).reshape(-1, 8), 8) if m else None
+            dpi = None
+            if proof_inf is not None and m:
+                dpi = self.to_device(np.ascontiguousarray(np.asarray(proof_inf, dtype=np.uint8).reshape(m, W + E + 3).T))
+            pts = [dvk, dvi, dpr, dpi]
+        held = [dev, dpub] + ins[3:] + pts
+        return m, W, E, [self._ptr(x) if isinstance(x, DeviceArray) or x is None else x for x in pts], \
+            [self._ptr(x) if isinstance(x, DeviceArray) else x for x in ins], dims, held
+
+    def plonk_verify_scalars(self, evals, pub, shifts, beta, gamma, alpha, zeta, v, u, log_n, log_e=2, max_blocks=-1):
+        """The term scalars of m proofs (sylow_pverify_scalars_batch): (k [m, 3 W + E + 5, 4] in the header's term order, y [m, 4], status
+        [m]: bit 1 = zeta^n = 1), canonical words.  Slot 2 W of evals is not read.  max_blocks >= 1 caps the blocks of a launch; the words do
+        not depend on it."""
+        m, W, E, _, ins, dims, held = self._plonk_verify_up(evals, pub, shifts, (beta, gamma, alpha, zeta, v, u), log_n, log_e)
+        T, mm = 3 * W + E + 5, max(m, 1)
+        dk, dy, ds = self.empty((4, T * mm)), self.empty((4, mm)), self.empty((mm,), np.uint8)
+        if max_blocks < 0:
+            self._call("sylow_pverify_scalars_batch", *ins, *dims, dk.ptr, dy.ptr, ds.ptr)
+        else:
+            self._call("sylow_pverify_scalars_batch_tuned", *ins, *dims, int(max_blocks), dk.ptr, dy.ptr, ds.ptr)
+        k = self.from_device_soa(dk)[:T * m].reshape(T, m, 4).transpose(1, 0, 2)
+        return np.ascontiguousarray(k), self.from_device_soa(dy)[:m], ds.download()[:m]
+
+    def plonk_verify_fold(self, vk, proofs, evals, pub, shifts, beta, gamma, alpha, zeta, v, u, log_n, log_e=2, proof_inf=None):
+        """The KZG row of every proof (sylow_pverify_fold_batch): ((C [m, 8], flags [m]), (pi [m, 8], flags [m]), y [m, 4], status [m]); C and
+        pi are bit-identical to g1_lincomb over the literal terms."""
+        m, W, E, pts, ins, dims, held = self._plonk_verify_up(evals, pub, shifts, (beta, gamma, alpha, zeta, v, u), log_n, log_e, vk, proofs, proof_inf)
+        mm = max(m, 1)
+        dc, dci, dp, dpi, dy, ds = (self.empty((8, mm)), self.empty((mm,), np.uint8), self.empty((8, mm)), self.empty((mm,), np.uint8), self.empty((4, mm)),
+                                    self.empty((mm,), np.uint8))
+        self._call("sylow_pverify_fold_batch", *pts, *ins, *dims, dc.ptr, dci.ptr, dp.ptr, dpi.ptr, dy.ptr, ds.ptr)
+        return ((self.from_device_soa(dc)[:m], dci.download()[:m]), (self.from_device_soa(dp)[:m], dpi.download()[:m]), self.from_device_soa(dy)[:m],
+                ds.download()[:m])
+
+    def plonk_verify(self, tau_g2, vk, proofs, evals, pub, shifts, beta, gamma, alpha, zeta, v, u, log_n, log_e=2, proof_inf=None):
+        """(ok [m], status [m]) for m proofs of one circuit (sylow_pverify_verify_batch): ok_i = both openings of proof i verify under u_i, and
+        0 where status bit 1 (zeta^n = 1) is set.  tau_g2 [1, 16] words or a DeviceArray [16, 1]; it must lie in G2 proper."""
+        dtau = tau_g2 if isinstance(tau_g2, DeviceArray) else self.to_device_soa(_aos(tau_g2, 16), 16)
+        assert dtau.shape == (16, 1), dtau.shape
+        m, W, E, pts, ins, dims, held = self._plonk_verify_up(evals, pub, shifts, (beta, gamma, alpha, zeta, v, u), log_n, log_e, vk, proofs, proof_inf)
+        dok, ds = self.empty((max(m, 1),), np.uint8), self.empty((max(m, 1),), np.uint8)
+        self._call("sylow_pverify_verify_batch", dtau.ptr, *pts, *ins, *dims, dok.ptr, ds.ptr)
+        return dok.download()[:m], ds.download()[:m]
+
+    def plonk_batch_verify_weighted(self, tau_g2, vk, proofs, evals, pub, shifts, beta, gamma, alpha, zeta, v, u, weights, log_n, log_e=2, proof_inf=None):
+        """m proofs as ONE Gt (sylow_pverify_batch_verify_weighted): (Gt words [1, 48], bool, status [m]); weights [m, 4] drawn by the caller
+        AFTER all proofs are fixed (any 256-bit words, taken mod r; 0 removes a proof).  The bool is False when a proof with a nonzero weight
+        has zeta^n = 1."""
+        dtau = tau_g2 if isinstance(tau_g2, DeviceArray) else self.to_device_soa(_aos(tau_g2, 16), 16)
+        assert dtau.shape == (16, 1), dtau.shape
+        m, W, E, pts, ins, dims, held = self._plonk_verify_up(evals, pub, shifts, (beta, gamma, alpha, zeta, v, u), log_n, log_e, vk, proofs, proof_inf)
+        dw, = self._plonk_challenges_up(m, weights)
+        dgt, dis, ds = self.empty((48, 1)), self.empty((1,), np.uint8), self.empty((max(m, 1),), np.uint8)
+        self._call("sylow_pverify_batch_verify_weighted", dtau.ptr, *pts, *ins, self._ptr(dw), *dims, dgt.ptr, dis.ptr, ds.ptr)
+        return self.from_device_soa(dgt), bool(dis.download()[0]), ds.download()[:m]
+
     # ---- Groth16, the prover's side.  A sparse matrix is CSR: (row_ptr [rows + 1], col [nnz], val [nnz, 4]); Fr batches are [m, n, 4] on the
     # host and [m][4][n] on the device; any 256-bit words, taken mod r ----
     def _csr_up(self, csr):
