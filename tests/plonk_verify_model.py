@@ -11,7 +11,8 @@ model works IN THE EXPONENT: a point is its discrete logarithm mod r, and a row 
     y  = sum_j v^(1+j) a_j + sum_{j<W-1} v^(W+1+j) s_j + u zw - [ p - B' (a_(W-1) + gamma) - alpha^2 L1 ]
     C  = sum_c k_c P_c,   pi = W_zeta + u W_omega,   status bit 1: zeta^n = 1 (then ok is forced to 0)
 
-Inputs are any 256-bit integers, taken mod r."""
+Inputs are any 256-bit integers, taken mod r.  proof_for is an independent prover in the exponent; holding_batch makes rows that verify at any
+shape with no circuit behind them, and break_rows breaks them."""
 import ntt_model as T
 import plonk_open_model as O
 import plonk_quotient_model as Q
@@ -108,10 +109,13 @@ def weighted_ok(vk, proofs, ks, ys, us, weights, W, tau=TAU):
     return (p0 + tau * p1) % R == 0
 
 
-def proof_for(rng, log_n, W, log_e, l, tau=TAU):
+def proof_for(rng, log_n, W, log_e, l, tau=TAU, circuit=None):
     """a circuit with l public inputs, a blinded witness that satisfies it and its proof by the prover's model (O.open_polys, then the two
-    quotients by X - zeta and X - zeta w_n), every commitment f(tau) as its logarithm: a dict with vk, proof, evals, pub, shifts, ch"""
-    c = public_circuit(rng, log_n, W, l)
+    quotients by X - zeta and X - zeta w_n), every commitment f(tau) as its logarithm: a dict with vk, proof, evals, pub, shifts, ch.
+    circuit: the "c" of an earlier call with the same log_n, W and l -- the proof is then of that circuit, under the same key, with blinders and
+    challenges of its own"""
+    c = public_circuit(rng, log_n, W, l) if circuit is None else circuit
+    assert (c["log_n"], c["W"], c["l"]) == (log_n, W, l)
     n, big = 1 << log_n, 1 << (log_n + log_e)
     ch = {k: rng.randrange(2, R) for k in CHALLENGES}
     wc, zc, pc = Q.witness_polys(c, ch["beta"], ch["gamma"], rng)
@@ -127,6 +131,129 @@ def proof_for(rng, log_n, W, log_e, l, tau=TAU):
     at = lambda poly: Q.p_eval(poly, tau)
     return {"c": c, "ct": ct, "wires": wc, "z": zc, "pi": pc, "t": t, "vk": [at(r) for r in ct], "evals": ev, "pub": list(c["pub"]), "shifts": c["shifts"], "ch": ch,
             "proof": [at(w) for w in wc] + [at(zc)] + [at(t[e * n:(e + 1) * n]) for e in range(1 << log_e)] + [at(q_f), at(q_z)]}
+
+
+# ---- batches of rows that hold at any shape, with no circuit behind them --------------------------------------------------------------------
+KINDS = ("evaluation", "public_input", "t0_is_z", "wzeta_is_womega", "zeta_in_domain")       # the ways break_rows breaks a row
+
+
+def batch_scalars(b, rows=None):
+    """[(k, y, status)] of the rows of a batch (all of them by default)"""
+    rows = range(b["m"]) if rows is None else rows
+    return [scalars(b["evals"][i], b["pub"][i], b["shifts"], *(b[c][i] for c in CHALLENGES), b["log_n"], b["log_e"]) for i in rows]
+
+
+def batch_verify(b, sc=None):
+    """[the boolean of every row]; sc: batch_scalars(b), where the caller has them"""
+    out = []
+    for i, (k, y, status) in enumerate(batch_scalars(b) if sc is None else sc):
+        c, pi = row(b["vk"], b["proofs"][i], k, b["u"][i])
+        out.append(status == 0 and (c - y - TAU * pi) % R == 0)
+    return out
+
+
+def batch_weighted(b, weights, sc=None):
+    """(p0, p1, the boolean) of the weighted form: the logarithms of the G1 sides of the two literal pairs, and weighted_ok with the veto of a
+    live row (weight != 0 mod r) whose zeta lies in the domain"""
+    sc = batch_scalars(b) if sc is None else sc
+    ks, ys = [s[0] for s in sc], [s[1] for s in sc]
+    p0, p1 = weighted_pairs(b["vk"], b["proofs"], ks, ys, b["u"], weights, b["W"])
+    vetoed = any(s[2] and w % R for s, w in zip(sc, weights))
+    assert ((p0 + TAU * p1) % R == 0) == weighted_ok(b["vk"], b["proofs"], ks, ys, b["u"], weights, b["W"])
+    return p0, p1, (p0 + TAU * p1) % R == 0 and not vetoed
+
+
+def solve_w0(b, i):
+    """slot 0 ([w_0], scalar v != 0) of proof i from C - y = tau pi: the row then holds in the exponent whatever its status says"""
+    (k, y, _), = batch_scalars(b, [i])
+    K, pr = key_points(b["W"]), b["proofs"][i]
+    assert k[K] == b["v"][i] % R != 0
+    pr[0] = 0
+    c, pi = row(b["vk"], pr, k, b["u"][i])
+    pr[0] = (y + TAU * pi - c) * pow(k[K], R - 2, R) % R
+    c, pi = row(b["vk"], pr, k, b["u"][i])
+    assert (c - y - TAU * pi) % R == 0
+
+
+def holding_batch(rng, log_n, W, log_e, n_pub, m, pool=None, vk_zero=(), proof_zero=None):
+    """m rows under one key that verify in the exponent, at ANY shape -- also where no satisfied witness exists (log_e = 0): evaluations, public
+    inputs, shifts and the six challenges are random full-range 256-bit words (v nonzero mod r), the key's logarithms and those of slots
+    1 .. P - 1 of every proof are random and nonzero (drawn from `pool`, a list of logarithms, where one is given), and slot 0 of every proof
+    is solved last.  vk_zero: key slots whose logarithm is 0 (the identity); proof_zero: {row: slots >= 1} likewise.  A dict: the dimensions,
+    vk [2 W + 2], proofs [m][W + E + 3], evals [m][2 W + 1], pub [m][n_pub], shifts [W] and a list [m] under the name of every challenge"""
+    wide = lambda: rng.getrandbits(256)
+    draw = (lambda: rng.choice(pool)) if pool else (lambda: rng.randrange(1, R))
+    K, P = key_points(W), proof_points(W, log_e)
+    b = {"log_n": log_n, "W": W, "log_e": log_e, "n_pub": n_pub, "m": m, "shifts": [wide() for _ in range(W)],
+         "evals": [[wide() for _ in range(2 * W + 1)] for _ in range(m)], "pub": [[wide() for _ in range(n_pub)] for _ in range(m)]}
+    for c in CHALLENGES:
+        b[c] = [wide() for _ in range(m)]
+    for i in range(m):
+        while b["v"][i] % R == 0:
+            b["v"][i] = wide()
+    b["vk"] = [0 if c in vk_zero else draw() for c in range(K)]
+    b["proofs"] = [[0] + [draw() for _ in range(P - 1)] for _ in range(m)]
+    for i, slots in (proof_zero or {}).items():
+        for s in slots:
+            assert 1 <= s < P
+            b["proofs"][i][s] = 0
+    for i in range(m):
+        solve_w0(b, i)
+    assert all(batch_verify(b))
+    return b
+
+
+def break_rows(b, where):
+    """a copy of a batch with the rows of `where` ({row: one of KINDS}) broken: evaluation 0 + 1; public input 0 + 1 (n_pub > 0); slot [t_0]
+    replaced by slot [z]; W_zeta replaced by W_omega; or zeta := w_n^j with [w_0] solved again, so that the row KEEPS holding in the exponent
+    and only its status (bit 1) refuses it"""
+    out = dict(b)
+    for key in ("evals", "pub", "proofs"):
+        out[key] = [list(r) for r in b[key]]
+    out["zeta"] = list(b["zeta"])
+    W, n = b["W"], 1 << b["log_n"]
+    for i, kind in where.items():
+        assert kind in KINDS
+        if kind == "evaluation":
+            out["evals"][i][0] = out["evals"][i][0] % R + 1            # + 1 in Fr, and still a 256-bit word
+        elif kind == "public_input":
+            assert b["n_pub"] > 0
+            out["pub"][i][0] = out["pub"][i][0] % R + 1
+        elif kind == "t0_is_z":
+            out["proofs"][i][W + 1] = out["proofs"][i][W]
+        elif kind == "wzeta_is_womega":
+            out["proofs"][i][-2] = out["proofs"][i][-1]
+        else:
+            out["zeta"][i] = pow(T.omega(b["log_n"]), 3 % n, R)
+            solve_w0(out, i)
+    return out
+
+
+def take_rows(b, rows):
+    """the rows `rows` of a batch as a batch of their own, under the same key"""
+    out = dict(b, m=len(rows))
+    for key in ("evals", "pub", "proofs") + CHALLENGES:
+        out[key] = [b[key][i] for i in rows]
+    return out
+
+
+def batch_of(proofs, log_n, log_e):
+    """the batch, as holding_batch lays it out, of proofs that proof_for made for ONE circuit"""
+    p = proofs[0]
+    assert all(q["vk"] == p["vk"] and q["shifts"] == p["shifts"] for q in proofs), "one key"
+    b = {"log_n": log_n, "W": len(p["shifts"]), "log_e": log_e, "n_pub": len(p["pub"]), "m": len(proofs), "shifts": list(p["shifts"]), "vk": list(p["vk"]),
+         "proofs": [list(q["proof"]) for q in proofs], "evals": [list(q["evals"]) for q in proofs], "pub": [list(q["pub"]) for q in proofs]}
+    for c in CHALLENGES:
+        b[c] = [q["ch"][c] for q in proofs]
+    return b
+
+
+def fold_chunk_bytes(W, log_e, n_pub, mc):
+    """the lease of a chunk of mc whole proofs of the fold, by the rule of plonk_verify_plan.hpp: per proof 8 n_pub words of denominators and
+    inverses, 4 + 8 words a term, 2 (8 + 4) + 16 words for pi's two terms and the two results, and the flags of the chunk -- a byte a term and
+    four a proof -- rounded up to a word"""
+    t = terms(W, log_e)
+    return 8 * (mc * (8 * n_pub + 12 * t + 40) + ((t + 4) * mc + 7) // 8)
 
 
 # ---- words for the tests that drive the engine: points from logarithms through the oracle's generator multiples ---------------------------
