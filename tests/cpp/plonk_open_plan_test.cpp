@@ -156,7 +156,38 @@ static void chunks_and_scratch() {
          "2^20 rows: %zu bytes an instance", open_budget_bytes(20, 2, 3, (1 << 20) + 2, (1 << 20) + 3, (1 << 20) + 4, 1));
 }
 
+// The scratch limits tests/test_gpu_plonk_prover_routes.py sets for the full route, one row each, the same numbers as that file's OPEN_LIMITS
+// (tests/test_plonk_prover_route_limits.py compares the two): log_n, log_e, W, len_w, len_z, len_f, m, the limit in bytes, the instances of a
+// full chunk.  Each limit holds that many instances and not one more by the plan's own functions, and cuts m into the chunks beside it.
+static const size_t ROUTE_LIMITS[][9] = {
+    {3, 2, 3, 10, 11, 16, 5, 6000, 2},           // a_two
+    {3, 2, 3, 10, 11, 16, 5, 4000, 1},           // a_one
+    {8, 2, 2, 258, 259, 300, 3, 70000, 2},       // b_two
+    {0, 2, 2, 3, 4, 4, 300, 164500, 128},        // e_128
+};
+static const std::vector<size_t> ROUTE_CHUNKS[] = {{2, 2, 1}, {1, 1, 1, 1, 1}, {2, 1}, {128, 128, 44}};
+static void limits_of_the_route_tests() {
+  static_assert(sizeof(ROUTE_LIMITS) / sizeof(ROUTE_LIMITS[0]) == sizeof(ROUTE_CHUNKS) / sizeof(ROUTE_CHUNKS[0]), "a chunk sequence per limit");
+  for (size_t i = 0; i < sizeof(ROUTE_LIMITS) / sizeof(ROUTE_LIMITS[0]); ++i) {
+    const size_t* r = ROUTE_LIMITS[i];
+    const int log_n = (int)r[0], log_e = (int)r[1], W = (int)r[2];
+    const size_t len_w = r[3], len_z = r[4], len_f = r[5], m = r[6], limit = r[7], k = r[8];
+    EXPECT(dims_ok(log_n, log_e, W) && lens_ok(log_big(log_n, log_e), len_w, len_z) && len_out_ok(log_n, len_w, len_z, len_f, true), "row %zu: the route takes the shape", i);
+    EXPECT(instances_per_chunk(log_n, log_e, W, len_w, len_z, len_f, m, limit) == k, "row %zu: %zu", i, instances_per_chunk(log_n, log_e, W, len_w, len_z, len_f, m, limit));
+    EXPECT(k < m && open_budget_bytes(log_n, log_e, W, len_w, len_z, len_f, k) <= limit && limit < open_budget_bytes(log_n, log_e, W, len_w, len_z, len_f, k + 1),
+           "row %zu: %zu <= %zu < %zu", i, open_budget_bytes(log_n, log_e, W, len_w, len_z, len_f, k), limit, open_budget_bytes(log_n, log_e, W, len_w, len_z, len_f, k + 1));
+    std::vector<size_t> sizes;
+    for (size_t s0 = 0; s0 < m; s0 += k) sizes.push_back(chunk_size(m, k, s0));
+    EXPECT(sizes == ROUTE_CHUNKS[i] && chunk_count(m, k) == sizes.size(), "row %zu: %zu chunks", i, sizes.size());
+  }
+  // the rule by hand at the first shape: an instance leases 260 words and the opening 64 more, and the two flags of each round up to a word
+  EXPECT(open_budget_bytes(3, 2, 3, 10, 11, 16, 2) == (2 * 324 + 1) * 8 && open_budget_bytes(3, 2, 3, 10, 11, 16, 3) == (3 * 324 + 1) * 8, "k 324 words and the flags");
+  // a ragged last chunk runs with stride 1 inside a lease laid out for 2: the second point of an instance lies 4 c words on, not 4 mc
+  EXPECT(chunk_size(5, 2, 4) == 1 && point_words(2) == 16 && point_words(1) == 8, "the last chunk of a_two");
+}
+
 int main() {
+  limits_of_the_route_tests();
   constants_and_pins();
   table_and_slots();
   eval_items_and_chunk_edges();

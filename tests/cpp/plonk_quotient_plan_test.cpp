@@ -121,7 +121,46 @@ static void chunks_and_scratch() {
   EXPECT(instances_per_chunk(26, 2, 3, 4, (size_t)1 << 40, (size_t)1 << 30) == 0 && chunk_budget_bytes(20, 2, 3, 4, 1) > ((size_t)1 << 30), "2^20 rows do not fit 1 GB");
 }
 
+// The scratch limits tests/test_gpu_plonk_prover_routes.py sets for the full route, one row each, the same numbers as that file's
+// QUOTIENT_LIMITS (tests/test_plonk_prover_route_limits.py compares the two): log_n, log_e, W, columns, m, the limit in bytes, the instances
+// of a full chunk.  Each limit holds that many instances and not one more by the plan's own functions, and cuts m into the chunks beside it.
+static const size_t ROUTE_LIMITS[][7] = {
+    {9, 2, 3, 4, 3, 2200000, 2},                 // f_two
+    {9, 2, 3, 5, 3, 2200000, 2},                 // f_two_pi
+};
+static const std::vector<size_t> ROUTE_CHUNKS[] = {{2, 1}, {2, 1}};
+static void limits_of_the_route_tests() {
+  static_assert(sizeof(ROUTE_LIMITS) / sizeof(ROUTE_LIMITS[0]) == sizeof(ROUTE_CHUNKS) / sizeof(ROUTE_CHUNKS[0]), "a chunk sequence per limit");
+  for (size_t i = 0; i < sizeof(ROUTE_LIMITS) / sizeof(ROUTE_LIMITS[0]); ++i) {
+    const size_t* r = ROUTE_LIMITS[i];
+    const int log_n = (int)r[0], log_e = (int)r[1], W = (int)r[2];
+    const size_t cols = r[3], m = r[4], limit = r[5], k = r[6];
+    EXPECT(dims_ok(log_n, log_e, W) && (cols == columns(W, false) || cols == columns(W, true)), "row %zu: the route takes the shape", i);
+    EXPECT(instances_per_chunk(log_n, log_e, W, cols, m, limit) == k, "row %zu: %zu", i, instances_per_chunk(log_n, log_e, W, cols, m, limit));
+    EXPECT(k < m && chunk_budget_bytes(log_n, log_e, W, cols, k) <= limit && limit < chunk_budget_bytes(log_n, log_e, W, cols, k + 1), "row %zu: %zu <= %zu < %zu", i,
+           chunk_budget_bytes(log_n, log_e, W, cols, k), limit, chunk_budget_bytes(log_n, log_e, W, cols, k + 1));
+    std::vector<size_t> sizes;
+    for (size_t s0 = 0; s0 < m; s0 += k) sizes.push_back(chunk_size(m, k, s0));
+    EXPECT(sizes == ROUTE_CHUNKS[i] && chunk_count(m, k) == sizes.size(), "row %zu: %zu chunks", i, sizes.size());
+    // the second buffer of the last chunk starts behind a first buffer of ONE instance, not of two
+    EXPECT(chunk_buffer_words(log_n, log_e, cols, sizes.back()) * 2 == chunk_buffer_words(log_n, log_e, cols, k), "row %zu: the smaller last chunk", i);
+  }
+  // what that file's shapes were chosen for.  (f) blinded rows of 514 and 515 coefficients end inside the third tile of eight, and the status
+  // reads 506 coefficients from 1542 on: two tiles, the first lane not at a multiple of 256
+  EXPECT(tiles(9, 2) == 8 && degree_ok(9, 2, 3, 514, 515) && tail_first(9, 3, 514, 515) == 1542 && tail_first(9, 3, 514, 515) % PQ_BLOCK == 6, "(f)");
+  EXPECT(tail_len(9, 2, 3, 514, 515) == 506 && tail_tiles(tail_len(9, 2, 3, 514, 515)) == 2 && 2 * PQ_BLOCK < 514 && 515 < 3 * PQ_BLOCK, "(f)");
+  // (g) W = 17 needs E = 32 at n = 16; two tiles.  W = 2 over E = 8 at n = 32: one tile
+  EXPECT(degree_ok(4, 5, 17, 18, 19) && !degree_ok(4, 4, 17, 18, 19) && tiles(4, 5) == 2 && tail_first(4, 17, 18, 19) == 292 && degree_ok(5, 3, 2, 34, 35) && tiles(5, 3) == 1, "(g)");
+  // (h) one row, constants: t has two coefficients and the status reads the other two; 300 instances are 1800 constants, 8 blocks of lanes
+  EXPECT(degree_ok(0, 2, 2, 1, 1) && tail_first(0, 2, 1, 1) == 2 && tail_len(0, 2, 2, 1, 1) == 2 && tail_tiles(300 * const_slots(2)) == 8 && tail_tiles(300) == 2, "(h)");
+  // the rule by hand at (3, E = 4, W = 3): 35000 bytes hold two instances and not three with either column count
+  EXPECT(chunk_budget_bytes(3, 2, 3, 5, 2) == 32256 && chunk_budget_bytes(3, 2, 3, 4, 3) == 38624 && instances_per_chunk(3, 2, 3, 4, 5, 35000) == 2 &&
+             instances_per_chunk(3, 2, 3, 5, 5, 35000) == 2,
+         "two and not three");
+}
+
 int main() {
+  limits_of_the_route_tests();
   constants_and_pins();
   table_layout();
   items_and_tail_tiles();
