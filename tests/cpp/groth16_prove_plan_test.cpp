@@ -7,6 +7,7 @@
 
 #include <cstdint>
 #include <cstdio>
+#include <vector>
 
 using namespace g16_plan;
 static int fails = 0;
@@ -59,7 +60,38 @@ static void prove_chunks() {
   EXPECT(prove_budget_bytes(28, SIZE_MAX / 2, 0, 3) == SIZE_MAX && witnesses_per_chunk(28, SIZE_MAX / 2, 0, 3, SIZE_MAX - 1) == 0, "a saturated witness never fits");
 }
 
+// The scratch limits of tests/test_gpu_groth16_prove_routes.py: (log_n, n_vars, n_inputs, m, the limit in bytes, the witnesses of a full chunk
+// under it).  tests/test_groth16_prove_route_limits.py reads these rows and compares them with the GPU file's.
+static const size_t ROUTE_LIMITS[][6] = {
+    {3, 7, 2, 7, 16000, 3},                      // a_three
+    {3, 7, 2, 7, 12000, 2},                      // a_two
+    {3, 7, 2, 513, 1350000, 257},                // b_257
+    {3, 65539, 2, 2, 6000000, 1},                // f_one
+};
+static const std::vector<size_t> ROUTE_CHUNKS[] = {{3, 3, 1}, {2, 2, 2, 1}, {257, 256}, {1, 1}};
+static void limits_of_the_route_tests() {
+  static_assert(sizeof(ROUTE_LIMITS) / sizeof(ROUTE_LIMITS[0]) == sizeof(ROUTE_CHUNKS) / sizeof(ROUTE_CHUNKS[0]), "a chunk sequence per limit");
+  for (size_t i = 0; i < sizeof(ROUTE_LIMITS) / sizeof(ROUTE_LIMITS[0]); ++i) {
+    const size_t* r = ROUTE_LIMITS[i];
+    const int32_t log_n = (int32_t)r[0];
+    const size_t n_vars = r[1], l = r[2], m = r[3], limit = r[4], mc = r[5];
+    EXPECT(log_n_ok(log_n) && l < n_vars, "row %zu: the entry point takes the shape", i);
+    EXPECT(witnesses_per_chunk(log_n, n_vars, l, m, limit) == mc, "row %zu: %zu", i, witnesses_per_chunk(log_n, n_vars, l, m, limit));
+    EXPECT(mc >= 1 && mc < m && prove_budget_bytes(log_n, n_vars, l, mc) <= limit && limit < prove_budget_bytes(log_n, n_vars, l, mc + 1), "row %zu: %zu <= %zu < %zu", i,
+           prove_budget_bytes(log_n, n_vars, l, mc), limit, prove_budget_bytes(log_n, n_vars, l, mc + 1));
+    std::vector<size_t> sizes;                   // the loop of sylow_hip_groth16_prove_batch
+    for (size_t j0 = 0; j0 < m; j0 += mc) sizes.push_back(m - j0 < mc ? m - j0 : mc);
+    EXPECT(sizes == ROUTE_CHUNKS[i], "row %zu: %zu chunks", i, sizes.size());
+  }
+  // the rule by hand at the first shape: a witness leases 4512 bytes of its own (above) and the transform of its three arrays 8 (4 + 16 + 96)
+  // more; what a second and a third add differs by the flags' rounding to a word only
+  EXPECT(prove_budget_bytes(3, 7, 2, 3) == 15928 && prove_budget_bytes(3, 7, 2, 4) == 21168 && prove_budget_bytes(3, 7, 2, 257) == 1347904, "n = 8");
+  // 2^16 + 3 variables: the witness and its private part are all but 5 KB of a chunk
+  EXPECT(prove_budget_bytes(3, 65539, 2, 1) == 4199488 && prove_budget_bytes(3, 65539, 2, 2) == 8398776 && 32 * (65539 + 65536) == 4194400, "n_vars = 2^16 + 3");
+}
+
 int main() {
+  limits_of_the_route_tests();
   spmv_geometry();
   quotient_scratch();
   prove_chunks();

@@ -187,6 +187,56 @@ class Setup:
         return (a * b - self.alpha * self.beta - vk_x * self.gamma - c * self.delta) % R == 0
 
 
+def free_key(ct, seed):
+    """a Setup whose query logarithms u, v, lq, hq are independent random values in Fr for every index.  The prover never checks a key against
+    its circuit, so proof_dlogs is still "the formulas' points" -- at any number of variables, without the Lagrange sums; ic keeps the
+    circuit's values, so `verifies` means nothing under such a key"""
+    st = Setup(ct, seed)
+    rng = random.Random(seed * 0x9E3779B1 + 1)
+    st.u, st.v = ([rng.randrange(R) for _ in range(ct.n_vars)] for _ in range(2))
+    st.lq = [rng.randrange(R) for _ in range(ct.n_vars - ct.l - 1)]
+    st.hq = [rng.randrange(R) for _ in range(ct.n - 1)]
+    return st
+
+
+def zero_witness(ct):
+    """zero but for z_0 = 1: every sum of the proof is empty (make_circuit keeps column 0 out of A and C)"""
+    return [1] + [0] * (ct.n_vars - 1)
+
+
+def witness_mix(ct, z, m, seed, zero_rows=()):
+    """m witnesses, each one of: z; the zero witness; a vector of random 256-bit words with z_0 = 1 (unsatisfied: its proof is the one by
+    the definition on the coset).  Adjacent rows never hold the same witness, so no two neighbouring rows share a proof; the rows in
+    zero_rows hold the zero witness."""
+    rng = random.Random(seed)
+    kinds = []
+    for j in range(m):
+        near = {kinds[j - 1]} if j else set()
+        if j + 1 in zero_rows:
+            near.add(1)
+        kinds.append(1 if j in zero_rows else rng.choice([k for k in (0, 1, 2) if k == 2 or k not in near]))
+    assert not any(j in zero_rows and j + 1 in zero_rows for j in range(m)), "two planted rows side by side would share a witness"
+    out = [list(z) if k == 0 else zero_witness(ct) if k == 1 else [1] + [rng.randrange(1 << 256) for _ in range(ct.n_vars - 1)] for k in kinds]
+    assert all(out[j] != out[j + 1] for j in range(m - 1))
+    return out
+
+
+def planted_randomness(st, what, rng):
+    """(r, s) under which the point `what` ("A", "B" or "C") of the ZERO witness's proof is the identity.  With z = (1, 0, ...) the sums
+    leave A = a0 + r delta, B = b0 + s delta and C = s A + r B - r s delta = s (a0 + r delta) + r b0, a0 = alpha + u_0, b0 = beta + v_0:
+    A = 0 at r = -a0 / delta, B = 0 at s = -b0 / delta, C = 0 at s = -r b0 / (a0 + r delta) for any r that leaves A != 0"""
+    a0, b0 = (st.alpha + st.query("a_query")[0]) % R, (st.beta + st.query("b_g1_query")[0]) % R
+    assert st.query("b_g2_query")[0] == st.query("b_g1_query")[0]
+    if what == "A":
+        return -a0 * inv(st.delta) % R, rng.randrange(1, R)
+    if what == "B":
+        return rng.randrange(1, R), -b0 * inv(st.delta) % R
+    assert what == "C"
+    r = rng.randrange(1, R)
+    assert (a0 + r * st.delta) % R
+    return r, -r * b0 * inv(a0 + r * st.delta) % R
+
+
 # ---- the same as points (the C oracle's generator multiples) -----------------------------------------------------------------------------
 def key_points(setup, g1_mul=None, g2_mul=None):
     """{name: (affine words, flags)}: the proving key as arrays.  A zero logarithm is the identity, flagged; so is a flagged entry.

@@ -84,3 +84,70 @@ def test_generated_zinv_table_is_what_pow_gives():
         value = sum(int(w[:-3], 16) << (64 * i) for i, w in enumerate(row))
         zh = (pow(5, 1 << k, R) - 1) % R
         assert zh != 0 and value == pow(zh, R - 2, R) == M.zinv(k) and value * zh % R == 1
+
+
+# ---- what tests/test_gpu_groth16_prove_routes.py leans on --------------------------------------------------------------------------------
+def test_a_free_key_s_proof_is_the_formula_written_out():
+    ct, z = M.make_circuit(1, 2, 4, 1, seed=21)
+    st = M.free_key(ct, seed=22)
+    assert len(st.u) == len(st.v) == 4 and len(st.lq) == 2 and len(st.hq) == 1
+    assert len(set(st.u + st.v + st.lq + st.hq)) == 11 and st.u != M.Setup(ct, seed=22).u, "independent values, not the circuit's"
+    rng = random.Random(23)
+    w = [1] + [rng.randrange(1 << 256) for _ in range(3)]            # unsatisfied, words past r
+    r, s = rng.randrange(R), rng.randrange(R)
+    a, b, c = st.proof_dlogs(w, r, s)
+    h = M.quotient_coset(M.matvec(ct.a, [x % R for x in w], 2), M.matvec(ct.b, [x % R for x in w], 2), M.matvec(ct.c, [x % R for x in w], 2), 1)
+    wa = (st.alpha + st.u[0] * w[0] + st.u[1] * w[1] + st.u[2] * w[2] + st.u[3] * w[3] + r * st.delta) % R
+    wb = (st.beta + st.v[0] * w[0] + st.v[1] * w[1] + st.v[2] * w[2] + st.v[3] * w[3] + s * st.delta) % R
+    wc = (st.lq[0] * w[2] + st.lq[1] * w[3] + st.hq[0] * h[0] + s * wa + r * wb - r * s * st.delta) % R
+    assert (a, b, c) == (wa, wb, wc)
+
+
+def test_witness_mix_holds_the_three_kinds_and_no_two_neighbours_alike():
+    ct, z = M.make_circuit(3, 8, 7, 2, seed=31, free=2)
+    z0 = M.zero_witness(ct)
+    for m, planted in ((7, ()), (513, (7, 255, 300, 512))):
+        zs = M.witness_mix(ct, z, m, seed=32, zero_rows=planted)
+        assert len(zs) == m and all(len(w) == 7 and w[0] == 1 for w in zs) and all(zs[j] != zs[j + 1] for j in range(m - 1))
+        kinds = [0 if w == z else 1 if w == z0 else 2 for w in zs]
+        assert {0, 1, 2} == set(kinds) and all(kinds[j] == 1 for j in planted)
+        assert all(ct.satisfied([v % R for v in w]) == (k != 2) for w, k in zip(zs, kinds))
+        assert zs == M.witness_mix(ct, z, m, seed=32, zero_rows=planted)
+
+
+def test_planted_randomness_makes_the_zero_witness_s_point_the_identity():
+    ct, z = M.make_circuit(3, 8, 7, 2, seed=41, free=2)
+    z0, rng = M.zero_witness(ct), random.Random(42)
+    for st in (M.Setup(ct, seed=43), M.free_key(ct, seed=44)):
+        assert st.proof_dlogs(z0, 0, 0)[2] == 0 and all(st.proof_dlogs(z0, 0, 0)[:2])
+        for k, what in enumerate("ABC"):
+            proof = st.proof_dlogs(z0, *M.planted_randomness(st, what, rng))
+            assert [v == 0 for v in proof] == [k == j for j in range(3)], what
+    st = M.Setup(ct, seed=43)                                        # under the circuit's own key such a proof still verifies
+    assert all(st.verifies(st.proof_dlogs(z0, *M.planted_randomness(st, what, rng)), z0[1:3]) for what in "ABC")
+
+
+def test_degenerate_circuits_no_private_variable_no_constraint_and_a_short_one():
+    rng = random.Random(51)
+    ct, z = M.make_circuit(2, 3, 4, 3, seed=52, free=0)              # every variable but z_0 is public
+    st = M.Setup(ct, seed=53)
+    assert len(st.lq) == 0 and len(st.ic) == 4 and st.verifies(st.proof_dlogs(z, rng.randrange(R), rng.randrange(R)), z[1:4])
+    for log_n in (0, 1):                                             # no constraint: u = v = 0 and h = 0
+        ct, z = M.make_circuit(log_n, 0, 3, 1, seed=54)
+        st = M.Setup(ct, seed=55)
+        assert ct.n_cons == 0 and not any(st.u) and not any(st.v) and not any(st.lq) and len(st.hq) == (1 << log_n) - 1
+        r, s = rng.randrange(R), rng.randrange(R)
+        a, b, c = st.proof_dlogs(z, r, s)
+        assert a == (st.alpha + r * st.delta) % R and b == (st.beta + s * st.delta) % R and st.verifies((a, b, c), z[1:2])
+    ct, z = M.make_circuit(3, 5, 7, 2, seed=56)                      # three padding rows
+    st = M.Setup(ct, seed=57)
+    assert st.verifies(st.proof_dlogs(z, 1, 2), z[1:3])
+    w = [1] + [rng.randrange(1 << 256) for _ in range(6)]
+    assert not ct.satisfied([v % R for v in w]) and not st.verifies(st.proof_dlogs(w, 1, 2), w[1:3])
+
+
+def test_the_sparse_product_s_accumulator_holds_27_products_and_not_28():
+    """what makes rows of 28 and 29 entries per lane the ones that matter: 16 products between two folds are far inside 512 bits, 28 are not"""
+    top = (R - 1) ** 2
+    assert 27 * top < 1 << 512 <= 28 * top and top % R == 1
+    assert (R - 1) + 16 * top < 1 << 512, "a fold's residue and SPMV_FLUSH products more"
