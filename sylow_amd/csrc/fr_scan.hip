@@ -240,9 +240,10 @@ static int32_t scan(const u64* a, size_t len, size_t m, int exclusive, long long
     LAUNCHED();
   }
   host::Lease ws;
-  int32_t rc = ws.acquire(scan_scratch_bytes(len, m, false), st);
+  const ScanLayout l = scan_layout(len, m, false);
+  int32_t rc = ws.acquire(l.bytes, st);
   if (rc != SYLOW_HIP_OK) return rc;
-  u64* totals = (u64*)ws.p;
+  u64* totals = ws.at<u64>(l.totals);
   k_scan_local<PRODUCT><<<per_item, dim3(BLOCK), 0, st>>>(a, len, n_chunks, its, exclusive, out, totals, nullptr, m);
   upper<PRODUCT>(totals, nullptr, len, m, max_blocks, tile, 0, out, total_out, nullptr, st);
   return host::finish(SYLOW_HIP_OK, ws);
@@ -257,10 +258,11 @@ static int32_t ratio_scan(const u64* num, const u64* den, size_t len, size_t m, 
     LAUNCHED();
   }
   host::Lease ws;
-  int32_t rc = ws.acquire(scan_scratch_bytes(len, m, true), st);
+  const ScanLayout l = scan_layout(len, m, true);
+  int32_t rc = ws.acquire(l.bytes, st);
   if (rc != SYLOW_HIP_OK) return rc;
-  u64* totals = (u64*)ws.p;
-  uint8_t* zflag = (uint8_t*)(totals + totals_words(len, m));
+  u64* totals = ws.at<u64>(l.totals);
+  uint8_t* zflag = ws.at<uint8_t>(l.zflag);
   k_ratio_local<PRODUCT><<<per_item, dim3(BLOCK), 0, st>>>(num, den, len, n_chunks, its, out, totals, zflag, nullptr, nullptr, m, closing);
   upper<PRODUCT>(totals, zflag, len, m, max_blocks, tile, closing, out, total_out, status, st);
   return host::finish(SYLOW_HIP_OK, ws);
@@ -315,7 +317,7 @@ int32_t sylow_hip_plonk_identity_batch(const uint64_t* shifts, int32_t log_n, in
   host::Lease ws;
   int32_t rc = ws.acquire(identity_scratch_bytes(log_n), st);
   if (rc != SYLOW_HIP_OK) return rc;
-  u64* roots = (u64*)ws.p;
+  u64* roots = ws.at<u64>(0);
   if (log_n >= 1) rc = ntth::build_table(log_n, roots, stream);
   if (rc == SYLOW_HIP_OK) {
     const size_t tiles = identity_items(log_n, W);
@@ -339,9 +341,10 @@ int32_t sylow_hip_plonk_permutation_batch_tuned(const uint64_t* wires, const uin
   ARGCHK(host::outputs_disjoint(in, outs, disjoint));
   const hipStream_t st = (hipStream_t)stream;
   host::Lease ws;
-  int32_t rc = ws.acquire(permutation_scratch_bytes(log_n, m), st);
+  const PermutationLayout l = permutation_layout(log_n, m);
+  int32_t rc = ws.acquire(l.bytes, st);
   if (rc != SYLOW_HIP_OK) return rc;
-  u64 *roots = (u64*)ws.p, *num = roots + root_words(log_n), *den = num + terms_words(log_n, m);
+  u64 *roots = ws.at<u64>(l.roots), *num = ws.at<u64>(l.num), *den = ws.at<u64>(l.den);
   if (log_n >= 1) rc = ntth::build_table(log_n, roots, stream);
   if (rc == SYLOW_HIP_OK) {
     const size_t tiles = terms_tiles(log_n), its = terms_items(log_n, m);

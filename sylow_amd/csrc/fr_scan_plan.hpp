@@ -1,5 +1,5 @@
 // fr_scan_plan.hpp -- the geometry of the scans over Fr under + and * and of PLONK's permutation grand product (fr_scan.hip): every size,
-// grid, item, tile, scratch and route decision between an entry point and its kernels, plain C++ so that tests/cpp/fr_scan_plan_test.cpp can
+// grid, item, tile, scratch size and offset, and route decision between an entry point and its kernels, plain C++ so that tests/cpp/fr_scan_plan_test.cpp can
 // compile it with g++ on a box without a GPU.  The launch code asks these functions and decides nothing itself.
 #pragma once
 #include "kzg_evals_plan.hpp"
@@ -7,6 +7,7 @@
 #include "plan_base.hpp"
 
 namespace fr_scan_plan {
+using plan_base::Carve;
 using plan_base::SAT;
 using plan_base::add_sat;
 using plan_base::disjoint;
@@ -77,9 +78,14 @@ constexpr bool scratch_ok(size_t bytes) { return bytes <= SAT / 2; }
 // ---- the scratch of a scan, bytes, saturated: the chunk totals [4][items], which phase 2 turns into the chunk prefixes in place, and for
 // the ratio scan a byte per item (a denominator of the chunk was 0), behind them.  Nothing for rows of one chunk -------------------------
 constexpr size_t totals_words(size_t len, size_t m) { return upper_phases(len) ? mul_sat(FR_WORDS, items(len, m)) : 0; }
-constexpr size_t scan_scratch_bytes(size_t len, size_t m, bool ratio) {
-  return upper_phases(len) ? add_sat(mul_sat(totals_words(len, m), sizeof(uint64_t)), ratio ? items(len, m) : 0) : 0;
+struct ScanLayout { size_t totals, zflag, bytes; };
+constexpr ScanLayout scan_layout(size_t len, size_t m, bool ratio) {
+  Carve c; ScanLayout l{};
+  l.totals = c.words(totals_words(len, m));
+  l.zflag = c.bytes(upper_phases(len) && ratio ? items(len, m) : 0);
+  l.bytes = c.at; return l;
 }
+constexpr size_t scan_scratch_bytes(size_t len, size_t m, bool ratio) { return scan_layout(len, m, ratio).bytes; }
 
 // ---- PLONK: the identity columns k_j w^i and the terms of the grand product.  w^i comes out of the transform's table of n / 2 roots
 // (ntt_plan.hpp: root_words, root_slot, root_negated) by ONE load: no power is formed per element.  A lane owns ONE element of a row, so a
@@ -96,9 +102,15 @@ constexpr size_t wires_bytes(int log_n, int wires, size_t m) { return rows_bytes
 // u64 words of num or of den, [m][4][n]
 constexpr size_t terms_words(int log_n, size_t m) { return mul_sat(mul_sat(FR_WORDS, elems(log_n)), m); }
 // the permutation entry leases the roots, num and den; the ratio scan it ends in leases its own on top
-constexpr size_t permutation_scratch_bytes(int log_n, size_t m) {
-  return mul_sat(add_sat(root_words(log_n), mul_sat(2, terms_words(log_n, m))), sizeof(uint64_t));
+struct PermutationLayout { size_t roots, num, den, bytes; };
+constexpr PermutationLayout permutation_layout(int log_n, size_t m) {
+  Carve c; PermutationLayout l{};
+  l.roots = c.words(root_words(log_n));
+  l.num = c.words(terms_words(log_n, m));
+  l.den = c.words(terms_words(log_n, m));
+  l.bytes = c.at; return l;
 }
+constexpr size_t permutation_scratch_bytes(int log_n, size_t m) { return permutation_layout(log_n, m).bytes; }
 // STATUS of a row: bit 0 a denominator was 0 mod r; bit 1 (the permutation entry alone) the product did not close to 1
 constexpr int STATUS_ZERO_DEN = 1, STATUS_NOT_CLOSED = 2;
 }  // namespace fr_scan_plan

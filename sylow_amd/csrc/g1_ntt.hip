@@ -83,14 +83,14 @@ __global__ void HEAVY_BOUNDS k_g1_ntt_close(const u64* src, const uint8_t* pinf,
 static int32_t transform(const uint64_t* p_xy, const uint8_t* p_inf, int log_n, size_t m, bool inverse, long long max_blocks, uint64_t* out_xy, uint8_t* out_inf,
                          void* stream) {
   const hipStream_t st = (hipStream_t)stream;
-  const size_t bytes = scratch_bytes(log_n, m, inverse, max_blocks);
-  if (bytes > SAT / 2) return host::fail(hipErrorOutOfMemory, "scratch of the G1 transform");
+  const ScratchLayout l = scratch_layout(log_n, m, inverse, max_blocks);
+  if (l.bytes > SAT / 2) return host::fail(hipErrorOutOfMemory, "scratch of the G1 transform");
   host::Lease ws;
-  int32_t rc = ws.acquire(bytes, st);
+  int32_t rc = ws.acquire(l.bytes, st);
   if (rc != SYLOW_HIP_OK) return rc;
-  uint8_t* tables = (uint8_t*)ws.p;
-  u64* twiddles = (u64*)(tables + table_bytes(log_n, m, inverse, max_blocks));
-  u64* buf[2] = {twiddles + twiddle_words(log_n), twiddles + twiddle_words(log_n) + (buffers(log_n) > 1 ? buffer_words(log_n, m) : 0)};
+  uint8_t* tables = ws.at<uint8_t>(l.tables);
+  u64* twiddles = ws.at<u64>(l.twiddles);
+  u64* buf[2] = {ws.at<u64>(l.buf[0]), ws.at<u64>(l.buf[1])};
   const size_t stride = points(log_n, m), total = butterflies(log_n, m);
   if (log_n >= 2) rc = ntth::build_table(log_n, twiddles, stream);
   for (int s = 0; s < stages(log_n) && rc == SYLOW_HIP_OK; ++s) {

@@ -1,10 +1,11 @@
 // g1_ntt_plan.hpp -- the geometry of the radix-2 transform over G1 points (g1_ntt.hip): the butterflies of a stage and their indices, which
-// lane takes which butterfly, the grid cap, the ping-pong between the projective buffers, the window tables and the scratch, plain C++ so that
+// lane takes which butterfly, the grid cap, the ping-pong between the projective buffers, the window tables and the scratch with its offsets, plain C++ so that
 // tests/cpp/g1_ntt_plan_test.cpp can compile it with g++ on a box without a GPU.  The launch code asks these functions and decides nothing itself.
 #pragma once
 #include "ntt_plan.hpp"
 
 namespace g1_ntt_plan {
+using plan_base::Carve;
 using plan_base::SAT;
 using plan_base::add_sat;
 using plan_base::elems;
@@ -94,8 +95,14 @@ constexpr size_t buffer_words(int log_n, size_t m) { return mul_sat(points(log_n
 
 // ---- the scratch of a call, bytes, saturated: the window tables (16-byte loads: first), the twiddle table, the buffers -----------------------------------
 constexpr size_t twiddle_words(int log_n) { return ntt_plan::table_words(log_n); }
-constexpr size_t scratch_bytes(int log_n, size_t m, bool inverse, long long max_blocks) {
-  return add_sat(add_sat(mul_sat(twiddle_words(log_n), sizeof(uint64_t)), mul_sat(mul_sat(buffer_words(log_n, m), (size_t)buffers(log_n)), sizeof(uint64_t))),
-                 table_bytes(log_n, m, inverse, max_blocks));
+struct ScratchLayout { size_t tables, twiddles, buf[2], bytes; };
+constexpr ScratchLayout scratch_layout(int log_n, size_t m, bool inverse, long long max_blocks) {
+  Carve c; ScratchLayout l{};
+  l.tables = c.bytes(table_bytes(log_n, m, inverse, max_blocks));      // a multiple of 1 KB: the words after it stay aligned
+  l.twiddles = c.words(twiddle_words(log_n));
+  l.buf[0] = c.words(buffers(log_n) > 0 ? buffer_words(log_n, m) : 0);
+  l.buf[1] = c.words(buffers(log_n) > 1 ? buffer_words(log_n, m) : 0);
+  l.bytes = c.at; return l;
 }
+constexpr size_t scratch_bytes(int log_n, size_t m, bool inverse, long long max_blocks) { return scratch_layout(log_n, m, inverse, max_blocks).bytes; }
 }  // namespace g1_ntt_plan

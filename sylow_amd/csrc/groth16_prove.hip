@@ -197,25 +197,14 @@ struct Proofs {
 };
 
 // the witnesses j0 .. j0 + mc - 1 in the arrays of one lease
-static int32_t prove_chunk(const Circuit& ct, const Key& pk, const uint64_t* z, const uint64_t* r, const uint64_t* s, size_t m, size_t j0, size_t mc, void* ws,
-                           const Proofs& out, void* stream) {
+static int32_t prove_chunk(const Circuit& ct, const Key& pk, const uint64_t* z, const uint64_t* r, const uint64_t* s, size_t m, size_t j0, size_t mc,
+                           const host::Lease& ws, const Proofs& out, void* stream) {
   const hipStream_t st = (hipStream_t)stream;
   const size_t n = elems(ct.log_n), nv = ct.n_vars, nl = private_vars(nv, ct.n_inputs), nh = n - 1;
-  u64* zc = (u64*)ws;
-  u64* zl = zc + batch_words(nv, mc);
-  u64* g = zl + batch_words(nl, mc);
-  u64* x = g + QUOT_CONST_WORDS;
-  u64* y = x + quot_buffer_words(ct.log_n, mc);
-  u64* hq = y + quot_buffer_words(ct.log_n, mc);
-  u64* raw1 = hq + batch_words(nh, mc);
-  u64* raw2 = raw1 + 8 * CLOSE_RAW_G1 * mc;
-  u64* p = raw2 + 16 * CLOSE_RAW_G2 * mc;
-  u64* q = p + 8 * CLOSE_G1 * mc;
-  u64* f = q + 16 * CLOSE_G2 * mc;
-  uint8_t* raw1_inf = (uint8_t*)(f + 4 * CLOSE_FR * mc);
-  uint8_t* raw2_inf = raw1_inf + CLOSE_RAW_G1 * mc;
-  uint8_t* p_inf = raw2_inf + CLOSE_RAW_G2 * mc;
-  uint8_t* q_inf = p_inf + CLOSE_G1 * mc;
+  const ProveLayout l = prove_layout(ct.log_n, nv, ct.n_inputs, mc);      // of THIS chunk: a short last one sits at the front of the lease
+  u64 *zc = ws.at<u64>(l.zc), *zl = ws.at<u64>(l.zl), *g = ws.at<u64>(l.quot.g), *x = ws.at<u64>(l.quot.x), *y = ws.at<u64>(l.quot.y), *hq = ws.at<u64>(l.hq);
+  u64 *raw1 = ws.at<u64>(l.raw1), *raw2 = ws.at<u64>(l.raw2), *p = ws.at<u64>(l.p), *q = ws.at<u64>(l.q), *f = ws.at<u64>(l.f);
+  uint8_t *raw1_inf = ws.at<uint8_t>(l.raw1_inf), *raw2_inf = ws.at<uint8_t>(l.raw2_inf), *p_inf = ws.at<uint8_t>(l.p_inf), *q_inf = ws.at<uint8_t>(l.q_inf);
 
   // 1. the witnesses mod r -- the vectors of the sparse products AND the scalars of the sums (below r, so below p: Fp::new leaves them alone)
   k_fr_canon<<<dim3(lane_grid(nv * mc)), dim3(BLOCK), 0, st>>>(z + j0 * 4 * nv, zc, nv, nv * mc);
@@ -283,10 +272,11 @@ int32_t sylow_hip_fr_spmv_batch_tuned(const uint64_t* row_ptr, const uint64_t* c
   ARGCHK(mul_sat(batch_words(n_out, m), 8) != SAT && mul_sat(batch_words(n_cols, m), 8) != SAT && mul_sat(nnz, 32) != SAT && rows != SAT);
   const hipStream_t st = (hipStream_t)stream;
   host::Lease ws;
-  int32_t rc = ws.acquire(spmv_scratch_words(n_cols, m) * sizeof(u64), st);
+  int32_t rc = ws.acquire(spmv_scratch_bytes(n_cols, m), st);
   if (rc != SYLOW_HIP_OK) return rc;
-  if (n_cols) g16p::k_fr_canon<<<dim3(g16p::lane_grid(n_cols * m)), dim3(BLOCK), 0, st>>>(w, (u64*)ws.p, n_cols, n_cols * m);
-  g16p::spmv_launch(row_ptr, col, val, rows, nnz, (const u64*)ws.p, n_cols, m, n_out, spmv_lanes_log_or_default(lanes_log, rows, nnz), out, st);
+  u64* wc = ws.at<u64>(0);
+  if (n_cols) g16p::k_fr_canon<<<dim3(g16p::lane_grid(n_cols * m)), dim3(BLOCK), 0, st>>>(w, wc, n_cols, n_cols * m);
+  g16p::spmv_launch(row_ptr, col, val, rows, nnz, wc, n_cols, m, n_out, spmv_lanes_log_or_default(lanes_log, rows, nnz), out, st);
   return host::finish(SYLOW_HIP_OK, ws);
 }
 int32_t sylow_hip_fr_spmv_batch(const uint64_t* row_ptr, const uint64_t* col, const uint64_t* val, size_t rows, size_t nnz, const uint64_t* w, size_t n_cols,
@@ -298,13 +288,14 @@ int32_t sylow_hip_groth16_quotient_batch(const uint64_t* a, const uint64_t* b, c
   ARGCHK(log_n_ok(log_n));
   if (!m) return SYLOW_HIP_OK;
   ARGCHK(a && b && c && h_out);
-  const size_t bytes = mul_sat(quot_scratch_words(log_n, m), sizeof(u64)), one = batch_words(elems(log_n), m);
+  const QuotLayout l = quot_layout(log_n, m);
+  const size_t bytes = l.bytes, one = batch_words(elems(log_n), m);
   ARGCHK(bytes != SAT);
   const hipStream_t st = (hipStream_t)stream;
   host::Lease ws;
   int32_t rc = ws.acquire(bytes, st);
   if (rc != SYLOW_HIP_OK) return rc;
-  u64 *g = (u64*)ws.p, *x = g + QUOT_CONST_WORDS, *y = x + quot_buffer_words(log_n, m);
+  u64 *g = ws.at<u64>(l.g), *x = ws.at<u64>(l.x), *y = ws.at<u64>(l.y);
   const uint64_t* src[3] = {a, b, c};
   for (int k = 0; k < 3 && rc == SYLOW_HIP_OK; ++k) {
     const hipError_t e = hipMemcpyAsync(x + (size_t)k * one, src[k], one * sizeof(u64), hipMemcpyDeviceToDevice, st);
@@ -342,7 +333,7 @@ int32_t sylow_hip_groth16_prove_batch(const uint64_t* a_row_ptr, const uint64_t*
   host::Lease ws;
   int32_t rc = ws.acquire(prove_chunk_bytes(log_n, n_vars, n_inputs, mc), (hipStream_t)stream);
   if (rc != SYLOW_HIP_OK) return rc;
-  for (size_t j0 = 0; j0 < m && rc == SYLOW_HIP_OK; j0 += mc) rc = g16p::prove_chunk(ct, pk, z, r, s, m, j0, m - j0 < mc ? m - j0 : mc, ws.p, out, stream);
+  for (size_t j0 = 0; j0 < m && rc == SYLOW_HIP_OK; j0 += mc) rc = g16p::prove_chunk(ct, pk, z, r, s, m, j0, m - j0 < mc ? m - j0 : mc, ws, out, stream);
   return host::finish(rc, ws);
 }
 }  // extern "C"

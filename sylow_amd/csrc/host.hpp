@@ -30,6 +30,7 @@ struct Lease {
   hipStream_t st = nullptr;
   int32_t acquire(size_t bytes, hipStream_t stream);
   int32_t release();                 // records the block's completion event on the stream; idempotent
+  template <class T> T* at(size_t off) const { return (T*)((char*)p + off); }     // the region at a byte offset of the unit's layout (plan_base::Carve)
   ~Lease() { release(); }
 };
 // The one way to end an entry point that holds leases and has launched kernels.  Reads the sticky launch error and releases every lease, in

@@ -241,10 +241,11 @@ static int32_t fold(const uint64_t* idx, const uint64_t* com_idx, const uint64_t
   const hipStream_t st = (hipStream_t)stream;
   const size_t nk = n_keys(route, log_c, n_com), ne = entries(route, rows), l = elems(log_l), c = elems(log_c);
   host::Lease ws;
-  int32_t rc = ws.acquire(fold_scratch_bytes(route, log_c, log_l, rows, n_com), st);
+  const FoldLayout lay = fold_layout(route, log_c, log_l, rows, n_com);
+  int32_t rc = ws.acquire(lay.bytes, st);
   if (rc != SYLOW_HIP_OK) return rc;
-  u64 *roots = (u64*)ws.p, *keys = roots + root_words(log_c), *perm = keys + ne, *cnt = perm + ne, *start = cnt + nk, *next = start + nk + 1, *wpart = next + nk;
-  u64* body = wpart + partial_words(n_com, 0, mac_slices(n_com, 0, rows));
+  u64 *roots = ws.at<u64>(lay.roots), *keys = ws.at<u64>(lay.keys), *perm = ws.at<u64>(lay.perm), *cnt = ws.at<u64>(lay.cnt), *start = ws.at<u64>(lay.start),
+      *next = ws.at<u64>(lay.next), *wpart = ws.at<u64>(lay.wpart), *body = ws.at<u64>(lay.body);
   if (hipMemsetAsync(in_range_out, 1, 1, st) != hipSuccess) rc = host::fail(hipGetLastError(), "setting the range flag");
   if (rc == SYLOW_HIP_OK && nk && hipMemsetAsync(cnt, 0, nk * sizeof(u64), st) != hipSuccess) rc = host::fail(hipGetLastError(), "clearing the counts");
   if (rc == SYLOW_HIP_OK && log_c >= 1) rc = ntth::build_table(log_c, roots, stream);
@@ -255,7 +256,7 @@ static int32_t fold(const uint64_t* idx, const uint64_t* com_idx, const uint64_t
   k_cells_scatter<<<dim3((unsigned)scatter_grid(route, rows, max_blocks)), dim3(BLOCK), 0, st>>>(keys, ne, nk, route, rows, next, perm);
   if (n_com) mac<false>(nullptr, r_out, perm, start + cell_keys(route, log_c), n_com, 0, rows, max_blocks, wpart, w_out, w_key_stride(), w_word_stride(n_com), st);
   if (route == ROUTE_COLUMNS) {
-    u64 *S = body, *a = S + array_words(log_c, log_l), *spart = a + array_words(log_c, log_l);
+    u64 *S = body, *a = ws.at<u64>(lay.a), *spart = ws.at<u64>(lay.spart);
     mac<true>(vals, r_out, perm, start, c, log_l, rows, max_blocks, spart, S, s_key_stride(log_l), s_word_stride(log_l), st);
     rc = sylow_hip_fr_ntt_batch(S, log_l, c, /*inverse=*/1, nullptr, a, stream);
     if (rc == SYLOW_HIP_OK)
@@ -319,11 +320,12 @@ int32_t sylow_hip_kzg_cells_reduce_batch(const uint64_t* srs_g1_xy, const uint64
   const hipStream_t st = (hipStream_t)stream;
   const size_t l = elems(log_l), total = terms(rows, n_com);
   host::Lease ws;
-  int32_t rc = ws.acquire(reduce_scratch_bytes(log_l, rows, n_com), st);
+  const ReduceLayout lay = reduce_layout(log_l, rows, n_com);
+  int32_t rc = ws.acquire(lay.bytes, st);
   if (rc != SYLOW_HIP_OK) return rc;
-  u64 *w = (u64*)ws.p, *a = w + FR_WORDS * n_com, *r = a + FR_WORDS * l, *rz = r + FR_WORDS * rows, *sc = rz + FR_WORDS * rows, *bases = sc + FR_WORDS * total,
-      *m1 = bases + G1_WORDS * total, *at = m1 + G1_WORDS;
-  uint8_t *binf = (uint8_t*)(at + G1_WORDS), *m1inf = binf + total, *atinf = m1inf + 1;
+  u64 *w = ws.at<u64>(lay.w), *a = ws.at<u64>(lay.a), *r = ws.at<u64>(lay.r), *rz = ws.at<u64>(lay.rz), *sc = ws.at<u64>(lay.sc), *bases = ws.at<u64>(lay.bases),
+      *m1 = ws.at<u64>(lay.m1), *at = ws.at<u64>(lay.at);
+  uint8_t *binf = ws.at<uint8_t>(lay.binf), *m1inf = ws.at<uint8_t>(lay.m1inf), *atinf = ws.at<uint8_t>(lay.atinf);
   rc = sylow_hip_kzg_cells_fold_batch(idx, com_idx, vals, weights, log_c, log_l, rows, n_com, w, a, r, rz, in_range_out, stream);
   if (rc == SYLOW_HIP_OK && total)
     kzce::k_cells_concat<<<dim3((unsigned)grid(blocks_of(total), -1)), dim3(BLOCK), 0, st>>>(w, c_xy, c_inf, rz, pi_xy, pi_inf, n_com, rows, sc, bases, binf);
@@ -350,10 +352,12 @@ int32_t sylow_hip_kzg_cells_verify_weighted(const uint64_t* srs_g1_xy, const uin
   ARGCHK(host::outputs_disjoint(in, out, disjoint_or_empty));
   const hipStream_t st = (hipStream_t)stream;
   host::Lease ws;
-  int32_t rc = ws.acquire(verify_scratch_bytes(), st);
+  const VerifyLayout lay = verify_layout();
+  int32_t rc = ws.acquire(lay.bytes, st);
   if (rc != SYLOW_HIP_OK) return rc;
-  u64 *f = (u64*)ws.p, *p = f + G1_WORDS, *pxy = p + G1_WORDS, *qxy = pxy + 2 * G1_WORDS;
-  uint8_t *finf = (uint8_t*)(qxy + 2 * G2_WORDS), *pinf_one = finf + 1, *pinf = pinf_one + 1, *qinf = pinf + 2, *flag = qinf + 2, *one = flag + 1;
+  u64 *f = ws.at<u64>(lay.f), *p = ws.at<u64>(lay.p), *pxy = ws.at<u64>(lay.pxy), *qxy = ws.at<u64>(lay.qxy);
+  uint8_t *finf = ws.at<uint8_t>(lay.finf), *pinf_one = ws.at<uint8_t>(lay.pinf_one), *pinf = ws.at<uint8_t>(lay.pinf), *qinf = ws.at<uint8_t>(lay.qinf),
+          *flag = ws.at<uint8_t>(lay.flag), *one = ws.at<uint8_t>(lay.one);
   rc = sylow_hip_kzg_cells_reduce_batch(srs_g1_xy, c_xy, c_inf, idx, com_idx, vals, pi_xy, pi_inf, weights, log_c, log_l, rows, n_com, f, finf, p, pinf_one, flag, stream);
   if (rc == SYLOW_HIP_OK) {
     kzce::k_cells_pairs<<<1, 64, 0, st>>>(f, finf, p, pinf_one, tau_l_g2_xy, pxy, pinf, qxy, qinf);

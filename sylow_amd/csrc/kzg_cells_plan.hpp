@@ -1,18 +1,20 @@
 // kzg_cells_plan.hpp -- the geometry of the check of many cells of many KZG blobs as one boolean (kzg_cells.hip): rows of (cell index < c,
 // commitment index < n_com, l values, weight), c = 2^log_c cells of l = 2^log_l points.  The route, the keys and their grouping, the keyed
-// multiply-accumulate with its teams, staging and slices, the Horner fold with its chunks, the grids and the scratch, plain C++ so that
+// multiply-accumulate with its teams, staging and slices, the Horner fold with its chunks, the grids and the scratch with its offsets, plain C++ so that
 // tests/cpp/kzg_cells_plan_test.cpp can compile it with g++ on a box without a GPU.  The launch code asks these functions and decides
 // nothing itself.
 #pragma once
 #include "ntt_plan.hpp"
 
 namespace kzg_cells_plan {
+using plan_base::Carve;
 using plan_base::SAT;
 using plan_base::add_sat;
 using plan_base::disjoint_or_empty;      // an empty array of the caller overlaps nothing here
 using plan_base::elems;
 using plan_base::max_blocks_ok;
 using plan_base::mul_sat;
+using plan_base::words_of;
 using ntt_plan::root_negated;
 using ntt_plan::root_slot;
 using ntt_plan::root_words;
@@ -125,35 +127,66 @@ constexpr uint64_t horner_join_exp(size_t t, size_t q, int log_c, int log_l) {
 constexpr size_t horner_grid(int log_c, int log_l, long long max_blocks) { return grid(blocks_of(horner_items(log_c, log_l)), max_blocks); }
 static_assert((1 << HORNER_LANES_LOG) <= CELLS_WAVE, "the lanes of a t share a wave");
 
-// ---- the scratch of the fold, u64 words, saturated: the roots; the keys of the entries; counts, starts (one more) and cursors of the
+// ---- the scratch of the fold, saturated: the roots; the keys of the entries; counts, starts (one more) and cursors of the
 // keys; the permutation; the partial sums of W; then by columns S and its transform [c][4][l] with the partials of S, by rows the
 // interpolants [rows][4][l].  The calls of the library the fold makes lease their own on top.
-constexpr size_t group_words(int route, int log_c, size_t rows, size_t n_com) {
-  return add_sat(mul_sat(entries(route, rows), 2), add_sat(mul_sat(n_keys(route, log_c, n_com), 3), 1));
-}
 constexpr size_t array_words(int log_c, int log_l) { return FR_WORDS << log_n(log_c, log_l); }
-constexpr size_t route_words(int route, int log_c, int log_l, size_t rows) {
-  return route == ROUTE_COLUMNS ? add_sat(mul_sat(array_words(log_c, log_l), 2), partial_words(elems(log_c), log_l, mac_slices(elems(log_c), log_l, rows)))
-                                : mul_sat(mul_sat(elems(log_l), rows), FR_WORDS);
+struct FoldLayout { size_t roots, keys, perm, cnt, start, next, wpart, body, a, spart, bytes; };      // body: S by columns, the interpolants by rows
+constexpr FoldLayout fold_layout(int route, int log_c, int log_l, size_t rows, size_t n_com) {
+  const bool cols = route == ROUTE_COLUMNS;
+  Carve c; FoldLayout l{};
+  l.roots = c.words(root_words(log_c));
+  l.keys = c.words(entries(route, rows));
+  l.perm = c.words(entries(route, rows));
+  l.cnt = c.words(n_keys(route, log_c, n_com));
+  l.start = c.words(add_sat(n_keys(route, log_c, n_com), 1));
+  l.next = c.words(n_keys(route, log_c, n_com));
+  l.wpart = c.words(partial_words(n_com, 0, mac_slices(n_com, 0, rows)));
+  l.body = c.words(cols ? array_words(log_c, log_l) : mul_sat(mul_sat(elems(log_l), rows), FR_WORDS));
+  l.a = c.words(cols ? array_words(log_c, log_l) : 0);
+  l.spart = c.words(cols ? partial_words(elems(log_c), log_l, mac_slices(elems(log_c), log_l, rows)) : 0);
+  l.bytes = c.at; return l;
 }
-constexpr size_t fold_scratch_words(int route, int log_c, int log_l, size_t rows, size_t n_com) {
-  return add_sat(add_sat(root_words(log_c), group_words(route, log_c, rows, n_com)),
-                 add_sat(partial_words(n_com, 0, mac_slices(n_com, 0, rows)), route_words(route, log_c, log_l, rows)));
-}
-constexpr size_t fold_scratch_bytes(int route, int log_c, int log_l, size_t rows, size_t n_com) {
-  return mul_sat(fold_scratch_words(route, log_c, log_l, rows, n_com), sizeof(uint64_t));
-}
+constexpr size_t fold_scratch_bytes(int route, int log_c, int log_l, size_t rows, size_t n_com) { return fold_layout(route, log_c, log_l, rows, n_com).bytes; }
+constexpr size_t fold_scratch_words(int route, int log_c, int log_l, size_t rows, size_t n_com) { return words_of(fold_scratch_bytes(route, log_c, log_l, rows, n_com)); }
 // of the reduction: W, A, r, r z; the n_com + rows scalars and bases of the first multi-scalar multiplication; its sum and A(tau) G1gen;
-// then the flags of the bases and of the two points.  Of the weighted check: F and P, the two pairs, and six flag bytes in one word.
+// then the flags of the bases and of the two points, the latter in 8 bytes of which 2 are used.  Of the weighted check: F and P, the two
+// pairs, and eight flag bytes in one word.
 constexpr size_t terms(size_t rows, size_t n_com) { return add_sat(rows, n_com); }
-constexpr size_t reduce_scratch_words(int log_l, size_t rows, size_t n_com) {
-  return add_sat(add_sat(mul_sat(add_sat(n_com, elems(log_l)), FR_WORDS), mul_sat(rows, 2 * FR_WORDS)),
-                 add_sat(mul_sat(terms(rows, n_com), FR_WORDS + G1_WORDS), 2 * G1_WORDS));
+struct ReduceLayout { size_t w, a, r, rz, sc, bases, m1, at, binf, m1inf, atinf, bytes; };
+constexpr ReduceLayout reduce_layout(int log_l, size_t rows, size_t n_com) {
+  Carve c; ReduceLayout l{};
+  l.w = c.words(mul_sat(FR_WORDS, n_com));
+  l.a = c.words(mul_sat(FR_WORDS, elems(log_l)));
+  l.r = c.words(mul_sat(FR_WORDS, rows));
+  l.rz = c.words(mul_sat(FR_WORDS, rows));
+  l.sc = c.words(mul_sat(FR_WORDS, terms(rows, n_com)));
+  l.bases = c.words(mul_sat(G1_WORDS, terms(rows, n_com)));
+  l.m1 = c.words(G1_WORDS);
+  l.at = c.words(G1_WORDS);
+  l.binf = c.bytes(terms(rows, n_com));
+  l.m1inf = c.bytes(1);
+  l.atinf = c.bytes(1);
+  c.bytes(6);
+  l.bytes = c.at; return l;
 }
-constexpr size_t reduce_scratch_bytes(int log_l, size_t rows, size_t n_com) {
-  return add_sat(mul_sat(reduce_scratch_words(log_l, rows, n_com), sizeof(uint64_t)), add_sat(terms(rows, n_com), 8));
+constexpr size_t reduce_scratch_bytes(int log_l, size_t rows, size_t n_com) { return reduce_layout(log_l, rows, n_com).bytes; }
+constexpr size_t reduce_scratch_words(int log_l, size_t rows, size_t n_com) { return words_of(reduce_layout(log_l, rows, n_com).binf); }      // before the flags
+struct VerifyLayout { size_t f, p, pxy, qxy, finf, pinf_one, pinf, qinf, flag, one, bytes; };
+constexpr VerifyLayout verify_layout() {
+  Carve c; VerifyLayout l{};
+  l.f = c.words(G1_WORDS);
+  l.p = c.words(G1_WORDS);
+  l.pxy = c.words(2 * G1_WORDS);
+  l.qxy = c.words(2 * G2_WORDS);
+  l.finf = c.bytes(1);
+  l.pinf_one = c.bytes(1);
+  l.pinf = c.bytes(2);
+  l.qinf = c.bytes(2);
+  l.flag = c.bytes(1);
+  l.one = c.bytes(1);
+  l.bytes = c.at; return l;
 }
-constexpr size_t verify_scratch_words() { return 2 * G1_WORDS + 2 * G1_WORDS + 2 * G2_WORDS + 1; }
-constexpr size_t verify_scratch_bytes() { return verify_scratch_words() * sizeof(uint64_t); }
+constexpr size_t verify_scratch_bytes() { return verify_layout().bytes; }
 constexpr bool scratch_ok(size_t bytes) { return bytes <= SAT / 2; }
 }  // namespace kzg_cells_plan

@@ -157,8 +157,8 @@ __global__ void __launch_bounds__(BLOCK) k_coset_flags(uint8_t* ok, const uint8_
 static int32_t open_cosets(const uint64_t* txy, const uint8_t* tinf, const uint64_t* coeffs, int log_c, int log_l, size_t m, long long max_blocks, int pl,
                            uint64_t* y_out, uint64_t* pi_xy, uint8_t* pi_inf, void* stream) {
   const hipStream_t st = (hipStream_t)stream;
-  const size_t bytes = scratch_bytes(log_c, log_l, m, pl, max_blocks);
-  if (bytes > SAT / 2) return host::fail(hipErrorOutOfMemory, "scratch of the proofs on every coset");
+  const ScratchLayout l = scratch_layout(log_c, log_l, m, pl, max_blocks);
+  if (l.bytes > SAT / 2) return host::fail(hipErrorOutOfMemory, "scratch of the proofs on every coset");
   int32_t rc = y_out ? sylow_hip_fr_ntt_batch(coeffs, log_n(log_c, log_l), m, /*inverse=*/0, nullptr, y_out, stream) : SYLOW_HIP_OK;
   if (rc != SYLOW_HIP_OK) return rc;
   if (trivial(log_c)) {
@@ -166,12 +166,12 @@ static int32_t open_cosets(const uint64_t* txy, const uint8_t* tinf, const uint6
     LAUNCHED();
   }
   host::Lease ws;
-  rc = ws.acquire(bytes, st);
+  rc = ws.acquire(l.bytes, st);
   if (rc != SYLOW_HIP_OK) return rc;
-  uint8_t* tables = (uint8_t*)ws.p;
-  u64 *tw_wide = (u64*)(tables + table_bytes(log_c, m, pl, max_blocks)), *tw = tw_wide + oa::wide_twiddle_words(log_c);
-  u64* buf[2] = {tw + oa::twiddle_words(log_c), tw + oa::twiddle_words(log_c) + oa::buffer_words(log_c, m)};
-  u64 *planes = buf[1] + oa::buffer_words(log_c, m), *padded = planes + plane_words(log_c, m, pl), *f = padded + split_words(log_c, log_l, m);
+  uint8_t* tables = ws.at<uint8_t>(l.tables);
+  u64 *tw_wide = ws.at<u64>(l.tw_wide), *tw = ws.at<u64>(l.tw);
+  u64* buf[2] = {ws.at<u64>(l.buf[0]), ws.at<u64>(l.buf[1])};
+  u64 *planes = ws.at<u64>(l.planes), *padded = ws.at<u64>(l.padded), *f = ws.at<u64>(l.f);
   const size_t str = stride(log_c, m);
   const int L = wide_log(log_c);
   const ntt_plan::Words4 ni = ntt_plan::n_inverse(L);
@@ -211,11 +211,12 @@ int32_t sylow_hip_kzg_open_cosets_prepare(const uint64_t* srs_g1_xy, int32_t log
   ARGCHK(logs_ok(log_c, log_l));
   ARGCHK(srs_g1_xy && table_xy && table_inf);
   ARGCHK(prepare_scratch_bytes(log_c, log_l) != SAT);
+  const PrepareLayout l = prepare_layout(log_c, log_l);
   host::Lease ws;
-  int32_t rc = ws.acquire(prepare_scratch_bytes(log_c, log_l), (hipStream_t)stream);
+  int32_t rc = ws.acquire(l.bytes, (hipStream_t)stream);
   if (rc != SYLOW_HIP_OK) return rc;
-  u64* xy = (u64*)ws.p;
-  uint8_t* inf = (uint8_t*)ws.p + table_xy_bytes(log_c, log_l);
+  u64* xy = ws.at<u64>(l.xy);
+  uint8_t* inf = ws.at<uint8_t>(l.inf);
   kzco::k_open_cosets_x<<<dim3((unsigned)prepare_grid(log_c, log_l)), dim3(BLOCK), 0, (hipStream_t)stream>>>(srs_g1_xy, log_c, log_l, prepare_items(log_c, log_l), xy, inf);
   rc = sylow_hip_g1_ntt_batch(xy, inf, wide_log(log_c), elems(log_l), /*inverse=*/0, table_xy, table_inf, stream);
   return host::finish(rc, ws);
@@ -256,7 +257,8 @@ int32_t sylow_hip_kzg_cosets_reduce_batch(const uint64_t* srs_g1_xy, const uint6
   ARGCHK(logs_ok(log_c, log_l));
   if (!rows) return SYLOW_HIP_OK;
   ARGCHK(srs_g1_xy && c_xy && idx && vals && cred_xy && cred_inf && z_out);
-  const size_t bytes = reduce_scratch_bytes(log_l, rows), vb = vals_bytes(log_l, rows), pb = point_bytes(rows), sb = scalar_bytes(rows);
+  const ReduceLayout l = reduce_layout(log_l, rows);
+  const size_t bytes = l.bytes, vb = vals_bytes(log_l, rows), pb = point_bytes(rows), sb = scalar_bytes(rows);
   ARGCHK(bytes != SAT);
   ARGCHK(disjoint((uintptr_t)c_xy, pb, (uintptr_t)cred_xy, pb) && disjoint((uintptr_t)vals, vb, (uintptr_t)cred_xy, pb) && disjoint((uintptr_t)vals, vb, (uintptr_t)z_out, sb));
   ARGCHK(disjoint((uintptr_t)idx, rows * sizeof(uint64_t), (uintptr_t)cred_xy, pb) && disjoint((uintptr_t)idx, rows * sizeof(uint64_t), (uintptr_t)z_out, sb));
@@ -264,8 +266,8 @@ int32_t sylow_hip_kzg_cosets_reduce_batch(const uint64_t* srs_g1_xy, const uint6
   host::Lease ws;
   int32_t rc = ws.acquire(bytes, (hipStream_t)stream);
   if (rc != SYLOW_HIP_OK) return rc;
-  u64 *r = (u64*)ws.p, *rc_xy = r + vb / sizeof(u64);
-  uint8_t* rc_inf = (uint8_t*)(rc_xy + pb / sizeof(u64));
+  u64 *r = ws.at<u64>(l.r), *rc_xy = ws.at<u64>(l.rc_xy);
+  uint8_t* rc_inf = ws.at<uint8_t>(l.rc_inf);
   rc = kzco::interp(vals, idx, log_c, log_l, rows, r, z_out, in_range_out, stream);
   if (rc == SYLOW_HIP_OK) rc = sylow_hip_kzg_commit_batch(srs_g1_xy, r, elems(log_l), rows, rc_xy, rc_inf, stream);        // R(tau) G1gen
   if (rc == SYLOW_HIP_OK) rc = sylow_hip_g1_sub_batch(c_xy, c_inf, rc_xy, rc_inf, cred_xy, cred_inf, rows, stream);       // C - R(tau) G1gen
@@ -278,14 +280,15 @@ int32_t sylow_hip_kzg_verify_cosets_batch(const uint64_t* srs_g1_xy, const uint6
   ARGCHK(logs_ok(log_c, log_l));
   if (!rows) return SYLOW_HIP_OK;
   ARGCHK(srs_g1_xy && tau_l_g2_xy && c_xy && idx && vals && pi_xy && ok);
-  const size_t bytes = verify_scratch_bytes(rows), pb = point_bytes(rows), sb = scalar_bytes(rows);
+  const VerifyLayout l = verify_layout(rows);
+  const size_t bytes = l.bytes, sb = scalar_bytes(rows);
   ARGCHK(bytes != SAT && reduce_scratch_bytes(log_l, rows) != SAT);
   const hipStream_t st = (hipStream_t)stream;
   host::Lease ws;
   int32_t rc = ws.acquire(bytes, st);
   if (rc != SYLOW_HIP_OK) return rc;
-  u64 *cred = (u64*)ws.p, *z = cred + pb / sizeof(u64), *y = z + sb / sizeof(u64);
-  uint8_t *cred_inf = (uint8_t*)(y + sb / sizeof(u64)), *in_rng = cred_inf + rows;
+  u64 *cred = ws.at<u64>(l.cred), *z = ws.at<u64>(l.z), *y = ws.at<u64>(l.y);
+  uint8_t *cred_inf = ws.at<uint8_t>(l.cred_inf), *in_rng = ws.at<uint8_t>(l.in_rng);
   if (hipMemsetAsync(y, 0, sb, st) != hipSuccess) rc = host::fail(hipGetLastError(), "clearing y");
   if (rc == SYLOW_HIP_OK) rc = sylow_hip_kzg_cosets_reduce_batch(srs_g1_xy, c_xy, c_inf, idx, vals, log_c, log_l, rows, cred, cred_inf, z, in_rng, stream);
   if (rc == SYLOW_HIP_OK) rc = sylow_hip_kzg_verify_batch(tau_l_g2_xy, cred, cred_inf, z, y, pi_xy, pi_inf, ok, rows, stream);

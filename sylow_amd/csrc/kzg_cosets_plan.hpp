@@ -2,19 +2,21 @@
 // of the Feist-Khovratovich construction): n = c l points cut into c = 2^log_c cosets of l = 2^log_l points, one proof per coset.  The l
 // arrays x^(a) the table is the transform of, the split of a polynomial into its l residue arrays, the fused first stage with its planes, the
 // fold of the planes, the ping-pong through both transforms (kzg_open_all_plan.hpp's with n -> c), the interpolation's twist, the window tables
-// and the scratch, plain C++ so that tests/cpp/kzg_cosets_plan_test.cpp can compile it with g++ on a box without a GPU.  The launch code asks
+// and the scratch with its offsets, plain C++ so that tests/cpp/kzg_cosets_plan_test.cpp can compile it with g++ on a box without a GPU.  The launch code asks
 // these functions and decides nothing itself.
 #pragma once
 #include "kzg_open_all_plan.hpp"
 
 namespace kzg_cosets_plan {
 namespace oa = kzg_open_all_plan;
+using plan_base::Carve;
 using plan_base::SAT;
 using plan_base::add_sat;
 using plan_base::disjoint;
 using plan_base::elems;
 using plan_base::max_blocks_ok;
 using plan_base::mul_sat;
+using plan_base::words_of;
 using g1_ntt_plan::G1_NTT_AFFINE_WORDS;
 using g1_ntt_plan::G1_NTT_PROJ_WORDS;
 using oa::FR_WORDS;
@@ -38,7 +40,14 @@ constexpr size_t x_srs_index(size_t a, size_t k, int log_c, int log_l) {
   return oa::x_srs_index(k, log_c) == X_IDENTITY ? X_IDENTITY : a + (oa::x_srs_index(k, log_c) << log_l);
 }
 constexpr size_t prepare_items(int log_c, int log_l) { return mul_sat(wide(log_c), elems(log_l)); }
-constexpr size_t prepare_scratch_bytes(int log_c, int log_l) { return add_sat(table_xy_bytes(log_c, log_l), table_inf_bytes(log_c, log_l)); }
+struct PrepareLayout { size_t xy, inf, bytes; };
+constexpr PrepareLayout prepare_layout(int log_c, int log_l) {
+  Carve c; PrepareLayout l{};
+  l.xy = c.words(words_of(table_xy_bytes(log_c, log_l)));
+  l.inf = c.bytes(table_inf_bytes(log_c, log_l));
+  l.bytes = c.at; return l;
+}
+constexpr size_t prepare_scratch_bytes(int log_c, int log_l) { return prepare_layout(log_c, log_l).bytes; }
 constexpr size_t prepare_grid(int log_c, int log_l) { return g1_ntt_plan::grid(prepare_items(log_c, log_l), -1); }
 
 // ---- per polynomial.  log_c = 0 has one proof, the identity: one launch writes it.  From log_c = 1 on, with L = log_c + 1:
@@ -108,12 +117,24 @@ constexpr size_t table_bytes(int log_c, size_t m, int pl, long long max_blocks) 
 
 // ---- the scratch of a call, bytes, saturated: the window tables (16-byte loads: first), the twiddles of 2c and of c points, the two
 // ping-pong buffers, the plane buffer, P and F -------------------------------------------------------------------------------------------------
-constexpr size_t scratch_words(int log_c, int log_l, size_t m, int pl) {
-  return add_sat(add_sat(oa::wide_twiddle_words(log_c) + oa::twiddle_words(log_c), mul_sat(oa::buffer_words(log_c, m), 2)),
-                 add_sat(plane_words(log_c, m, pl), mul_sat(split_words(log_c, log_l, m), 2)));
+struct ScratchLayout { size_t tables, tw_wide, tw, buf[2], planes, padded, f, bytes; };
+constexpr ScratchLayout scratch_layout(int log_c, int log_l, size_t m, int pl, long long max_blocks) {
+  Carve c; ScratchLayout l{};
+  if (trivial(log_c)) return l;
+  l.tables = c.bytes(table_bytes(log_c, m, pl, max_blocks));      // a multiple of 1 KB: the words after it stay aligned
+  l.tw_wide = c.words(oa::wide_twiddle_words(log_c));
+  l.tw = c.words(oa::twiddle_words(log_c));
+  l.buf[0] = c.words(oa::buffer_words(log_c, m));
+  l.buf[1] = c.words(oa::buffer_words(log_c, m));
+  l.planes = c.words(plane_words(log_c, m, pl));
+  l.padded = c.words(split_words(log_c, log_l, m));
+  l.f = c.words(split_words(log_c, log_l, m));
+  l.bytes = c.at; return l;
 }
-constexpr size_t scratch_bytes(int log_c, int log_l, size_t m, int pl, long long max_blocks) {
-  return trivial(log_c) ? 0 : add_sat(mul_sat(scratch_words(log_c, log_l, m, pl), sizeof(uint64_t)), table_bytes(log_c, m, pl, max_blocks));
+constexpr size_t scratch_bytes(int log_c, int log_l, size_t m, int pl, long long max_blocks) { return scratch_layout(log_c, log_l, m, pl, max_blocks).bytes; }
+// its u64 words, behind the tables (none at c = 1, where nothing is leased)
+constexpr size_t scratch_words(int log_c, int log_l, size_t m, int pl) {
+  return scratch_layout(log_c, log_l, m, pl, -1).bytes == SAT ? SAT : (scratch_layout(log_c, log_l, m, pl, -1).bytes - scratch_layout(log_c, log_l, m, pl, -1).tw_wide) / 8;
 }
 
 // ---- the verifier's side: R_i = f mod (X^l - v^i) from the l values of coset i: the inverse Fr transform of l points, then
@@ -135,6 +156,24 @@ constexpr size_t vals_bytes(int log_l, size_t n_rows) { return mul_sat(mul_sat(e
 // [4][rows] each, in_range [rows]
 constexpr size_t point_bytes(size_t n_rows) { return mul_sat(n_rows, G1_NTT_AFFINE_WORDS * sizeof(uint64_t)); }
 constexpr size_t scalar_bytes(size_t n_rows) { return mul_sat(n_rows, FR_WORDS * sizeof(uint64_t)); }
-constexpr size_t reduce_scratch_bytes(int log_l, size_t n_rows) { return add_sat(add_sat(vals_bytes(log_l, n_rows), point_bytes(n_rows)), n_rows); }
-constexpr size_t verify_scratch_bytes(size_t n_rows) { return add_sat(add_sat(point_bytes(n_rows), mul_sat(scalar_bytes(n_rows), 2)), mul_sat(n_rows, 2)); }
+struct ReduceLayout { size_t r, rc_xy, rc_inf, bytes; };
+constexpr ReduceLayout reduce_layout(int log_l, size_t n_rows) {
+  Carve c; ReduceLayout l{};
+  l.r = c.words(words_of(vals_bytes(log_l, n_rows)));
+  l.rc_xy = c.words(words_of(point_bytes(n_rows)));
+  l.rc_inf = c.bytes(n_rows);
+  l.bytes = c.at; return l;
+}
+constexpr size_t reduce_scratch_bytes(int log_l, size_t n_rows) { return reduce_layout(log_l, n_rows).bytes; }
+struct VerifyLayout { size_t cred, z, y, cred_inf, in_rng, bytes; };
+constexpr VerifyLayout verify_layout(size_t n_rows) {
+  Carve c; VerifyLayout l{};
+  l.cred = c.words(words_of(point_bytes(n_rows)));
+  l.z = c.words(words_of(scalar_bytes(n_rows)));
+  l.y = c.words(words_of(scalar_bytes(n_rows)));
+  l.cred_inf = c.bytes(n_rows);
+  l.in_rng = c.bytes(n_rows);
+  l.bytes = c.at; return l;
+}
+constexpr size_t verify_scratch_bytes(size_t n_rows) { return verify_layout(n_rows).bytes; }
 }  // namespace kzg_cosets_plan

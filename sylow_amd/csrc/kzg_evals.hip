@@ -238,9 +238,10 @@ static int32_t quotient_evals(const uint64_t* evals, int log_n, size_t m, const 
   const hipStream_t st = (hipStream_t)stream;
   const size_t n_chunks = poly_chunks(log_n), its = items(log_n, m);
   host::Lease ws;
-  int32_t rc = ws.acquire(mul_sat(quotient_scratch_words(log_n, m, y_out != nullptr), sizeof(u64)), st);
+  const QuotientLayout l = quotient_layout(log_n, m, y_out != nullptr);
+  int32_t rc = ws.acquire(l.bytes, st);
   if (rc != SYLOW_HIP_OK) return rc;
-  u64 *roots = (u64*)ws.p, *totals = roots + roots_words(), *hit = totals + 4 * its, *y = y_out ? y_out : hit + m;
+  u64 *roots = ws.at<u64>(l.roots), *totals = ws.at<u64>(l.totals), *hit = ws.at<u64>(l.hit), *y = y_out ? y_out : ws.at<u64>(l.y);
   const ntt_plan::Words4 ni = ntt_plan::n_inverse(log_n);
   const Scalar n_inv = {{ni.w[0], ni.w[1], ni.w[2], ni.w[3]}};
   const dim3 per_item((unsigned)grid(its)), per_poly((unsigned)grid(m));
@@ -279,13 +280,14 @@ int32_t sylow_hip_kzg_open_evals_batch(const uint64_t* srs_lagrange_xy, const ui
   using namespace kzg_evals_plan;
   ARGCHK(log_n >= 0 && log_n <= EVALS_LOG_N_MAX); if (!m) return SYLOW_HIP_OK;
   ARGCHK(srs_lagrange_xy && evals && z && y_out && pi_xy && pi_inf);
-  const size_t bytes = mul_sat(open_scratch_words(log_n, m), sizeof(uint64_t));
+  const size_t bytes = open_scratch_bytes(log_n, m);
   ARGCHK(bytes != SAT);
   host::Lease ws;
   int32_t rc = ws.acquire(bytes, (hipStream_t)stream);
   if (rc != SYLOW_HIP_OK) return rc;
-  rc = kze::quotient_evals(evals, log_n, m, z, (uint64_t*)ws.p, y_out, stream);
-  if (rc == SYLOW_HIP_OK) rc = kzgph::commit_canonical(srs_lagrange_xy, (const uint64_t*)ws.p, elems(log_n), m, pi_xy, pi_inf, stream);
+  uint64_t* q = ws.at<uint64_t>(0);
+  rc = kze::quotient_evals(evals, log_n, m, z, q, y_out, stream);
+  if (rc == SYLOW_HIP_OK) rc = kzgph::commit_canonical(srs_lagrange_xy, q, elems(log_n), m, pi_xy, pi_inf, stream);
   return host::finish(rc, ws);
 }
 }  // extern "C"

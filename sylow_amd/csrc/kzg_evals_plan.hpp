@@ -1,14 +1,16 @@
 // kzg_evals_plan.hpp -- the geometry of the shared-inverse batch inversion in Fr and of the KZG quotient from evaluations (kzg_evals.hip):
-// every size, grid, scratch and route decision between an entry point and its kernels, plain C++ so that tests/cpp/kzg_evals_plan_test.cpp
+// every size, grid, scratch size and offset, and route decision between an entry point and its kernels, plain C++ so that tests/cpp/kzg_evals_plan_test.cpp
 // can compile it with g++ on a box without a GPU.  The launch code asks these functions and decides nothing itself.
 #pragma once
 #include "plan_base.hpp"
 
 namespace kzg_evals_plan {
+using plan_base::Carve;
 using plan_base::SAT;
 using plan_base::add_sat;
 using plan_base::elems;
 using plan_base::mul_sat;
+using plan_base::words_of;
 // ---- the chunk: a lane owns EVALS_LANE_ELEMS consecutive elements, a block of EVALS_BLOCK lanes a chunk of EVALS_CHUNK -------------------
 // The elements of a chunk share ONE inversion: prefix products inside a lane, a prefix and a suffix scan of the lane totals through LDS, the
 // inverse of the chunk's product on one lane (bn254_fr_euclid.hpp), and the way back.  There is no level above the chunk: every chunk pays
@@ -51,13 +53,21 @@ constexpr size_t ROOT_SLOTS = EVALS_LOG_N_MAX + 1;       // w^(2^s) at slot s < 
 constexpr size_t roots_words() { return 4 * ROOT_SLOTS; }
 // u64 words a call leases: the roots, the chunk sums [4][items] (the first sum's, then the second's), the hit index per polynomial [m],
 // and y [4][m] when the caller wants none (the quotient still needs it)
-constexpr size_t quotient_scratch_words(int log_n, size_t m, bool has_y_out) {
-  return add_sat(add_sat(roots_words(), mul_sat(4, items(log_n, m))), add_sat(m, has_y_out ? 0 : mul_sat(4, m)));
+struct QuotientLayout { size_t roots, totals, hit, y, bytes; };
+constexpr QuotientLayout quotient_layout(int log_n, size_t m, bool has_y_out) {
+  Carve c; QuotientLayout l{};
+  l.roots = c.words(roots_words());
+  l.totals = c.words(mul_sat(4, items(log_n, m)));
+  l.hit = c.words(m);
+  l.y = c.words(has_y_out ? 0 : mul_sat(4, m));
+  l.bytes = c.at; return l;
 }
+constexpr size_t quotient_scratch_words(int log_n, size_t m, bool has_y_out) { return words_of(quotient_layout(log_n, m, has_y_out).bytes); }
 constexpr size_t batch_words(int log_n, size_t m) { return mul_sat(mul_sat(4, elems(log_n)), m); }
 constexpr uint64_t NO_HIT = ~(uint64_t)0;        // the hit slot of a polynomial whose z is outside the domain (k_evals_roots clears every slot to it)
 
 // ---- the opening: the quotient's values into a leased [m][4][n], then the commitment over the Lagrange SRS -----------------------------
 // The quotient's words are canonical, so the commitment is entered past its mod-r pass (kzg_prove.hip exports that entry to this unit).
 constexpr size_t open_scratch_words(int log_n, size_t m) { return batch_words(log_n, m); }
+constexpr size_t open_scratch_bytes(int log_n, size_t m) { return mul_sat(open_scratch_words(log_n, m), sizeof(uint64_t)); }
 }  // namespace kzg_evals_plan

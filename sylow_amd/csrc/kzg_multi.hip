@@ -168,20 +168,20 @@ static bool ranges_overlap(const void* a, size_t a_bytes, const void* b, size_t 
 }
 
 // The prover's common part once the y_j are written: the powers and z spread to the polynomials are in ws; F = the folded polynomials (or
-// the folded values) into ws.  Layout of ws: gs [G + 1] | pow [4][m] | zs [4][m] | F [G][4][len] | yF [4][G]
+// the folded values) into ws.  Layout of ws: kzgm_plan::open_layout
 struct OpenScratch {
   u64 *gs, *pow, *zs, *f, *yf;
-  OpenScratch(void* p, size_t len, size_t m, size_t G) : gs((u64*)p), pow(gs + offset_words(G)), zs(pow + 4 * m), f(zs + 4 * m), yf(f + 4 * G * len) {}
+  OpenScratch(const host::Lease& ws, const OpenLayout& l) : gs(ws.at<u64>(l.gs)), pow(ws.at<u64>(l.pow)), zs(ws.at<u64>(l.zs)), f(ws.at<u64>(l.f)), yf(ws.at<u64>(l.yf)) {}
 };
 static int32_t open_setup(host::Lease& ws, const uint64_t* group_start, size_t len, size_t m, size_t G, const uint64_t* z, const uint64_t* gamma, hipStream_t st) {
-  const size_t words = open_scratch_words(len, m, G);
-  if (words > SAT / sizeof(u64)) {
+  const OpenLayout l = open_layout(len, m, G);
+  if (l.bytes == SAT) {
     snprintf(sylow_g_err, sizeof(sylow_g_err), "bad argument: the scratch of %zu groups of %zu terms does not fit size_t", G, len);
     return SYLOW_HIP_E_ARG;
   }
-  int32_t rc = ws.acquire(words * sizeof(u64), st);
+  int32_t rc = ws.acquire(l.bytes, st);
   if (rc != SYLOW_HIP_OK) return rc;
-  const OpenScratch s(ws.p, len, m, G);
+  const OpenScratch s(ws, l);
   rc = put_offsets(group_start, G, s.gs, st);
   if (rc == SYLOW_HIP_OK) powers_launch(gamma, z, s.gs, G, m, s.pow, s.zs, st);
   return rc;
@@ -200,10 +200,11 @@ static int32_t combine(const uint64_t* c_xy, const uint8_t* c_inf, const uint64_
     const size_t n = n_seg * ch.terms, w_acc = ch.route == Route::SEGMENTS ? g1h::sum_segments_scratch_words(n_seg, ch.terms) : 0;
     const bool direct = ch.route == Route::SEGMENTS && n_seg == G;      // one chunk: the segmented sum writes [8][G] itself
     host::Lease ws;
-    rc = ws.acquire((4 * n + 8 * n + 8 * n + w_acc + 8 * n_seg) * sizeof(u64) + 2 * n + n_seg, st);
+    const ChunkLayout l = chunk_layout(n, n_seg, w_acc);
+    rc = ws.acquire(l.bytes, st);
     if (rc != SYLOW_HIP_OK) return rc;
-    u64 *sc = (u64*)ws.p, *bases = sc + 4 * n, *prod = bases + 8 * n, *acc = prod + 8 * n, *part = acc + w_acc;
-    uint8_t *flags = (uint8_t*)(part + 8 * n_seg), *prod_inf = flags + n, *part_inf = prod_inf + n;
+    u64 *sc = ws.at<u64>(l.sc), *bases = ws.at<u64>(l.bases), *prod = ws.at<u64>(l.prod), *acc = ws.at<u64>(l.acc), *part = ws.at<u64>(l.part);
+    uint8_t *flags = ws.at<uint8_t>(l.flags), *prod_inf = ws.at<uint8_t>(l.prod_inf), *part_inf = ws.at<uint8_t>(l.part_inf);
     k_kzgm_combine_prep<<<dim3((unsigned)lane_grid(n)), dim3(BLOCK), 0, st>>>(c_xy, c_inf, m, pow, gs, g0, n_seg, ch.terms, sc, bases, flags);
     if (ch.route == Route::MSM) {
       rc = sylow_hip_g1_msm(bases, flags, sc, n, part, part_inf, stream);
@@ -222,12 +223,13 @@ static int32_t combine(const uint64_t* c_xy, const uint8_t* c_inf, const uint64_
 static int32_t combine_call(const uint64_t* c_xy, const uint8_t* c_inf, const uint64_t* y, size_t m, const uint64_t* group_start, size_t G, const uint64_t* gamma,
                             uint64_t* cf_xy, uint8_t* cf_inf, uint64_t* yf, void* stream) {
   const hipStream_t st = (hipStream_t)stream;
-  const size_t words = combine_scratch_words(m, G);
+  const CombineLayout l = combine_layout(m, G);
+  const size_t words = words_of(l.bytes);
   ARGCHK(words <= SAT / sizeof(u64));
   host::Lease ws;
-  int32_t rc = ws.acquire(words * sizeof(u64), st);
+  int32_t rc = ws.acquire(l.bytes, st);
   if (rc != SYLOW_HIP_OK) return rc;
-  u64 *gs = (u64*)ws.p, *pow = gs + offset_words(G);
+  u64 *gs = ws.at<u64>(l.gs), *pow = ws.at<u64>(l.pow);
   rc = put_offsets(group_start, G, gs, st);
   if (rc == SYLOW_HIP_OK) {
     powers_launch(gamma, nullptr, gs, G, m, pow, nullptr, st);
@@ -250,10 +252,11 @@ int32_t sylow_hip_fr_lincomb_batch(const uint64_t* a, size_t len, size_t m, cons
   ARGCHK(!ranges_overlap(a, 4 * sizeof(u64) * len * m, out, 4 * sizeof(u64) * len * G));
   const hipStream_t st = (hipStream_t)stream;
   host::Lease ws;
-  int32_t rc = ws.acquire(offset_words(G) * sizeof(u64), st);
+  int32_t rc = ws.acquire(offset_bytes(G), st);
   if (rc != SYLOW_HIP_OK) return rc;
-  rc = put_offsets(group_start, G, (u64*)ws.p, st);
-  if (rc == SYLOW_HIP_OK) lincomb_launch(a, len, m, weights, (const u64*)ws.p, G, out, st);
+  u64* gs = ws.at<u64>(0);
+  rc = put_offsets(group_start, G, gs, st);
+  if (rc == SYLOW_HIP_OK) lincomb_launch(a, len, m, weights, gs, G, out, st);
   return host::finish(rc, ws);
 }
 int32_t sylow_hip_fr_group_powers_batch(const uint64_t* gamma, const uint64_t* group_start, size_t G, size_t m, uint64_t* out, void* stream) {
@@ -263,10 +266,11 @@ int32_t sylow_hip_fr_group_powers_batch(const uint64_t* gamma, const uint64_t* g
   GROUPCHK(group_start, G, m);
   const hipStream_t st = (hipStream_t)stream;
   host::Lease ws;
-  int32_t rc = ws.acquire(offset_words(G) * sizeof(u64), st);
+  int32_t rc = ws.acquire(offset_bytes(G), st);
   if (rc != SYLOW_HIP_OK) return rc;
-  rc = put_offsets(group_start, G, (u64*)ws.p, st);
-  if (rc == SYLOW_HIP_OK) powers_launch(gamma, nullptr, (const u64*)ws.p, G, m, out, nullptr, st);
+  u64* gs = ws.at<u64>(0);
+  rc = put_offsets(group_start, G, gs, st);
+  if (rc == SYLOW_HIP_OK) powers_launch(gamma, nullptr, gs, G, m, out, nullptr, st);
   return host::finish(rc, ws);
 }
 int32_t sylow_hip_kzg_open_multi_batch(const uint64_t* srs_g1_xy, const uint64_t* coeffs, size_t len, size_t m, const uint64_t* group_start, size_t G,
@@ -279,7 +283,7 @@ int32_t sylow_hip_kzg_open_multi_batch(const uint64_t* srs_g1_xy, const uint64_t
   host::Lease ws;
   int32_t rc = open_setup(ws, group_start, len, m, G, z, gamma, st);
   if (rc != SYLOW_HIP_OK) return rc;
-  const OpenScratch s(ws.p, len, m, G);
+  const OpenScratch s(ws, open_layout(len, m, G));
   rc = sylow_hip_kzg_quotient_batch(coeffs, len, m, s.zs, nullptr, y_out, stream);                 // y_j = f_j(z_g): evaluation only
   if (rc == SYLOW_HIP_OK) {
     lincomb_launch(coeffs, len, m, s.pow, s.gs, G, s.f, st);
@@ -298,7 +302,7 @@ int32_t sylow_hip_kzg_open_multi_evals_batch(const uint64_t* srs_lagrange_xy, co
   host::Lease ws;
   int32_t rc = open_setup(ws, group_start, n, m, G, z, gamma, st);
   if (rc != SYLOW_HIP_OK) return rc;
-  const OpenScratch s(ws.p, n, m, G);
+  const OpenScratch s(ws, open_layout(n, m, G));
   rc = sylow_hip_kzg_quotient_evals_batch(evals, log_n, m, s.zs, nullptr, y_out, stream);          // barycentric evaluation alone
   if (rc == SYLOW_HIP_OK) {
     lincomb_launch(evals, n, m, s.pow, s.gs, G, s.f, st);                                          // the values of F_g: the fold is linear
@@ -320,13 +324,14 @@ int32_t sylow_hip_kzg_verify_multi_batch(const uint64_t* tau_g2_xy, const uint64
   if (!m || !G) return SYLOW_HIP_OK;
   ARGCHK(tau_g2_xy && c_xy && y && group_start && z && gamma && pi_xy && ok);
   GROUPCHK(group_start, G, m);
-  const size_t words = verify_scratch_words(G);
+  const VerifyLayout l = verify_layout(G);
+  const size_t words = words_of(l.bytes);
   ARGCHK(words <= SAT / sizeof(u64));
   host::Lease ws;
-  int32_t rc = ws.acquire(words * sizeof(u64), (hipStream_t)stream);
+  int32_t rc = ws.acquire(l.bytes, (hipStream_t)stream);
   if (rc != SYLOW_HIP_OK) return rc;
-  u64 *cf = (u64*)ws.p, *yf = cf + 8 * G;
-  uint8_t* cf_inf = (uint8_t*)(yf + 4 * G);
+  u64 *cf = ws.at<u64>(l.cf), *yf = ws.at<u64>(l.yf);
+  uint8_t* cf_inf = ws.at<uint8_t>(l.cf_inf);
   rc = combine_call(c_xy, c_inf, y, m, group_start, G, gamma, cf, cf_inf, yf, stream);
   if (rc == SYLOW_HIP_OK) rc = sylow_hip_kzg_verify_batch(tau_g2_xy, cf, cf_inf, z, yf, pi_xy, pi_inf, ok, G, stream);
   return host::finish(rc, ws);

@@ -1,12 +1,14 @@
 // kzg_multi_plan.hpp -- the geometry of the grouped linear combination over Fr and the routes of the folded KZG openings (kzg_multi.hip):
-// tiles, grids, the flush length, how group_start travels to the device, scratch sizes and the chunks of the combined commitments.  Plain
+// tiles, grids, the flush length, how group_start travels to the device, scratch sizes and offsets, and the chunks of the combined commitments.  Plain
 // C++ so that tests/cpp/kzg_multi_plan_test.cpp can compile it with g++ on a box without a GPU.  The launch code asks these functions and
 // decides nothing itself.
 #pragma once
 #include "plan_base.hpp"
 
 namespace kzgm_plan {
+using plan_base::Carve;
 using plan_base::SAT;
+using plan_base::words_of;
 // ---- groups ------------------------------------------------------------------------------------------------------------------------
 // group_start is a HOST array of G + 1 offsets: non-decreasing, group_start[0] = 0, group_start[G] = m.  Empty groups are legal.
 constexpr bool groups_ok(const uint64_t* group_start, size_t G, size_t m) {
@@ -54,14 +56,55 @@ constexpr size_t group_grid(size_t G) { return G < KZGM_LANE_GRID_CAP ? G : KZGM
 // ---- scratch, in u64 words; (size_t)-1 = does not fit size_t (the entry point refuses it before the lease) ----------------------------
 constexpr size_t sat_mul(size_t a, size_t b) { return a && b > SAT / a ? SAT : a * b; }
 constexpr size_t sat_add(size_t a, size_t b) { return a > SAT - b ? SAT : a + b; }
+// the offsets alone
+constexpr size_t offset_bytes(size_t G) { return sat_mul(offset_words(G), 8); }
 // the prover: the offsets, the powers [4][m], z spread [4][m], the folded polynomials [G][4][len] (32 G len bytes) and their values [4][G]
-constexpr size_t open_scratch_words(size_t len, size_t m, size_t G) {
-  return sat_add(sat_add(offset_words(G), sat_mul(8, m)), sat_add(sat_mul(sat_mul(4, G), len), sat_mul(4, G)));
+struct OpenLayout { size_t gs, pow, zs, f, yf, bytes; };
+constexpr OpenLayout open_layout(size_t len, size_t m, size_t G) {
+  Carve c; OpenLayout l{};
+  l.gs = c.words(offset_words(G));
+  l.pow = c.words(sat_mul(4, m));
+  l.zs = c.words(sat_mul(4, m));
+  l.f = c.words(sat_mul(sat_mul(4, G), len));
+  l.yf = c.words(sat_mul(4, G));
+  l.bytes = c.at; return l;
 }
+constexpr size_t open_scratch_words(size_t len, size_t m, size_t G) { return words_of(open_layout(len, m, G).bytes); }
 // the verifier's calls: the offsets and the powers [4][m]
-constexpr size_t combine_scratch_words(size_t m, size_t G) { return sat_add(offset_words(G), sat_mul(4, m)); }
+struct CombineLayout { size_t gs, pow, bytes; };
+constexpr CombineLayout combine_layout(size_t m, size_t G) {
+  Carve c; CombineLayout l{};
+  l.gs = c.words(offset_words(G));
+  l.pow = c.words(sat_mul(4, m));
+  l.bytes = c.at; return l;
+}
+constexpr size_t combine_scratch_words(size_t m, size_t G) { return words_of(combine_layout(m, G).bytes); }
+// one chunk of the combined commitments, n = n_seg * terms slots: the scalars [4][n], the bases and the products [8][n] each, the segmented
+// sum's w_acc words, the chunk's sums [8][n_seg]; then the flags of the bases and of the products [n] each and of the sums [n_seg]
+struct ChunkLayout { size_t sc, bases, prod, acc, part, flags, prod_inf, part_inf, bytes; };
+constexpr ChunkLayout chunk_layout(size_t n, size_t n_seg, size_t w_acc) {
+  Carve c; ChunkLayout l{};
+  l.sc = c.words(sat_mul(4, n));
+  l.bases = c.words(sat_mul(8, n));
+  l.prod = c.words(sat_mul(8, n));
+  l.acc = c.words(w_acc);
+  l.part = c.words(sat_mul(8, n_seg));
+  l.flags = c.bytes(n);
+  l.prod_inf = c.bytes(n);
+  l.part_inf = c.bytes(n_seg);
+  l.bytes = c.at; return l;
+}
 // sylow_hip_kzg_verify_multi_batch on top of that: C_F [8][G], y_F [4][G] and the flags [G] (rounded up to words)
-constexpr size_t verify_scratch_words(size_t G) { return sat_add(sat_mul(12, G), (G + 7) / 8); }
+struct VerifyLayout { size_t cf, yf, cf_inf, bytes; };
+constexpr VerifyLayout verify_layout(size_t G) {
+  Carve c; VerifyLayout l{};
+  l.cf = c.words(sat_mul(8, G));
+  l.yf = c.words(sat_mul(4, G));
+  l.cf_inf = c.bytes(G);
+  c.round();
+  l.bytes = c.at; return l;
+}
+constexpr size_t verify_scratch_words(size_t G) { return words_of(verify_layout(G).bytes); }
 
 // ---- the combined commitments: C_F,g = sum_j gamma_g^i C_j ---------------------------------------------------------------------------
 enum class Route {

@@ -103,15 +103,15 @@ static int32_t open_all(const uint64_t* txy, const uint8_t* tinf, const uint64_t
     k_open_all_trivial<<<dim3((unsigned)trivial_grid(m)), dim3(BLOCK), 0, st>>>(pi_xy, pi_inf, m);
     LAUNCHED();
   }
-  const size_t bytes = scratch_bytes(log_n, m, max_blocks);
-  if (bytes > SAT / 2) return host::fail(hipErrorOutOfMemory, "scratch of the proofs at every point");
+  const ScratchLayout l = scratch_layout(log_n, m, max_blocks);
+  if (l.bytes > SAT / 2) return host::fail(hipErrorOutOfMemory, "scratch of the proofs at every point");
   host::Lease ws;
-  rc = ws.acquire(bytes, st);
+  rc = ws.acquire(l.bytes, st);
   if (rc != SYLOW_HIP_OK) return rc;
-  uint8_t* tables = (uint8_t*)ws.p;
-  u64 *tw_wide = (u64*)(tables + table_bytes(log_n, m, max_blocks)), *tw = tw_wide + wide_twiddle_words(log_n);
-  u64* buf[2] = {tw + twiddle_words(log_n), tw + twiddle_words(log_n) + buffer_words(log_n, m)};
-  u64 *padded = buf[FR_BUFFER] + pad_offset(), *f = buf[FR_BUFFER] + f_offset(log_n, m);
+  uint8_t* tables = ws.at<uint8_t>(l.tables);
+  u64 *tw_wide = ws.at<u64>(l.tw_wide), *tw = ws.at<u64>(l.tw);
+  u64* buf[2] = {ws.at<u64>(l.buf[0]), ws.at<u64>(l.buf[1])};
+  u64 *padded = ws.at<u64>(l.padded), *f = ws.at<u64>(l.f);
   const size_t str = stride(log_n, m);
   const int L = wide_log(log_n);
   const ntt_plan::Words4 ni = ntt_plan::n_inverse(L);
@@ -146,10 +146,11 @@ int32_t sylow_hip_kzg_open_all_prepare(const uint64_t* srs_g1_xy, int32_t log_n,
   ARGCHK(log_n_ok(log_n));
   ARGCHK(srs_g1_xy && table_xy && table_inf);
   host::Lease ws;
-  int32_t rc = ws.acquire(prepare_scratch_bytes(log_n), (hipStream_t)stream);
+  const PrepareLayout l = prepare_layout(log_n);
+  int32_t rc = ws.acquire(l.bytes, (hipStream_t)stream);
   if (rc != SYLOW_HIP_OK) return rc;
-  u64* xy = (u64*)ws.p;
-  uint8_t* inf = (uint8_t*)ws.p + table_xy_bytes(log_n);
+  u64* xy = ws.at<u64>(l.xy);
+  uint8_t* inf = ws.at<uint8_t>(l.inf);
   kzoa::k_open_all_x<<<dim3((unsigned)prepare_grid(log_n)), dim3(BLOCK), 0, (hipStream_t)stream>>>(srs_g1_xy, log_n, xy, inf);
   rc = sylow_hip_g1_ntt_batch(xy, inf, wide_log(log_n), 1, /*inverse=*/0, table_xy, table_inf, stream);
   return host::finish(rc, ws);

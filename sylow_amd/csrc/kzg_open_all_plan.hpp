@@ -1,19 +1,21 @@
 // kzg_open_all_plan.hpp -- the geometry of the KZG proofs of one polynomial at ALL n = 2^log_n points of its domain (kzg_open_all.hip, the
 // Feist-Khovratovich construction): the array x the table is the transform of, the fused first stage of the size-2n inverse transform, the
 // first stage of the size-n forward transform that reads h out of the wider arrays, the ping-pong through both transforms, where the Fr
-// arrays live, the window tables and the scratch, plain C++ so that tests/cpp/kzg_open_all_plan_test.cpp can compile it with g++ on a box
+// arrays live, the window tables and the scratch with its offsets, plain C++ so that tests/cpp/kzg_open_all_plan_test.cpp can compile it with g++ on a box
 // without a GPU.  The launch code asks these functions and decides nothing itself.  The stages between the two first stages and the closing
 // kernel are g1_ntt.hip's, with the indices of g1_ntt_plan.hpp.
 #pragma once
 #include "g1_ntt_plan.hpp"
 
 namespace kzg_open_all_plan {
+using plan_base::Carve;
 using plan_base::SAT;
 using plan_base::add_sat;
 using plan_base::disjoint;
 using plan_base::elems;
 using plan_base::max_blocks_ok;
 using plan_base::mul_sat;
+using plan_base::words_of;
 using g1_ntt_plan::G1_NTT_AFFINE_WORDS;
 using g1_ntt_plan::G1_NTT_PROJ_WORDS;
 constexpr int OPEN_ALL_LOG_N_MAX = g1_ntt_plan::G1_NTT_LOG_N_MAX - 1;        // the transform of 2n points must fit the 2^28 roots
@@ -32,7 +34,14 @@ constexpr size_t pi_xy_bytes(int log_n, size_t m) { return g1_ntt_plan::xy_bytes
 constexpr size_t X_IDENTITY = SAT;
 constexpr size_t x_srs_index(size_t k, int log_n) { return k > elems(log_n) ? wide(log_n) - 1 - k : X_IDENTITY; }
 // scratch of prepare: x as affine words + flags, [8][2n] words then [2n] bytes
-constexpr size_t prepare_scratch_bytes(int log_n) { return add_sat(table_xy_bytes(log_n), wide(log_n)); }
+struct PrepareLayout { size_t xy, inf, bytes; };
+constexpr PrepareLayout prepare_layout(int log_n) {
+  Carve c; PrepareLayout l{};
+  l.xy = c.words(words_of(table_xy_bytes(log_n)));
+  l.inf = c.bytes(wide(log_n));
+  l.bytes = c.at; return l;
+}
+constexpr size_t prepare_scratch_bytes(int log_n) { return prepare_layout(log_n).bytes; }
 constexpr size_t prepare_grid(int log_n) { return g1_ntt_plan::blocks_for(wide(log_n)); }
 
 // ---- per polynomial.  log_n = 0 has one proof, the identity (h_(n-1) is the identity): one launch writes it and nothing below runs.
@@ -93,10 +102,20 @@ constexpr size_t table_bytes(int log_n, size_t m, long long max_blocks) { return
 // ---- the scratch of a call, bytes, saturated: the window tables (16-byte loads: first), the twiddles of 2n and of n points, two buffers --------
 constexpr size_t wide_twiddle_words(int log_n) { return g1_ntt_plan::twiddle_words(wide_log(log_n)); }
 constexpr size_t twiddle_words(int log_n) { return g1_ntt_plan::twiddle_words(log_n); }
-constexpr size_t scratch_bytes(int log_n, size_t m, long long max_blocks) {
-  return trivial(log_n) ? 0
-                        : add_sat(add_sat(mul_sat(wide_twiddle_words(log_n) + twiddle_words(log_n), sizeof(uint64_t)),
-                                          mul_sat(mul_sat(buffer_words(log_n, m), 2), sizeof(uint64_t))),
-                                  table_bytes(log_n, m, max_blocks));
+// padded and f are no regions of their own: they lie in buf[FR_BUFFER], at pad_offset() and f_offset() words
+struct ScratchLayout { size_t tables, tw_wide, tw, buf[2], bytes, padded, f; };
+constexpr ScratchLayout scratch_layout(int log_n, size_t m, long long max_blocks) {
+  Carve c; ScratchLayout l{};
+  if (trivial(log_n)) return l;
+  l.tables = c.bytes(table_bytes(log_n, m, max_blocks));      // a multiple of 1 KB: the words after it stay aligned
+  l.tw_wide = c.words(wide_twiddle_words(log_n));
+  l.tw = c.words(twiddle_words(log_n));
+  l.buf[0] = c.words(buffer_words(log_n, m));
+  l.buf[1] = c.words(buffer_words(log_n, m));
+  l.bytes = c.at;
+  l.padded = add_sat(l.buf[FR_BUFFER], mul_sat(pad_offset(), 8));
+  l.f = add_sat(l.buf[FR_BUFFER], mul_sat(f_offset(log_n, m), 8));
+  return l;
 }
+constexpr size_t scratch_bytes(int log_n, size_t m, long long max_blocks) { return scratch_layout(log_n, m, max_blocks).bytes; }
 }  // namespace kzg_open_all_plan

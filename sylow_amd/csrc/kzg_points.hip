@@ -270,9 +270,10 @@ static int32_t quotient(const uint64_t* coeffs, size_t len, size_t m, const uint
   const hipStream_t st = (hipStream_t)stream;
   const size_t mk = m * k, n_chunks = chunks(len), s_items = scan_items(len, m, k), c_items = chunk_items(len, m);
   host::Lease ws;
-  int32_t rc = ws.acquire(quot_scratch_words(len, m, k) * sizeof(u64), st);
+  const PointsQuotLayout l = points_quot_layout(len, m, k);
+  int32_t rc = ws.acquire(l.bytes, st);
   if (rc != SYLOW_HIP_OK) return rc;
-  u64 *den = (u64*)ws.p, *a = den + 4 * mk, *totals = a + 4 * mk, *carries = totals + 4 * s_items;
+  u64 *den = ws.at<u64>(l.den), *a = ws.at<u64>(l.a), *totals = ws.at<u64>(l.totals), *carries = ws.at<u64>(l.carries);
   if (q_out) rc = weights(z, k, m, den, a, nullptr, stream);
   if (rc == SYLOW_HIP_OK) {
     if (!carry_levels(len)) {
@@ -288,9 +289,10 @@ static int32_t quotient(const uint64_t* coeffs, size_t len, size_t m, const uint
 static int32_t polys(const uint64_t* z, const uint64_t* y, size_t k, size_t n, uint64_t* zpoly, uint64_t* rpoly, uint8_t* distinct, void* stream) {
   const hipStream_t st = (hipStream_t)stream;
   host::Lease ws;
-  int32_t rc = ws.acquire(polys_scratch_words(n, k) * sizeof(u64), st);
+  const PolysLayout l = polys_layout(n, k);
+  int32_t rc = ws.acquire(l.bytes, st);
   if (rc != SYLOW_HIP_OK) return rc;
-  u64 *den = (u64*)ws.p, *a = den + 4 * n * k;
+  u64 *den = ws.at<u64>(l.den), *a = ws.at<u64>(l.a);
   rc = weights(z, k, n, den, a, distinct, stream);
   if (rc == SYLOW_HIP_OK) k_kzgpt_polys<<<blocks(n), dim3(RB), 0, st>>>(z, y, a, k, n, zpoly, rpoly);
   return host::finish(rc, ws);
@@ -304,9 +306,9 @@ int32_t sylow_hip_kzg_points_weights_batch(const uint64_t* z, size_t k, size_t m
   ARGCHK(z && a_out);
   ARGCHK(weights_scratch_words(m, k) <= SAT / sizeof(u64));
   host::Lease ws;
-  int32_t rc = ws.acquire(weights_scratch_words(m, k) * sizeof(u64), (hipStream_t)stream);
+  int32_t rc = ws.acquire(weights_scratch_bytes(m, k), (hipStream_t)stream);
   if (rc != SYLOW_HIP_OK) return rc;
-  rc = weights(z, k, m, (u64*)ws.p, a_out, distinct_out, stream);
+  rc = weights(z, k, m, ws.at<u64>(0), a_out, distinct_out, stream);
   return host::finish(rc, ws);
 }
 int32_t sylow_hip_kzg_quotient_points_batch(const uint64_t* coeffs, size_t len, size_t m, const uint64_t* z, size_t k, uint64_t* q_out, uint64_t* y_out,
@@ -327,8 +329,9 @@ int32_t sylow_hip_kzg_open_points_batch(const uint64_t* srs_g1_xy, const uint64_
   host::Lease ws;
   int32_t rc = ws.acquire(poly_bytes(len, m), (hipStream_t)stream);
   if (rc != SYLOW_HIP_OK) return rc;
-  rc = quotient(coeffs, len, m, z, k, (uint64_t*)ws.p, y_out, stream);
-  if (rc == SYLOW_HIP_OK) rc = kzgph::commit_canonical(srs_g1_xy, (const uint64_t*)ws.p, len, m, pi_xy, pi_inf, stream);
+  uint64_t* q = ws.at<uint64_t>(0);
+  rc = quotient(coeffs, len, m, z, k, q, y_out, stream);
+  if (rc == SYLOW_HIP_OK) rc = kzgph::commit_canonical(srs_g1_xy, q, len, m, pi_xy, pi_inf, stream);
   return host::finish(rc, ws);
 }
 int32_t sylow_hip_kzg_points_polys_batch(const uint64_t* z, const uint64_t* y, size_t k, size_t n, uint64_t* zpoly_out, uint64_t* rpoly_out, uint8_t* distinct_out,
@@ -336,7 +339,7 @@ int32_t sylow_hip_kzg_points_polys_batch(const uint64_t* z, const uint64_t* y, s
   using namespace kzgpt;
   ARGCHK(points_ok(k)); if (!n) return SYLOW_HIP_OK;
   ARGCHK(z && y && zpoly_out && rpoly_out && distinct_out);
-  ARGCHK(polys_scratch_words(n, k) <= SAT / sizeof(u64) && sat_mul(sat_mul(32, n), k + 1) != SAT);
+  ARGCHK(polys_scratch_words(n, k) <= SAT / sizeof(u64) && mul_sat(mul_sat(32, n), k + 1) != SAT);
   return polys(z, y, k, n, zpoly_out, rpoly_out, distinct_out, stream);
 }
 int32_t sylow_hip_kzg_verify_points_batch(const uint64_t* srs_g1_xy, const uint64_t* srs_g2_xy, const uint64_t* c_xy, const uint8_t* c_inf, const uint64_t* z,
@@ -346,31 +349,31 @@ int32_t sylow_hip_kzg_verify_points_batch(const uint64_t* srs_g1_xy, const uint6
   ARGCHK(srs_g1_xy && srs_g2_xy && c_xy && z && y && pi_xy && ok);
   const hipStream_t st = (hipStream_t)stream;
   const size_t lim = host::scratch_limit(), rows = g2_rows_per_chunk(n, k, lim ? lim : msmh::default_budget());
-  const size_t bytes = verify_scratch_bytes(n, k, rows);
+  const VerifyLayout v = verify_layout(n, k, rows);
+  const size_t bytes = v.bytes;
   ARGCHK(bytes != SAT && polys_scratch_words(n, k) <= SAT / sizeof(u64));
   host::Lease ws;
   int32_t rc = ws.acquire(bytes, st);
   if (rc != SYLOW_HIP_OK) return rc;
-  const VerifyLayout v = verify_layout(n, k, rows);
-  u64* w = (u64*)ws.p;
-  uint8_t* b = (uint8_t*)(w + v.words);
+  const auto W = [&](size_t off) { return ws.at<u64>(off); };
+  const auto B = [&](size_t off) { return ws.at<uint8_t>(off); };
   const bool direct = rows == n;                              // one chunk: the G2 sum writes [16][n] itself
-  rc = polys(z, y, k, n, w + v.z, w + v.r, b + v.distinct, stream);
-  if (rc == SYLOW_HIP_OK) rc = kzgph::commit_canonical(srs_g1_xy, w + v.r, k, n, w + v.rc, b + v.rc_inf, stream);      // R(tau) G1gen
+  rc = polys(z, y, k, n, W(v.z), W(v.r), B(v.distinct), stream);
+  if (rc == SYLOW_HIP_OK) rc = kzgph::commit_canonical(srs_g1_xy, W(v.r), k, n, W(v.rc), B(v.rc_inf), stream);      // R(tau) G1gen
   for (size_t j0 = 0; j0 < n && rc == SYLOW_HIP_OK; j0 += rows) {                                                        // Z(tau) G2gen
     const size_t rc_rows = n - j0 < rows ? n - j0 : rows;
-    k_kzgpt_g2_prep<<<lanes(rc_rows * (k + 1)), dim3(BLOCK), 0, st>>>(w + v.z, srs_g2_xy, k, j0, rc_rows, w + v.sc, w + v.bases);
-    rc = direct ? sylow_hip_g2_lincomb_batch(w + v.bases, nullptr, w + v.sc, w + v.zg, b + v.zg_inf, n, k + 1, stream)
-                : sylow_hip_g2_lincomb_batch(w + v.bases, nullptr, w + v.sc, w + v.part, b + v.part_inf, rc_rows, k + 1, stream);
-    if (rc == SYLOW_HIP_OK && !direct) k_kzgpt_put_g2<<<lanes(rc_rows), dim3(BLOCK), 0, st>>>(w + v.part, b + v.part_inf, rc_rows, w + v.zg, b + v.zg_inf, n, j0);
+    k_kzgpt_g2_prep<<<lanes(rc_rows * (k + 1)), dim3(BLOCK), 0, st>>>(W(v.z), srs_g2_xy, k, j0, rc_rows, W(v.sc), W(v.bases));
+    rc = direct ? sylow_hip_g2_lincomb_batch(W(v.bases), nullptr, W(v.sc), W(v.zg), B(v.zg_inf), n, k + 1, stream)
+                : sylow_hip_g2_lincomb_batch(W(v.bases), nullptr, W(v.sc), W(v.part), B(v.part_inf), rc_rows, k + 1, stream);
+    if (rc == SYLOW_HIP_OK && !direct) k_kzgpt_put_g2<<<lanes(rc_rows), dim3(BLOCK), 0, st>>>(W(v.part), B(v.part_inf), rc_rows, W(v.zg), B(v.zg_inf), n, j0);
   }
-  if (rc == SYLOW_HIP_OK) rc = sylow_hip_g1_sub_batch(c_xy, c_inf, w + v.rc, b + v.rc_inf, w + v.f, b + v.f_inf, n, stream);      // F = C - R(tau) G1gen
+  if (rc == SYLOW_HIP_OK) rc = sylow_hip_g1_sub_batch(c_xy, c_inf, W(v.rc), B(v.rc_inf), W(v.f), B(v.f_inf), n, stream);      // F = C - R(tau) G1gen
   if (rc == SYLOW_HIP_OK) {
-    k_kzgpt_pairs<<<lanes(n), dim3(BLOCK), 0, st>>>(w + v.f, b + v.f_inf, pi_xy, pi_inf, w + v.zg, b + v.zg_inf, n, w + v.p, b + v.p_inf, w + v.q, b + v.q_inf,
-                                                   w + v.offs);
-    rc = sylow_hip_multi_pairing_batch(w + v.p, b + v.p_inf, w + v.q, b + v.q_inf, w + v.offs, n, 2 * n, /*skip_infinity=*/1, nullptr, b + v.is_one, stream);
+    k_kzgpt_pairs<<<lanes(n), dim3(BLOCK), 0, st>>>(W(v.f), B(v.f_inf), pi_xy, pi_inf, W(v.zg), B(v.zg_inf), n, W(v.p), B(v.p_inf), W(v.q), B(v.q_inf),
+                                                   W(v.offs));
+    rc = sylow_hip_multi_pairing_batch(W(v.p), B(v.p_inf), W(v.q), B(v.q_inf), W(v.offs), n, 2 * n, /*skip_infinity=*/1, nullptr, B(v.is_one), stream);
   }
-  if (rc == SYLOW_HIP_OK) k_kzgpt_flags<<<lanes(n), dim3(BLOCK), 0, st>>>(b + v.is_one, b + v.distinct, n, ok);
+  if (rc == SYLOW_HIP_OK) k_kzgpt_flags<<<lanes(n), dim3(BLOCK), 0, st>>>(B(v.is_one), B(v.distinct), n, ok);
   return host::finish(rc, ws);
 }
 }  // extern "C"

@@ -128,9 +128,10 @@ static int32_t quotient(const uint64_t* coeffs, size_t len, size_t m, const uint
     LAUNCHED();
   }
   host::Lease ws;
-  int32_t rc = ws.acquire(quot_scratch_words(len, m) * sizeof(u64), st);
+  const QuotLayout l = quot_layout(len, m);
+  int32_t rc = ws.acquire(l.bytes, st);
   if (rc != SYLOW_HIP_OK) return rc;
-  u64 *totals = (u64*)ws.p, *carries = totals + 4 * items;
+  u64 *totals = ws.at<u64>(l.totals), *carries = ws.at<u64>(l.carries);
   k_kzg_quot_totals<<<dim3((unsigned)quot_grid(items)), dim3(BLOCK), 0, st>>>(coeffs, len, chunks, items, z, m, totals);
   k_kzg_quot_carry<<<dim3((unsigned)quot_grid(m)), dim3(BLOCK), 0, st>>>(totals, chunks, items, z, m, carries, q_out ? nullptr : y_out);
   if (q_out) k_kzg_quot_chunk<<<dim3((unsigned)quot_grid(items)), dim3(BLOCK), 0, st>>>(coeffs, len, chunks, items, z, m, carries, q_out, y_out);
@@ -143,11 +144,11 @@ static int32_t commit_msm_each(const uint64_t* srs, const uint64_t* coeffs, size
                                uint64_t* out_xy, uint8_t* out_inf, void* stream) {
   const hipStream_t st = (hipStream_t)stream;
   host::Lease ws;
-  const size_t w_pts = 8 * m, w_sc = canonical ? 0 : 4 * len;
-  int32_t rc = ws.acquire((w_pts + w_sc) * sizeof(u64) + m, st);
+  const MsmEachLayout l = msm_each_layout(len, m, canonical);
+  int32_t rc = ws.acquire(l.bytes, st);
   if (rc != SYLOW_HIP_OK) return rc;
-  u64 *pts = (u64*)ws.p, *sc = pts + w_pts;
-  uint8_t* inf = (uint8_t*)(sc + w_sc);
+  u64 *pts = ws.at<u64>(l.pts), *sc = ws.at<u64>(l.sc);
+  uint8_t* inf = ws.at<uint8_t>(l.inf);
   for (size_t j = 0; j < m && rc == SYLOW_HIP_OK; ++j) {
     const u64* k = coeffs + j * 4 * len;
     if (!canonical) {
@@ -161,14 +162,15 @@ static int32_t commit_msm_each(const uint64_t* srs, const uint64_t* coeffs, size
 }
 static int32_t commit_short(const uint64_t* srs, const uint64_t* coeffs, size_t len, size_t m, size_t per_chunk, uint64_t* out_xy, uint8_t* out_inf, void* stream) {
   const hipStream_t st = (hipStream_t)stream;
-  const size_t n = per_chunk * len, last = m % per_chunk;     // a shorter last chunk may cut its segments into more slices
+  const size_t last = m % per_chunk;                         // a shorter last chunk may cut its segments into more slices
   const size_t w_a = g1h::sum_segments_scratch_words(per_chunk, len), w_b = last ? g1h::sum_segments_scratch_words(last, len) : 0, w_acc = w_a > w_b ? w_a : w_b;
   const bool direct = per_chunk == m;                        // one chunk: the segmented sum writes [8][m] itself
   host::Lease ws;
-  int32_t rc = ws.acquire((4 * n + 8 * n + 8 * n + w_acc + (direct ? 0 : 8 * per_chunk)) * sizeof(u64) + n + per_chunk, st);
+  const ShortLayout l = short_layout(len, per_chunk, w_acc, direct);
+  int32_t rc = ws.acquire(l.bytes, st);
   if (rc != SYLOW_HIP_OK) return rc;
-  u64 *sc = (u64*)ws.p, *bases = sc + 4 * n, *prod = bases + 8 * n, *acc = prod + 8 * n, *part = acc + w_acc;
-  uint8_t *prod_inf = (uint8_t*)(part + (direct ? 0 : 8 * per_chunk)), *part_inf = prod_inf + n;
+  u64 *sc = ws.at<u64>(l.sc), *bases = ws.at<u64>(l.bases), *prod = ws.at<u64>(l.prod), *acc = ws.at<u64>(l.acc), *part = ws.at<u64>(l.part);
+  uint8_t *prod_inf = ws.at<uint8_t>(l.prod_inf), *part_inf = ws.at<uint8_t>(l.part_inf);
   for (size_t j0 = 0; j0 < m && rc == SYLOW_HIP_OK; j0 += per_chunk) {
     const size_t mc = m - j0 < per_chunk ? m - j0 : per_chunk, nc = mc * len;
     k_kzg_commit_prep<<<GRID(nc)>>>(srs, coeffs, len, j0, mc, sc, bases);
@@ -219,10 +221,11 @@ int32_t sylow_hip_kzg_open_batch(const uint64_t* srs_g1_xy, const uint64_t* coef
   ARGCHK(len > 0); if (!m) return SYLOW_HIP_OK;
   ARGCHK(srs_g1_xy && coeffs && z && y_out && pi_xy && pi_inf);
   host::Lease ws;
-  int32_t rc = ws.acquire(4 * len * m * sizeof(u64), (hipStream_t)stream);
+  int32_t rc = ws.acquire(kzg_plan::coeffs_bytes(len, m), (hipStream_t)stream);
   if (rc != SYLOW_HIP_OK) return rc;
-  rc = kzgp::quotient(coeffs, len, m, z, (uint64_t*)ws.p, y_out, stream);
-  if (rc == SYLOW_HIP_OK) rc = kzgp::commit(srs_g1_xy, (const uint64_t*)ws.p, len, m, /*canonical=*/true, -1, -1, pi_xy, pi_inf, stream);
+  uint64_t* q = ws.at<uint64_t>(0);
+  rc = kzgp::quotient(coeffs, len, m, z, q, y_out, stream);
+  if (rc == SYLOW_HIP_OK) rc = kzgp::commit(srs_g1_xy, q, len, m, /*canonical=*/true, -1, -1, pi_xy, pi_inf, stream);
   return host::finish(rc, ws);
 }
 int32_t sylow_hip_kzg_commit_evals_batch(const uint64_t* srs_g1_xy, const uint64_t* evals, int32_t log_n, size_t m, uint64_t* out_xy, uint8_t* out_inf, void* stream) {
@@ -231,10 +234,11 @@ int32_t sylow_hip_kzg_commit_evals_batch(const uint64_t* srs_g1_xy, const uint64
   const size_t len = (size_t)1 << log_n;
   ARGCHK(m <= (size_t)-1 / (4 * sizeof(u64)) / len);
   host::Lease ws;
-  int32_t rc = ws.acquire(4 * len * m * sizeof(u64), (hipStream_t)stream);
+  int32_t rc = ws.acquire(kzg_plan::coeffs_bytes(len, m), (hipStream_t)stream);
   if (rc != SYLOW_HIP_OK) return rc;
-  rc = sylow_hip_fr_ntt_batch(evals, log_n, m, /*inverse=*/1, nullptr, (uint64_t*)ws.p, stream);      // the coefficients, canonical
-  if (rc == SYLOW_HIP_OK) rc = kzgp::commit(srs_g1_xy, (const uint64_t*)ws.p, len, m, /*canonical=*/true, -1, -1, out_xy, out_inf, stream);
+  uint64_t* f = ws.at<uint64_t>(0);
+  rc = sylow_hip_fr_ntt_batch(evals, log_n, m, /*inverse=*/1, nullptr, f, stream);      // the coefficients, canonical
+  if (rc == SYLOW_HIP_OK) rc = kzgp::commit(srs_g1_xy, f, len, m, /*canonical=*/true, -1, -1, out_xy, out_inf, stream);
   return host::finish(rc, ws);
 }
 }  // extern "C"

@@ -1,10 +1,13 @@
-// kzg_prove_plan.hpp -- the geometry of the KZG quotient kernels and the route of a commitment (kzg_prove.hip): every decision between an
-// entry point and its kernels, plain C++ so that tests/cpp/kzg_prove_plan_test.cpp can compile it with g++ on a box without a GPU.  The
+// kzg_prove_plan.hpp -- the geometry of the KZG quotient kernels and the route of a commitment (kzg_prove.hip): every decision, byte
+// count and scratch offset between an entry point and its kernels, plain C++ so that tests/cpp/kzg_prove_plan_test.cpp can compile it with g++ on a box without a GPU.  The
 // launch code asks these functions and decides nothing itself.
 #pragma once
-#include <cstddef>
+#include "plan_base.hpp"
 
 namespace kzg_plan {
+using plan_base::Carve;
+using plan_base::mul_sat;
+using plan_base::words_of;
 // ---- the quotient: q(X) = (f(X) - f(z)) / (X - z) as the recurrence h_len = 0, h_k = f_k + z h_{k+1} --------------------------------
 // A lane owns KZG_POLY_LANE_COEFFS consecutive coefficients, a block of KZG_POLY_BLOCK lanes a chunk of KZG_POLY_CHUNK; the chunks of one
 // polynomial are joined by ONE carry level: a block per polynomial walks the chunk totals from the top in tiles of KZG_POLY_BLOCK chunks
@@ -25,8 +28,17 @@ constexpr size_t quot_grid(size_t items) { return items < KZG_QUOT_GRID_CAP ? it
 constexpr int quot_carry_levels(size_t len) { return quot_chunks(len) > 1 ? 1 : 0; }
 // serial tiles of the carry level per polynomial
 constexpr size_t quot_carry_tiles(size_t len) { return (quot_chunks(len) + KZG_POLY_BLOCK - 1) / KZG_POLY_BLOCK; }
-// u64 words of scratch the quotient leases: the chunk totals and the carries, [4][m chunks] each; none for one chunk
-constexpr size_t quot_scratch_words(size_t len, size_t m) { return quot_carry_levels(len) ? 2 * 4 * quot_items(len, m) : 0; }
+// the scratch the quotient leases: the chunk totals and the carries, [4][m chunks] each; none for one chunk
+struct QuotLayout { size_t totals, carries, bytes; };
+constexpr QuotLayout quot_layout(size_t len, size_t m) {
+  Carve c; QuotLayout l{};
+  l.totals = c.words(quot_carry_levels(len) ? mul_sat(4, quot_items(len, m)) : 0);
+  l.carries = c.words(quot_carry_levels(len) ? mul_sat(4, quot_items(len, m)) : 0);
+  l.bytes = c.at; return l;
+}
+constexpr size_t quot_scratch_words(size_t len, size_t m) { return words_of(quot_layout(len, m).bytes); }
+// bytes of m polynomials of len coefficients: the quotients of an opening, or the coefficients behind evaluations, in scratch
+constexpr size_t coeffs_bytes(size_t len, size_t m) { return mul_sat(mul_sat(32, len), m); }
 
 // ---- the commitment: out_j = sum_k f_jk srs_k ----------------------------------------------------------------------------------------
 enum class Route {
@@ -55,5 +67,32 @@ constexpr CommitPlan commit_plan(size_t len, size_t m, size_t min_len, size_t bu
   return len >= min_len ? CommitPlan{Route::BUCKET, 0}
          : short_polys_per_chunk(len, m, budget) == 0 ? CommitPlan{Route::MSM_EACH, 0}
                                                       : CommitPlan{Route::SHORT, short_polys_per_chunk(len, m, budget)};
+}
+// ---- the scratch of the commitment's routes ------------------------------------------------------------------------------------------------
+// a multi-scalar multiplication per polynomial: the m sums [8] each, one polynomial's scalars mod r [4][len] unless they are canonical as
+// they lie, and the m flags
+struct MsmEachLayout { size_t pts, sc, inf, bytes; };
+constexpr MsmEachLayout msm_each_layout(size_t len, size_t m, bool canonical) {
+  Carve c; MsmEachLayout l{};
+  l.pts = c.words(mul_sat(8, m));
+  l.sc = c.words(canonical ? 0 : mul_sat(4, len));
+  l.inf = c.bytes(m);
+  l.bytes = c.at; return l;
+}
+// the short route, n = per_chunk * len pairs: the scalars [4][n], the bases and the products [8][n] each, the segmented sum's w_acc words
+// (g1h::sum_segments_scratch_words of the larger of a whole and the last chunk), the chunk's sums [8][per_chunk] unless the one chunk writes
+// the caller's array; then the flags of the products [n] and of the sums [per_chunk]
+struct ShortLayout { size_t sc, bases, prod, acc, part, prod_inf, part_inf, bytes; };
+constexpr ShortLayout short_layout(size_t len, size_t per_chunk, size_t w_acc, bool direct) {
+  const size_t n = mul_sat(per_chunk, len);
+  Carve c; ShortLayout l{};
+  l.sc = c.words(mul_sat(4, n));
+  l.bases = c.words(mul_sat(8, n));
+  l.prod = c.words(mul_sat(8, n));
+  l.acc = c.words(w_acc);
+  l.part = c.words(direct ? 0 : mul_sat(8, per_chunk));
+  l.prod_inf = c.bytes(n);
+  l.part_inf = c.bytes(per_chunk);
+  l.bytes = c.at; return l;
 }
 }  // namespace kzg_plan

@@ -176,11 +176,12 @@ static int32_t recover(const uint64_t* y, const uint8_t* present, int log_c, int
   const hipStream_t st = (hipStream_t)stream;
   const int L = log_n(log_c, log_l);
   host::Lease ws;
-  int32_t rc = ws.acquire(recover_scratch_bytes(log_c, log_l, m), st);
+  const RecoverLayout l = recover_layout(log_c, log_l, m);
+  int32_t rc = ws.acquire(l.bytes, st);
   if (rc != SYLOW_HIP_OK) return rc;
-  u64 *consts = (u64*)ws.p, *roots = consts + CONST_WORDS, *zd = roots + root_words(log_c), *zc = zd + z_words(log_c, m), *zci = zc + z_words(log_c, m);
-  u32* flags = (u32*)(zci + z_words(log_c, m));
-  u64* buf = (u64*)flags + flag_words(m);
+  u64 *consts = ws.at<u64>(l.v.consts), *roots = ws.at<u64>(l.v.roots), *zd = ws.at<u64>(l.zd), *zc = ws.at<u64>(l.zc), *zci = ws.at<u64>(l.zci);
+  u32* flags = ws.at<u32>(l.flags);
+  u64* buf = ws.at<u64>(l.buf);
   const u64* shift = consts + CONST_SHIFT;
   const size_t total = elem_items(log_c, log_l, m);
   const dim3 eg((unsigned)elem_grid(log_c, log_l, m));
@@ -218,10 +219,10 @@ int32_t sylow_hip_kzg_recover_vanish_batch(const uint8_t* present, int32_t log_c
   const host::Range out[3] = {{(uintptr_t)zd_out, zb}, {(uintptr_t)zc_out, zb}, {(uintptr_t)status_out, sb}};
   ARGCHK(host::outputs_disjoint(in, out, disjoint));
   host::Lease ws;
-  int32_t rc = ws.acquire(vanish_scratch_bytes(log_c), (hipStream_t)stream);
+  const VanishLayout l = vanish_layout(log_c);
+  int32_t rc = ws.acquire(l.bytes, (hipStream_t)stream);
   if (rc != SYLOW_HIP_OK) return rc;
-  u64* consts = (u64*)ws.p;
-  rc = kzrc::vanish(present, log_c, log_l, m, consts, consts + CONST_WORDS, zd_out, zc_out, /*packed=*/false, status_out, stream);
+  rc = kzrc::vanish(present, log_c, log_l, m, ws.at<u64>(l.consts), ws.at<u64>(l.roots), zd_out, zc_out, /*packed=*/false, status_out, stream);
   return host::finish(rc, ws);
 }
 int32_t sylow_hip_kzg_recover_batch(const uint64_t* y, const uint8_t* present, int32_t log_c, int32_t log_l, size_t m, uint64_t* coeffs_out, uint64_t* y_out,

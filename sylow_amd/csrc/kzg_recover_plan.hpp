@@ -1,17 +1,19 @@
 // kzg_recover_plan.hpp -- the geometry of the recovery of a KZG polynomial from any half of its cosets (kzg_recover.hip): n = c l points cut
 // into c = 2^log_c cells of l = 2^log_l points, a polynomial of degree below n / 2, and per row a set M of at most c / 2 missing cells.
-// The vanishing values, the staging of the missing roots, the element-wise kernels, the status reduction and the scratch, plain C++ so
+// The vanishing values, the staging of the missing roots, the element-wise kernels, the status reduction and the scratch with its offsets, plain C++ so
 // that tests/cpp/kzg_recover_plan_test.cpp can compile it with g++ on a box without a GPU.  The launch code asks these functions and
 // decides nothing itself.
 #pragma once
 #include "ntt_plan.hpp"
 
 namespace kzg_recover_plan {
+using plan_base::Carve;
 using plan_base::SAT;
 using plan_base::add_sat;
 using plan_base::disjoint;
 using plan_base::elems;
 using plan_base::mul_sat;
+using plan_base::words_of;
 using ntt_plan::root_negated;
 using ntt_plan::root_slot;
 using ntt_plan::root_words;
@@ -96,13 +98,33 @@ constexpr size_t flag_words(size_t m) { return m / 2 + 1; }                     
 // ---- the scratch of a call, u64 words then bytes, saturated.  vanish alone: the constants and the roots.  recover: those, zd, zc and
 // zc^-1 packed, the flags, and ONE buffer [m][4][n] that the transforms ping-pong against coeffs_out (each transform leases its own table
 // and buffer on top)
-constexpr size_t vanish_scratch_words(int log_c) { return CONST_WORDS + root_words(log_c); }
-constexpr size_t vanish_scratch_bytes(int log_c) { return vanish_scratch_words(log_c) * sizeof(uint64_t); }
-constexpr size_t buffer_words(int log_c, int log_l, size_t m) { return mul_sat(elem_items(log_c, log_l, m), FR_WORDS); }
-constexpr size_t recover_scratch_words(int log_c, int log_l, size_t m) {
-  return add_sat(add_sat(vanish_scratch_words(log_c), mul_sat(z_words(log_c, m), 3)), add_sat(flag_words(m), buffer_words(log_c, log_l, m)));
+struct VanishLayout { size_t consts, roots, bytes; };
+constexpr VanishLayout vanish_layout(int log_c, Carve c = {}) {      // c: the lease it is a part of (recover's), or its own
+  VanishLayout l{};
+  l.consts = c.words(CONST_WORDS);
+  l.roots = c.words(root_words(log_c));
+  l.bytes = c.at; return l;
 }
-constexpr size_t recover_scratch_bytes(int log_c, int log_l, size_t m) { return mul_sat(recover_scratch_words(log_c, log_l, m), sizeof(uint64_t)); }
+constexpr size_t vanish_scratch_bytes(int log_c) { return vanish_layout(log_c).bytes; }
+constexpr size_t vanish_scratch_words(int log_c) { return words_of(vanish_scratch_bytes(log_c)); }
+constexpr size_t buffer_words(int log_c, int log_l, size_t m) { return mul_sat(elem_items(log_c, log_l, m), FR_WORDS); }
+struct RecoverLayout {
+  VanishLayout v;      // offsets in this lease; v.bytes is where it ends
+  size_t zd, zc, zci, flags, buf, bytes;
+};
+constexpr RecoverLayout recover_layout(int log_c, int log_l, size_t m) {
+  Carve c; RecoverLayout l{};
+  l.v = vanish_layout(log_c, c);
+  c.at = l.v.bytes;
+  l.zd = c.words(z_words(log_c, m));
+  l.zc = c.words(z_words(log_c, m));
+  l.zci = c.words(z_words(log_c, m));
+  l.flags = c.words(flag_words(m));
+  l.buf = c.words(buffer_words(log_c, log_l, m));
+  l.bytes = c.at; return l;
+}
+constexpr size_t recover_scratch_bytes(int log_c, int log_l, size_t m) { return recover_layout(log_c, log_l, m).bytes; }
+constexpr size_t recover_scratch_words(int log_c, int log_l, size_t m) { return words_of(recover_scratch_bytes(log_c, log_l, m)); }
 constexpr bool scratch_ok(size_t bytes) { return bytes <= SAT / 2; }
 constexpr int transforms(bool with_y) { return with_y ? 4 : 3; }                       // sylow_hip_fr_ntt_batch calls: the floor of a call
 }  // namespace kzg_recover_plan

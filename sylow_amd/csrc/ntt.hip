@@ -149,9 +149,10 @@ static int32_t transform(const uint64_t* in, int log_n, size_t m, bool inverse, 
   const bool shifted = shift != nullptr;
   const int n_pass = passes(log_n, stages), n_steps = steps(log_n, stages, inverse, shifted);
   host::Lease ws;
-  int32_t rc = ws.acquire(mul_sat(scratch_words(log_n, m, n_steps), sizeof(u64)), st);
+  const ScratchLayout l = scratch_layout(log_n, m, n_steps);
+  int32_t rc = ws.acquire(l.bytes, st);
   if (rc != SYLOW_HIP_OK) return rc;
-  u64 *consts = (u64*)ws.p, *table = consts + NTT_CONST_WORDS, *buf = table + table_words(log_n);
+  u64 *consts = ws.at<u64>(l.consts), *table = ws.at<u64>(l.table), *buf = ws.at<u64>(l.buf);
   if (n_pass || shifted)
     k_ntt_table<<<dim3((unsigned)grid(table_blocks(log_n))), dim3(BLOCK), 0, st>>>(log_n, table, shift, inverse ? 1 : 0, consts);
   const Words4 ni = inverse ? n_inverse(log_n) : Words4{{1, 0, 0, 0}};

@@ -1,14 +1,16 @@
 // ntt_plan.hpp -- the geometry of the batched radix-2 transform over Fr (ntt.hip): passes, stages per pass, tiles, grids, the twiddle table,
-// the ping-pong and the scratch, plain C++ so that tests/cpp/ntt_plan_test.cpp can compile it with g++ on a box without a GPU.  The launch
+// the ping-pong and the scratch with its offsets, plain C++ so that tests/cpp/ntt_plan_test.cpp can compile it with g++ on a box without a GPU.  The launch
 // code asks these functions and decides nothing itself.
 #pragma once
 #include "plan_base.hpp"
 
 namespace ntt_plan {
+using plan_base::Carve;
 using plan_base::SAT;
 using plan_base::add_sat;
 using plan_base::elems;
 using plan_base::mul_sat;
+using plan_base::words_of;
 // r - 1 = 2^28 * odd: radix-2 domains up to 2^28
 constexpr int NTT_LOG_N_MAX = 28;
 constexpr int NTT_BLOCK = 256;                   // == BLOCK of common.hpp (ntt.hip asserts it)
@@ -70,10 +72,16 @@ constexpr bool step_writes_out(int n_steps, int i) { return ((n_steps - 1 - i) &
 constexpr bool needs_buffer(int n_steps) { return n_steps >= 2; }
 // u64 words of one buffer of the batch, [m][4][n], saturated
 constexpr size_t batch_words(int log_n, size_t m) { return mul_sat(mul_sat(4, elems(log_n)), m); }
-// u64 words a call leases: the shift, the table, the ping-pong buffer
-constexpr size_t scratch_words(int log_n, size_t m, int n_steps) {
-  return add_sat(NTT_CONST_WORDS + table_words(log_n), needs_buffer(n_steps) ? batch_words(log_n, m) : 0);
+// what a call leases: the shift, the table, the ping-pong buffer
+struct ScratchLayout { size_t consts, table, buf, bytes; };
+constexpr ScratchLayout scratch_layout(int log_n, size_t m, int n_steps) {
+  Carve c; ScratchLayout l{};
+  l.consts = c.words(NTT_CONST_WORDS);
+  l.table = c.words(table_words(log_n));
+  l.buf = c.words(needs_buffer(n_steps) ? batch_words(log_n, m) : 0);
+  l.bytes = c.at; return l;
 }
+constexpr size_t scratch_words(int log_n, size_t m, int n_steps) { return words_of(scratch_layout(log_n, m, n_steps).bytes); }
 
 // ---- n^-1 = r - ((r - 1) >> log_n): n (-(r - 1) / n) = 1 - r = 1 mod r, and 2^log_n divides r - 1 for log_n <= 28 ------------------------
 struct Words4 {

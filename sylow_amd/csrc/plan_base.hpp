@@ -9,6 +9,17 @@ namespace plan_base {
 constexpr size_t SAT = (size_t)-1;               // "does not fit size_t": an entry point refuses it before any lease
 constexpr size_t mul_sat(size_t a, size_t b) { return b && a > SAT / b ? SAT : a * b; }
 constexpr size_t add_sat(size_t a, size_t b) { return a > SAT - b ? SAT : a + b; }
+// ---- the regions of ONE scratch lease, listed once: a plan header walks a Carve over the lease's regions in order, keeps the byte offset
+// each call returns and, last, `at`: the byte count acquire() receives.  The launch code takes its pointers from the same offsets
+// (host::Lease::at), so a lease has one description.  Saturates like the sizes above and stays SAT; a word region on an offset that is no
+// multiple of 8 makes the whole lease SAT, which every entry point refuses.
+struct Carve {
+  size_t at = 0;
+  constexpr size_t bytes(size_t n) { const size_t off = at; at = add_sat(at, n); return off; }
+  constexpr size_t words(size_t n) { if (at % 8) at = SAT; return bytes(mul_sat(n, 8)); }     // n u64
+  constexpr void round() { at = at > SAT - 7 ? SAT : (at + 7) & ~(size_t)7; }                 // up to a word
+};
+constexpr size_t words_of(size_t bytes) { return bytes == SAT ? SAT : bytes / 8; }            // a layout's bytes as u64 words, SAT kept
 constexpr size_t elems(int log_n) { return (size_t)1 << log_n; }
 constexpr bool max_blocks_ok(long long max_blocks) { return max_blocks != 0; }      // a pin: < 0 the default, > 0 a cap; no block is refused
 // [a, a + a_bytes) and [b, b + b_bytes) share no byte and neither lies inside the other: an empty range inside a non-empty one collides

@@ -304,14 +304,14 @@ struct Job {
   u64 *evals_out, *w_zeta_xy, *w_omega_xy;
   uint8_t *w_zeta_inf, *w_omega_inf, *status;
 };
-// instances s0 .. s0 + c - 1 through the lease ws: pts | partials | weights | F [c][4][len_f] | Z the same | F(zeta) [4][c] | z(zeta w_n) [4][c] |
-// the two proofs [8][c] each | their flags, every part sized for a full chunk
-static int32_t chunk(const Job& j, size_t s0, size_t c, u64* ws, void* stream) {
+// instances s0 .. s0 + c - 1 through the lease ws (open_layout): every part sized for a full chunk
+static int32_t chunk(const Job& j, size_t s0, size_t c, const host::Lease& ws, void* stream) {
   const hipStream_t st = (hipStream_t)stream;
-  const size_t n = elems(j.log_n), N = elems(log_big(j.log_n, j.log_e)), longest = longest_row(j.log_n, j.len_w, j.len_z), poly = FR_WORDS * j.len_f * j.mc;
-  u64 *pts = ws, *partials = pts + point_words(j.mc), *weights = partials + eval_partial_words(eval_slots(j.W), longest, j.mc),
-      *F = weights + weight_words(j.log_e, j.W, j.mc), *Z = F + poly, *yf = Z + poly, *yz = yf + FR_WORDS * j.mc, *p1 = yz + FR_WORDS * j.mc, *p2 = p1 + 8 * j.mc;
-  uint8_t *f1 = (uint8_t*)(p2 + 8 * j.mc), *f2 = f1 + j.mc;
+  const size_t n = elems(j.log_n), N = elems(log_big(j.log_n, j.log_e)), longest = longest_row(j.log_n, j.len_w, j.len_z);
+  const OpenLayout l = open_layout(j.log_n, j.log_e, j.W, j.len_w, j.len_z, j.len_f, j.mc);
+  u64 *pts = ws.at<u64>(l.ev.pts), *partials = ws.at<u64>(l.ev.partials), *weights = ws.at<u64>(l.weights), *F = ws.at<u64>(l.F), *Z = ws.at<u64>(l.Z),
+      *yf = ws.at<u64>(l.yf), *yz = ws.at<u64>(l.yz), *p1 = ws.at<u64>(l.p1), *p2 = ws.at<u64>(l.p2);
+  uint8_t *f1 = ws.at<uint8_t>(l.f1), *f2 = ws.at<uint8_t>(l.f2);
   const u64 *wires = j.wires + s0 * (size_t)j.W * FR_WORDS * j.len_w, *z = j.z + s0 * FR_WORDS * j.len_z;
   k_po_points<<<dim3(lane_grid(c, -1)), dim3(BLOCK), 0, st>>>(j.zeta, j.m, s0, c, j.log_n, pts);
   const Rows rows = {wires, j.ctable + row_sigma(j.W, 0) * FR_WORDS * n, z, j.pi ? j.pi + s0 * FR_WORDS * n : nullptr, j.len_w, j.len_z, n, j.W, j.W - 1, 1, 1};
@@ -355,9 +355,10 @@ int32_t sylow_popen_evaluate_batch_tuned(const uint64_t* ctable, const uint64_t*
   ARGCHK(host::outputs_disjoint(in, outs, disjoint));
   const hipStream_t st = (hipStream_t)stream;
   host::Lease ws;
-  int32_t rc = ws.acquire(scratch * sizeof(u64), st);
+  const EvaluateLayout l = evaluate_layout(log_n, W, len_w, len_z, m);
+  int32_t rc = ws.acquire(l.bytes, st);
   if (rc != SYLOW_HIP_OK) return rc;
-  u64 *pts = (u64*)ws.p, *partials = pts + point_words(m);
+  u64 *pts = ws.at<u64>(l.pts), *partials = ws.at<u64>(l.partials);
   po::k_po_points<<<dim3(po::lane_grid(m, max_blocks)), dim3(BLOCK), 0, st>>>(zeta, m, 0, m, log_n, pts);
   const po::Rows rows = {wires, ctable + row_sigma(W, 0) * FR_WORDS * n, z, pi, len_w, len_z, n, W, W - 1, 1, 1};
   po::eval_launch(rows, pts, m, longest_row(log_n, len_w, len_z), max_blocks, partials, evals_out, evals_count(W, m), 0, st);
@@ -389,11 +390,12 @@ int32_t sylow_popen_linearise_batch_tuned(const uint64_t* ctable, const uint64_t
   ARGCHK(host::outputs_disjoint(in, outs, disjoint));
   const hipStream_t st = (hipStream_t)stream;
   host::Lease ws;
-  int32_t rc = ws.acquire(scratch * sizeof(u64), st);
+  const LineariseLayout l = linearise_layout(log_n, log_e, W, len_z, len_out, m, own_r);
+  int32_t rc = ws.acquire(l.bytes, st);
   if (rc != SYLOW_HIP_OK) return rc;
   const size_t r_len = own_r ? len_r(log_n, len_z) : len_out;
-  u64 *pts = (u64*)ws.p, *weights = pts + point_words(m), *rz = weights + weight_words(log_e, W, m), *partials = rz + FR_WORDS * m,
-      *r_buf = own_r ? partials + eval_partial_words(1, r_len, m) : r_out;
+  u64 *pts = ws.at<u64>(l.pts), *weights = ws.at<u64>(l.weights), *rz = ws.at<u64>(l.rz), *partials = ws.at<u64>(l.partials),
+      *r_buf = own_r ? ws.at<u64>(l.r_buf) : r_out;
   po::k_po_points<<<dim3(po::lane_grid(m, max_blocks)), dim3(BLOCK), 0, st>>>(zeta, m, 0, m, log_n, pts);
   po::k_po_consts<<<dim3((unsigned)grid(m, max_blocks)), dim3(BLOCK), 0, st>>>(evals, shifts, beta, gamma, alpha, zeta, f_out ? v : nullptr, m, 0, m, log_n, log_e, W, weights);
   const po::Fold f = {ctable, wires, z, t, weights, len_w, len_z, r_len, len_out, r_buf, f_out, nullptr, log_n, log_e, W};
@@ -445,7 +447,7 @@ int32_t sylow_popen_open_batch(const uint64_t* srs_g1_xy, const uint64_t* ctable
   if (rc != SYLOW_HIP_OK) return rc;
   const po::Job job = {srs_g1_xy, ctable, wires, z, pi, t, shifts, beta, gamma, alpha, zeta, v, len_w, len_z, len_f, m, mc, log_n, log_e, W,
                        evals_out, w_zeta_xy, w_omega_xy, w_zeta_inf, w_omega_inf, status};
-  for (size_t s0 = 0; s0 < m && rc == SYLOW_HIP_OK; s0 += mc) rc = po::chunk(job, s0, chunk_size(m, mc, s0), (u64*)ws.p, stream);
+  for (size_t s0 = 0; s0 < m && rc == SYLOW_HIP_OK; s0 += mc) rc = po::chunk(job, s0, chunk_size(m, mc, s0), ws, stream);
   return host::finish(rc, ws);
 }
 }  // extern "C"

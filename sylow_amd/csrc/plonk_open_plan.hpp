@@ -1,6 +1,6 @@
 // plonk_open_plan.hpp -- the geometry of PLONK's closing rounds (plonk_open.hip): the rows of the per-circuit coefficient table, the slots of
 // an instance's evaluations and of its weight vector, the items, chunks and tiles of the three kernels, the lengths of r and F, the chunks of
-// whole instances under a scratch limit and every byte count, plain C++ so that tests/cpp/plonk_open_plan_test.cpp can compile it with g++ on a
+// whole instances under a scratch limit and every byte count and scratch offset, plain C++ so that tests/cpp/plonk_open_plan_test.cpp can compile it with g++ on a
 // box without a GPU.  The launch code asks these functions and decides nothing itself.
 #pragma once
 #include "fr_scan_plan.hpp"
@@ -9,12 +9,14 @@
 #include "plan_base.hpp"
 
 namespace plonk_open_plan {
+using plan_base::Carve;
 using plan_base::SAT;
 using plan_base::add_sat;
 using plan_base::disjoint;
 using plan_base::elems;
 using plan_base::max_blocks_ok;
 using plan_base::mul_sat;
+using plan_base::words_of;
 constexpr int PO_BLOCK = 256;                    // == BLOCK of common.hpp (plonk_open.hip asserts it): a lane per column, a tile per block
 constexpr int PO_FLUSH = 16;                     // products an accumulator adds unreduced between two Barrett reductions (bn254_fr_acc.hpp)
 constexpr int PO_WEIGHT_ROUND = 16;              // weights of an instance a block stages in LDS at a time
@@ -77,8 +79,16 @@ constexpr size_t eval_partial_words(size_t rows, size_t longest, size_t m) { ret
 // the two points of an instance, [2][4][m]: zeta and zeta w_n, canonical
 constexpr size_t point_words(size_t m) { return mul_sat(2 * FR_WORDS, m); }
 constexpr size_t longest_row(int log_n, size_t len_w, size_t len_z) { return max2(max2(elems(log_n), len_w), len_z); }
+// the evaluate entry leases the points and the partials; c: the lease they are a part of (the full route's), or their own
+struct EvaluateLayout { size_t pts, partials, bytes; };
+constexpr EvaluateLayout evaluate_layout(int log_n, int wires, size_t len_w, size_t len_z, size_t m, Carve c = {}) {
+  EvaluateLayout l{};
+  l.pts = c.words(point_words(m));
+  l.partials = c.words(eval_partial_words(eval_slots(wires), longest_row(log_n, len_w, len_z), m));
+  l.bytes = c.at; return l;
+}
 constexpr size_t evaluate_scratch_words(int log_n, int wires, size_t len_w, size_t len_z, size_t m) {
-  return add_sat(point_words(m), eval_partial_words(eval_slots(wires), longest_row(log_n, len_w, len_z), m));
+  return words_of(evaluate_layout(log_n, wires, len_w, len_z, m).bytes);
 }
 constexpr bool scratch_ok(size_t words) { return words <= SAT / 2 / sizeof(uint64_t); }
 
@@ -110,23 +120,52 @@ constexpr size_t tiles(size_t len) { return ceil_div(len, PO_BLOCK); }
 constexpr size_t items(size_t len, size_t m) { return mul_sat(tiles(len), m); }
 constexpr size_t item_instance(size_t item, size_t n_tiles) { return item / n_tiles; }
 constexpr size_t column(size_t item, size_t n_tiles, int lane) { return item % n_tiles * PO_BLOCK + (size_t)lane; }
-// the linearise entry leases: the points, the weights, r itself when the caller takes only F, the partials of r's evaluation and r(zeta) [4][m]
-constexpr size_t linearise_scratch_words(int log_n, int log_e, int wires, size_t len_z, size_t len_out, size_t m, bool own_r) {
+// the linearise entry leases: the points, the weights, r(zeta) [4][m], the partials of r's evaluation and r itself when the caller takes only F
+struct LineariseLayout { size_t pts, weights, rz, partials, r_buf, bytes; };
+constexpr LineariseLayout linearise_layout(int log_n, int log_e, int wires, size_t len_z, size_t len_out, size_t m, bool own_r) {
   const size_t r_row = own_r ? len_r(log_n, len_z) : len_out;
-  return add_sat(add_sat(add_sat(point_words(m), weight_words(log_e, wires, m)), own_r ? mul_sat(mul_sat(r_row, FR_WORDS), m) : 0),
-                 add_sat(eval_partial_words(1, r_row, m), mul_sat(FR_WORDS, m)));
+  Carve c; LineariseLayout l{};
+  l.pts = c.words(point_words(m));
+  l.weights = c.words(weight_words(log_e, wires, m));
+  l.rz = c.words(mul_sat(FR_WORDS, m));
+  l.partials = c.words(eval_partial_words(1, r_row, m));
+  l.r_buf = c.words(own_r ? mul_sat(mul_sat(r_row, FR_WORDS), m) : 0);
+  l.bytes = c.at; return l;
+}
+constexpr size_t linearise_scratch_words(int log_n, int log_e, int wires, size_t len_z, size_t len_out, size_t m, bool own_r) {
+  return words_of(linearise_layout(log_n, log_e, wires, len_z, len_out, m, own_r).bytes);
 }
 
 // ---- the full route: a chunk of mc whole instances leases the points, the partials, the weights, F and the padded z [mc][4][len_srs] each,
 // F(zeta) and z(zeta w_n) [4][mc] each, the two proofs [8][mc] each and their flags; sylow_hip_kzg_open_batch leases a quotient buffer
 // [mc][4][len_srs] on top, which the budget counts (the commitment under it plans its own chunks against the same limit) -------------------
-constexpr size_t flag_words(size_t mc) { return ceil_div(mul_sat(2, mc), sizeof(uint64_t)); }
-constexpr size_t open_chunk_words(int log_n, int log_e, int wires, size_t len_w, size_t len_z, size_t len_srs, size_t mc) {
-  const size_t polys = mul_sat(mul_sat(mul_sat(2, FR_WORDS), len_srs), mc), small = mul_sat(2 * FR_WORDS + 2 * 8, mc);
-  return add_sat(add_sat(add_sat(evaluate_scratch_words(log_n, wires, len_w, len_z, mc), weight_words(log_e, wires, mc)), add_sat(polys, small)), flag_words(mc));
+struct OpenLayout {
+  EvaluateLayout ev;      // offsets in this lease; ev.bytes is where it ends
+  size_t weights, F, Z, yf, yz, p1, p2, f1, f2, bytes;
+};
+constexpr OpenLayout open_layout(int log_n, int log_e, int wires, size_t len_w, size_t len_z, size_t len_srs, size_t mc) {
+  Carve c; OpenLayout l{};
+  l.ev = evaluate_layout(log_n, wires, len_w, len_z, mc, c);
+  c.at = l.ev.bytes;
+  l.weights = c.words(weight_words(log_e, wires, mc));
+  l.F = c.words(mul_sat(mul_sat(FR_WORDS, len_srs), mc));
+  l.Z = c.words(mul_sat(mul_sat(FR_WORDS, len_srs), mc));
+  l.yf = c.words(mul_sat(FR_WORDS, mc));
+  l.yz = c.words(mul_sat(FR_WORDS, mc));
+  l.p1 = c.words(mul_sat(8, mc));
+  l.p2 = c.words(mul_sat(8, mc));
+  l.f1 = c.bytes(mc);
+  l.f2 = c.bytes(mc);
+  c.round();
+  l.bytes = c.at; return l;
 }
 constexpr size_t open_chunk_bytes(int log_n, int log_e, int wires, size_t len_w, size_t len_z, size_t len_srs, size_t mc) {
-  return mul_sat(open_chunk_words(log_n, log_e, wires, len_w, len_z, len_srs, mc), sizeof(uint64_t));
+  return open_layout(log_n, log_e, wires, len_w, len_z, len_srs, mc).bytes;
+}
+// the u64 words its two flags an instance take: the same at every shape, read off the smallest one
+constexpr size_t flag_words(size_t mc) { return words_of(open_layout(0, 0, PO_WIRES_MIN, 1, 1, 1, mc).bytes - open_layout(0, 0, PO_WIRES_MIN, 1, 1, 1, mc).f1); }
+constexpr size_t open_chunk_words(int log_n, int log_e, int wires, size_t len_w, size_t len_z, size_t len_srs, size_t mc) {
+  return words_of(open_chunk_bytes(log_n, log_e, wires, len_w, len_z, len_srs, mc));
 }
 constexpr size_t open_budget_bytes(int log_n, int log_e, int wires, size_t len_w, size_t len_z, size_t len_srs, size_t mc) {
   return mul_sat(add_sat(open_chunk_words(log_n, log_e, wires, len_w, len_z, len_srs, mc), mul_sat(mul_sat(FR_WORDS, len_srs), mc)), sizeof(uint64_t));

@@ -166,18 +166,18 @@ static void pad_launch(const u64* src, size_t len, size_t arrays, size_t per, si
 
 struct Job {
   const u64 *table, *wires, *z, *pi, *shifts, *beta, *gamma, *alpha;
-  size_t len_w, len_z, m, consts_words;               // consts_words: of the largest chunk, which fixes the layout of the lease
+  size_t len_w, len_z, m, mc_lease;                   // mc_lease: the instances of the largest chunk, which fixes the layout of the lease
   int log_n, log_e, W;
   long long max_blocks;
   u64* t_out;
 };
-// instances s0 .. s0 + mc - 1 through the lease ws: g [4] | roots | consts | A [mc][cols][4][N] | B the same
-static int32_t chunk(const Job& j, size_t s0, size_t mc, u64* ws, void* stream) {
+// instances s0 .. s0 + mc - 1 through the lease ws (chunk_layout): A [mc][cols][4][N] | B the same
+static int32_t chunk(const Job& j, size_t s0, size_t mc, const host::Lease& ws, void* stream) {
   const hipStream_t st = (hipStream_t)stream;
   const int lb = log_big(j.log_n, j.log_e);
   const size_t N = elems(lb), n = elems(j.log_n), row = row_words(j.log_n, j.log_e), cols = columns(j.W, j.pi != nullptr);
-  u64 *g = ws, *roots = g + PQ_SHIFT_WORDS, *consts = roots + ntt_plan::root_words(lb), *A = consts + j.consts_words,
-      *B = A + chunk_buffer_words(j.log_n, j.log_e, cols, mc);
+  const ChunkLayout l = chunk_layout(j.log_n, j.log_e, j.W, cols, j.mc_lease, mc);
+  u64 *g = ws.at<u64>(l.g), *roots = ws.at<u64>(l.roots), *consts = ws.at<u64>(l.consts), *A = ws.at<u64>(l.a), *B = ws.at<u64>(l.b);
   pad_launch(j.wires + s0 * (size_t)j.W * FR_WORDS * j.len_w, j.len_w, mc * (size_t)j.W, (size_t)j.W, cols, 0, j.log_n, j.log_e, j.max_blocks, A, st);
   pad_launch(j.z + s0 * FR_WORDS * j.len_z, j.len_z, mc, 1, cols, col_z(j.W), j.log_n, j.log_e, j.max_blocks, A, st);
   if (j.pi) pad_launch(j.pi + s0 * FR_WORDS * n, n, mc, 1, cols, col_pi(j.W), j.log_n, j.log_e, j.max_blocks, A, st);
@@ -202,10 +202,10 @@ int32_t sylow_plonk_quotient_prepare(const uint64_t* selectors, const uint64_t* 
   const int lb = log_big(log_n, log_e);
   const size_t n = elems(log_n), rows = table_rows(W);
   host::Lease ws;
-  int32_t rc = ws.acquire(prepare_scratch_bytes(log_n, log_e, W), st);
+  const PrepareLayout l = prepare_layout(log_n, log_e, W);
+  int32_t rc = ws.acquire(l.bytes, st);
   if (rc != SYLOW_HIP_OK) return rc;
-  u64 *g = (u64*)ws.p, *roots = g + PQ_SHIFT_WORDS, *coeff = roots + ntt_plan::root_words(lb), *l1 = coeff + prepare_coeff_words(log_n, W),
-      *padded = l1 + FR_WORDS * n;
+  u64 *g = ws.at<u64>(l.g), *roots = ws.at<u64>(l.roots), *coeff = ws.at<u64>(l.coeff), *l1 = ws.at<u64>(l.l1), *padded = ws.at<u64>(l.padded);
   pq::k_pq_shift<<<1, 64, 0, st>>>(g);
   pq::k_pq_l1<<<dim3((unsigned)grid(tiles(log_n, 0), -1)), dim3(BLOCK), 0, st>>>(l1, n);
   rc = sylow_hip_fr_ntt_batch(selectors, log_n, (size_t)W + 2, /*inverse=*/1, nullptr, coeff, stream);
@@ -238,9 +238,10 @@ int32_t sylow_plonk_quotient_evals_batch_tuned(const uint64_t* table, const uint
   const hipStream_t st = (hipStream_t)stream;
   const int lb = log_big(log_n, log_e);
   host::Lease ws;
-  int32_t rc = ws.acquire(evals_scratch_bytes(log_n, log_e, W, m), st);
+  const EvalsLayout l = evals_layout(log_n, log_e, W, m);
+  int32_t rc = ws.acquire(l.bytes, st);
   if (rc != SYLOW_HIP_OK) return rc;
-  u64 *roots = (u64*)ws.p, *consts = roots + ntt_plan::root_words(lb);
+  u64 *roots = ws.at<u64>(l.roots), *consts = ws.at<u64>(l.consts);
   if (lb >= 1) rc = ntth::build_table(lb, roots, stream);
   if (rc == SYLOW_HIP_OK) pq::fused_launch(table, wires_ext, z_ext, pi_ext, 0, shifts, beta, gamma, alpha, m, 0, m, consts, roots, log_n, log_e, W, max_blocks, t_ext_out, st);
   return host::finish(rc, ws);
@@ -273,13 +274,13 @@ int32_t sylow_plonk_quotient_batch_tuned(const uint64_t* table, const uint64_t* 
   const hipStream_t st = (hipStream_t)stream;
   const int lb = log_big(log_n, log_e);
   host::Lease ws;
-  int32_t rc = ws.acquire(chunk_bytes(log_n, log_e, W, cols, mc), st);
+  const ChunkLayout l = chunk_layout(log_n, log_e, W, cols, mc, mc);
+  int32_t rc = ws.acquire(l.bytes, st);
   if (rc != SYLOW_HIP_OK) return rc;
-  u64* g = (u64*)ws.p;
-  pq::k_pq_shift<<<1, 64, 0, st>>>(g);
-  if (lb >= 1) rc = ntth::build_table(lb, g + PQ_SHIFT_WORDS, stream);
-  const pq::Job job = {table, wires, z, pi, shifts, beta, gamma, alpha, len_w, len_z, m, consts_words(W, mc), log_n, log_e, W, max_blocks, t_out};
-  for (size_t s0 = 0; s0 < m && rc == SYLOW_HIP_OK; s0 += mc) rc = pq::chunk(job, s0, chunk_size(m, mc, s0), g, stream);
+  pq::k_pq_shift<<<1, 64, 0, st>>>(ws.at<u64>(l.g));
+  if (lb >= 1) rc = ntth::build_table(lb, ws.at<u64>(l.roots), stream);
+  const pq::Job job = {table, wires, z, pi, shifts, beta, gamma, alpha, len_w, len_z, m, mc, log_n, log_e, W, max_blocks, t_out};
+  for (size_t s0 = 0; s0 < m && rc == SYLOW_HIP_OK; s0 += mc) rc = pq::chunk(job, s0, chunk_size(m, mc, s0), ws, stream);
   if (rc == SYLOW_HIP_OK) {
     const size_t tail = tail_len(log_n, log_e, W, len_w, len_z), n_tiles = tail_tiles(tail), its = tail_items(tail, m);
     pq::k_pq_status_clear<<<dim3((unsigned)grid(tail_tiles(m), max_blocks)), dim3(BLOCK), 0, st>>>(status, m);

@@ -1,6 +1,6 @@
 // plonk_quotient_plan.hpp -- the geometry of PLONK's quotient polynomial (plonk_quotient.hip): the rows of the per-circuit table, the items
 // and tiles of the fused kernel, the degree bound and the tail the status reads, the chunks of whole instances under a scratch limit and
-// every byte count, plain C++ so that tests/cpp/plonk_quotient_plan_test.cpp can compile it with g++ on a box without a GPU.  The launch
+// every byte count and scratch offset, plain C++ so that tests/cpp/plonk_quotient_plan_test.cpp can compile it with g++ on a box without a GPU.  The launch
 // code asks these functions and decides nothing itself.
 #pragma once
 #include "fr_scan_plan.hpp"
@@ -8,12 +8,14 @@
 #include "plan_base.hpp"
 
 namespace plonk_quotient_plan {
+using plan_base::Carve;
 using plan_base::SAT;
 using plan_base::add_sat;
 using plan_base::disjoint;
 using plan_base::elems;
 using plan_base::max_blocks_ok;
 using plan_base::mul_sat;
+using plan_base::words_of;
 constexpr int PQ_BLOCK = 256;                    // == BLOCK of common.hpp (plonk_quotient.hip asserts it): a lane per point, a tile per block
 constexpr int PQ_FLUSH = 16;                     // products the gate sum adds unreduced between two Barrett reductions (bn254_fr_acc.hpp)
 constexpr uint64_t PQ_COSET_SHIFT = 5;           // K = 5 <w_N>: the shift of the Groth16 quotient; X^n - 1 never vanishes on K
@@ -51,11 +53,18 @@ constexpr size_t sigma_bytes(int log_n, int wires) { return (size_t)wires * FR_W
 // of the N / 2 roots and the 4 words of the shift; the transforms lease their own on top
 constexpr size_t PQ_SHIFT_WORDS = 4;
 constexpr size_t prepare_coeff_words(int log_n, int wires) { return table_rows(wires) * FR_WORDS * elems(log_n); }
-constexpr size_t prepare_scratch_words(int log_n, int log_e, int wires) {
-  return prepare_coeff_words(log_n, wires) + FR_WORDS * elems(log_n) + zinv_offset_words(log_n, log_e, wires) + ntt_plan::root_words(log_big(log_n, log_e)) +
-         PQ_SHIFT_WORDS;
+struct PrepareLayout { size_t g, roots, coeff, l1, padded, bytes; };
+constexpr PrepareLayout prepare_layout(int log_n, int log_e, int wires) {
+  Carve c; PrepareLayout l{};
+  l.g = c.words(PQ_SHIFT_WORDS);
+  l.roots = c.words(ntt_plan::root_words(log_big(log_n, log_e)));
+  l.coeff = c.words(prepare_coeff_words(log_n, wires));
+  l.l1 = c.words(FR_WORDS * elems(log_n));
+  l.padded = c.words(zinv_offset_words(log_n, log_e, wires));
+  l.bytes = c.at; return l;
 }
-constexpr size_t prepare_scratch_bytes(int log_n, int log_e, int wires) { return prepare_scratch_words(log_n, log_e, wires) * sizeof(uint64_t); }
+constexpr size_t prepare_scratch_bytes(int log_n, int log_e, int wires) { return prepare_layout(log_n, log_e, wires).bytes; }
+constexpr size_t prepare_scratch_words(int log_n, int log_e, int wires) { return words_of(prepare_scratch_bytes(log_n, log_e, wires)); }
 
 // ---- the fused kernel: items are (instance, tile of PQ_BLOCK points), instance-major, a lane per point ----------------------------------
 constexpr size_t tiles(int log_n, int log_e) { return elems(log_big(log_n, log_e)) / PQ_BLOCK + (elems(log_big(log_n, log_e)) % PQ_BLOCK ? 1 : 0); }
@@ -75,9 +84,14 @@ constexpr size_t PQ_CHALLENGE_SLOTS = 4;
 constexpr size_t const_slots(int wires) { return (size_t)wires + PQ_CHALLENGE_SLOTS; }
 constexpr size_t consts_words(int wires, size_t m) { return mul_sat(mul_sat(const_slots(wires), FR_WORDS), m); }
 // the evaluation entry leases the table of the N / 2 roots and the constants
-constexpr size_t evals_scratch_bytes(int log_n, int log_e, int wires, size_t m) {
-  return mul_sat(add_sat(ntt_plan::root_words(log_big(log_n, log_e)), consts_words(wires, m)), sizeof(uint64_t));
+struct EvalsLayout { size_t roots, consts, bytes; };
+constexpr EvalsLayout evals_layout(int log_n, int log_e, int wires, size_t m) {
+  Carve c; EvalsLayout l{};
+  l.roots = c.words(ntt_plan::root_words(log_big(log_n, log_e)));
+  l.consts = c.words(consts_words(wires, m));
+  l.bytes = c.at; return l;
 }
+constexpr size_t evals_scratch_bytes(int log_n, int log_e, int wires, size_t m) { return evals_layout(log_n, log_e, wires, m).bytes; }
 constexpr bool scratch_ok(size_t bytes) { return bytes <= SAT / 2; }
 
 // ---- the degree bound of the numerator and the tail of t the status reads ----------------------------------------------------------------
@@ -109,11 +123,20 @@ constexpr size_t coeff_bytes(size_t len, size_t arrays) { return mul_sat(mul_sat
 constexpr size_t pad_tiles(int log_n, int log_e, size_t cols, size_t mc) { return mul_sat(mul_sat(tiles(log_n, log_e), cols), mc); }
 // u64 words of one of the two buffers
 constexpr size_t chunk_buffer_words(int log_n, int log_e, size_t cols, size_t mc) { return mul_sat(mul_sat(row_words(log_n, log_e), cols), mc); }
-// u64 words the call leases for a chunk: the shift, the roots, the constants, the two buffers
-constexpr size_t chunk_words(int log_n, int log_e, int wires, size_t cols, size_t mc) {
-  return add_sat(add_sat(PQ_SHIFT_WORDS + ntt_plan::root_words(log_big(log_n, log_e)), consts_words(wires, mc)), mul_sat(2, chunk_buffer_words(log_n, log_e, cols, mc)));
+// what the call leases for its chunks: the shift, the roots, the constants of the largest chunk (mc_lease instances, which fixes where the
+// buffers start), the two buffers of this chunk's mc instances
+struct ChunkLayout { size_t g, roots, consts, a, b, bytes; };
+constexpr ChunkLayout chunk_layout(int log_n, int log_e, int wires, size_t cols, size_t mc_lease, size_t mc) {
+  Carve c; ChunkLayout l{};
+  l.g = c.words(PQ_SHIFT_WORDS);
+  l.roots = c.words(ntt_plan::root_words(log_big(log_n, log_e)));
+  l.consts = c.words(consts_words(wires, mc_lease));
+  l.a = c.words(chunk_buffer_words(log_n, log_e, cols, mc));
+  l.b = c.words(chunk_buffer_words(log_n, log_e, cols, mc));
+  l.bytes = c.at; return l;
 }
-constexpr size_t chunk_bytes(int log_n, int log_e, int wires, size_t cols, size_t mc) { return mul_sat(chunk_words(log_n, log_e, wires, cols, mc), sizeof(uint64_t)); }
+constexpr size_t chunk_bytes(int log_n, int log_e, int wires, size_t cols, size_t mc) { return chunk_layout(log_n, log_e, wires, cols, mc, mc).bytes; }
+constexpr size_t chunk_words(int log_n, int log_e, int wires, size_t cols, size_t mc) { return words_of(chunk_bytes(log_n, log_e, wires, cols, mc)); }
 // what a chunk holds at its peak: its own lease and the forward transform's on top (the larger of the two transforms)
 constexpr size_t chunk_budget_bytes(int log_n, int log_e, int wires, size_t cols, size_t mc) {
   return mul_sat(add_sat(chunk_words(log_n, log_e, wires, cols, mc),

@@ -307,8 +307,8 @@ static int32_t scalars_run(const In& a, size_t s0, size_t c, long long max_block
   return SYLOW_HIP_OK;
 }
 
-// The rows of all m proofs into c_xy, pi_xy [8][m] + flags, y [4][m], status [m], chunk by chunk through one lease laid out for mc proofs:
-// den | k | bases | pbases | psc | C | pi | the flags of bases, pbases, C and pi
+// The rows of all m proofs into c_xy, pi_xy [8][m] + flags, y [4][m], status [m], chunk by chunk through one lease laid out for mc proofs
+// (fold_layout)
 static int32_t fold_run(const In& a, const Points& p, u64* c_xy, uint8_t* c_inf, u64* pi_xy, uint8_t* pi_inf, u64* y, uint8_t* status, void* stream) {
   const hipStream_t st = (hipStream_t)stream;
   const size_t lim = host::scratch_limit(), mc = proofs_per_chunk(a.log_e, a.W, a.n_pub, a.m, lim ? lim : msmh::default_budget());
@@ -317,12 +317,13 @@ static int32_t fold_run(const In& a, const Points& p, u64* c_xy, uint8_t* c_inf,
     return SYLOW_HIP_E_HIP;
   }
   host::Lease ws;
-  int32_t rc = ws.acquire(fold_chunk_bytes(a.log_e, a.W, a.n_pub, mc), st);
+  const FoldLayout l = fold_layout(a.log_e, a.W, a.n_pub, mc);
+  int32_t rc = ws.acquire(l.bytes, st);
   if (rc != SYLOW_HIP_OK) return rc;
-  const size_t T = terms(a.log_e, a.W), tn = T * mc;
-  u64 *den = (u64*)ws.p, *k = den + den_words(a.n_pub, mc), *bases = k + FR_WORDS * tn, *pbases = bases + G1_WORDS * tn, *psc = pbases + G1_WORDS * PI_TERMS * mc,
-      *C = psc + FR_WORDS * PI_TERMS * mc, *PI = C + G1_WORDS * mc;
-  uint8_t *binf = (uint8_t*)(PI + G1_WORDS * mc), *pbinf = binf + tn, *cinf = pbinf + PI_TERMS * mc, *pinf = cinf + mc;
+  const size_t T = terms(a.log_e, a.W);
+  u64 *den = ws.at<u64>(l.den), *k = ws.at<u64>(l.k), *bases = ws.at<u64>(l.bases), *pbases = ws.at<u64>(l.pbases), *psc = ws.at<u64>(l.psc), *C = ws.at<u64>(l.C),
+      *PI = ws.at<u64>(l.PI);
+  uint8_t *binf = ws.at<uint8_t>(l.binf), *pbinf = ws.at<uint8_t>(l.pbinf), *cinf = ws.at<uint8_t>(l.cinf), *pinf = ws.at<uint8_t>(l.pinf);
   for (size_t s0 = 0; s0 < a.m && rc == SYLOW_HIP_OK; s0 += mc) {
     const size_t c = chunk_size(a.m, mc, s0);
     rc = scalars_run(a, s0, c, -1, den, k, y, status, stream);
@@ -354,8 +355,8 @@ int32_t sylow_pverify_scalars_batch_tuned(const uint64_t* evals, const uint64_t*
   const host::Range outs[3] = {{(uintptr_t)k_out, scalars_bytes(term_count(log_e, W, m))}, {(uintptr_t)y_out, scalars_bytes(m)}, {(uintptr_t)status, m}};
   ARGCHK(pv::apart(a, nullptr, outs));
   host::Lease ws;
-  if (scratch && (rc = ws.acquire(scratch * sizeof(u64), (hipStream_t)stream)) != SYLOW_HIP_OK) return rc;
-  rc = pv::scalars_run(a, 0, m, max_blocks, (u64*)ws.p, k_out, y_out, status, stream);
+  if (scratch && (rc = ws.acquire(scalars_scratch_bytes(n_pub, m), (hipStream_t)stream)) != SYLOW_HIP_OK) return rc;
+  rc = pv::scalars_run(a, 0, m, max_blocks, ws.at<u64>(0), k_out, y_out, status, stream);
   return host::finish(rc, ws);
 }
 int32_t sylow_pverify_scalars_batch(const uint64_t* evals, const uint64_t* pub, size_t n_pub, const uint64_t* shifts, const uint64_t* beta,
@@ -399,9 +400,10 @@ int32_t sylow_pverify_verify_batch(const uint64_t* tau_g2_xy, const uint64_t* vk
   ARGCHK(pv::apart(a, &p, outs));
   const hipStream_t st = (hipStream_t)stream;
   host::Lease ws;
-  if ((rc = ws.acquire(verify_words(m) * sizeof(u64), st)) != SYLOW_HIP_OK) return rc;
-  u64 *C = (u64*)ws.p, *PI = C + G1_WORDS * m, *y = PI + G1_WORDS * m, *z = y + FR_WORDS * m;
-  uint8_t *cinf = (uint8_t*)(z + FR_WORDS * m), *pinf = cinf + m;
+  const VerifyLayout l = verify_layout(m);
+  if ((rc = ws.acquire(l.bytes, st)) != SYLOW_HIP_OK) return rc;
+  u64 *C = ws.at<u64>(l.C), *PI = ws.at<u64>(l.PI), *y = ws.at<u64>(l.y), *z = ws.at<u64>(l.z);
+  uint8_t *cinf = ws.at<uint8_t>(l.cinf), *pinf = ws.at<uint8_t>(l.pinf);
   rc = pv::fold_run(a, p, C, cinf, PI, pinf, y, status, stream);
   if (rc == SYLOW_HIP_OK && hipMemsetAsync(z, 0, FR_WORDS * m * sizeof(u64), st) != hipSuccess) rc = host::fail(hipGetLastError(), "hipMemsetAsync");
   if (rc == SYLOW_HIP_OK) rc = sylow_hip_kzg_verify_batch(tau_g2_xy, C, cinf, z, y, PI, pinf, ok, m, stream);
@@ -429,14 +431,14 @@ int32_t sylow_pverify_batch_verify_weighted(const uint64_t* tau_g2_xy, const uin
   ARGCHK(pv::apart(a, &p, outs));
   const hipStream_t st = (hipStream_t)stream;
   host::Lease ws;
-  if ((rc = ws.acquire(scratch * sizeof(u64), st)) != SYLOW_HIP_OK) return rc;
-  const size_t K = key_points(W), P = proof_points(log_e, W), T = K + P, parts = weighted_parts(m), cols = weighted_columns(W);
-  u64 *den = (u64*)ws.p, *k = den + den_words(n_pub, m), *y = k + FR_WORDS * T * m, *sc_own = y + FR_WORDS * m, *sc_open = sc_own + FR_WORDS * P * m,
-      *obases = sc_open + FR_WORDS * PI_TERMS * m, *partial = obases + G1_WORDS * PI_TERMS * m, *ksum = partial + FR_WORDS * cols * parts, *s = ksum + FR_WORDS * K,
-      *bad = s + FR_WORDS, *m_own = bad + FR_WORDS, *m2 = m_own + G1_WORDS, *m_key = m2 + G1_WORDS, *m1 = m_key + G1_WORDS, *sg = m1 + G1_WORDS,
-      *pxy = sg + G1_WORDS, *qxy = pxy + 2 * G1_WORDS;
-  uint8_t *obinf = (uint8_t*)(qxy + 2 * G2_WORDS), *f_own = obinf + PI_TERMS * m, *f2 = f_own + 1, *f_key = f2 + 1, *f1 = f_key + 1, *fsg = f1 + 1, *pinf = fsg + 1,
-          *qinf = pinf + 2;
+  const WeightedLayout l = weighted_layout(log_e, W, n_pub, m);
+  if ((rc = ws.acquire(l.bytes, st)) != SYLOW_HIP_OK) return rc;
+  const size_t K = key_points(W), P = proof_points(log_e, W), parts = weighted_parts(m), cols = weighted_columns(W);
+  const auto U = [&](size_t off) { return ws.at<u64>(off); };
+  const auto B = [&](size_t off) { return ws.at<uint8_t>(off); };
+  u64 *den = U(l.den), *k = U(l.k), *y = U(l.y), *sc_own = U(l.sc_own), *sc_open = U(l.sc_open), *obases = U(l.obases), *partial = U(l.partial), *ksum = U(l.ksum),
+      *s = U(l.s), *bad = U(l.bad), *m_own = U(l.m_own), *m2 = U(l.m2), *m_key = U(l.m_key), *m1 = U(l.m1), *sg = U(l.sg), *pxy = U(l.pxy), *qxy = U(l.qxy);
+  uint8_t *obinf = B(l.obinf), *f_own = B(l.f_own), *f2 = B(l.f2), *f_key = B(l.f_key), *f1 = B(l.f1), *fsg = B(l.fsg), *pinf = B(l.pinf), *qinf = B(l.qinf);
   rc = pv::scalars_run(a, 0, m, -1, den, k, y, status, stream);
   if (rc == SYLOW_HIP_OK) {
     pv::k_pv_weighted_prep<<<dim3((unsigned)parts), dim3(BLOCK), 0, st>>>(k, y, status, weights, u, proof_xy, proof_inf, m, log_e, W, sc_own, sc_open, obases, obinf,

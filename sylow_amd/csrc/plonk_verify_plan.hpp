@@ -1,18 +1,20 @@
 // plonk_verify_plan.hpp -- the geometry of the batched PLONK verifier (plonk_verify.hip): the terms of a proof's linear combination C and
 // their order, the slots of the key and of a proof, the columns of the weighted form's reduction, the chunks of whole proofs under a scratch
-// limit and every byte count, plain C++ so that tests/cpp/plonk_verify_plan_test.cpp can compile it with g++ on a box without a GPU.  The
+// limit and every byte count and scratch offset, plain C++ so that tests/cpp/plonk_verify_plan_test.cpp can compile it with g++ on a box without a GPU.  The
 // launch code asks these functions and decides nothing itself.  The evaluation slots, the bounds on log_n, log_e and W and the status bit are
 // plonk_open_plan.hpp's: the verifier reads what the prover wrote.
 #pragma once
 #include "plonk_open_plan.hpp"
 
 namespace plonk_verify_plan {
+using plan_base::Carve;
 using plan_base::SAT;
 using plan_base::add_sat;
 using plan_base::disjoint;
 using plan_base::elems;
 using plan_base::max_blocks_ok;
 using plan_base::mul_sat;
+using plan_base::words_of;
 using plonk_open_plan::FR_WORDS;
 using plonk_open_plan::STATUS_ZETA_IN_DOMAIN;
 using plonk_open_plan::ceil_div;
@@ -71,19 +73,34 @@ constexpr size_t gt_bytes() { return 48 * sizeof(uint64_t); }
 // batch inversion reads the first and writes the second); then a lane per proof ----------------------------------------------------------------
 constexpr size_t den_words(size_t n_pub, size_t mc) { return mul_sat(mul_sat(2 * FR_WORDS, n_pub), mc); }
 constexpr size_t scalars_scratch_words(size_t n_pub, size_t mc) { return den_words(n_pub, mc); }
+constexpr size_t scalars_scratch_bytes(size_t n_pub, size_t mc) { return mul_sat(scalars_scratch_words(n_pub, mc), sizeof(uint64_t)); }
 constexpr bool scratch_ok(size_t words) { return plonk_open_plan::scratch_ok(words); }
-constexpr size_t flag_words(size_t flags) { return ceil_div(flags, sizeof(uint64_t)); }
+constexpr size_t flag_words(size_t flags) { Carve c; c.bytes(flags); c.round(); return words_of(c.at); }      // the u64 words `flags` trailing bytes end in, as every layout below ends
 
 // ---- the fold: a chunk of mc whole proofs leases the denominators, the scalars k [4][T mc], the gathered bases [8][T mc] and [8][2 mc], the
 // scalars (1, u) [4][2 mc], C and pi [8][mc] each, and the flags of all of them.  sylow_hip_g1_lincomb_batch leases nothing ------------------------
-constexpr size_t fold_flags(int log_e, int wires, size_t mc) { return add_sat(term_count(log_e, wires, mc), mul_sat(PI_TERMS + 2, mc)); }
-constexpr size_t fold_chunk_words(int log_e, int wires, size_t n_pub, size_t mc) {
+struct FoldLayout { size_t den, k, bases, pbases, psc, C, PI, binf, pbinf, cinf, pinf, bytes; };
+constexpr FoldLayout fold_layout(int log_e, int wires, size_t n_pub, size_t mc) {
   const size_t t = term_count(log_e, wires, mc);
-  return add_sat(add_sat(add_sat(scalars_scratch_words(n_pub, mc), mul_sat(FR_WORDS + G1_WORDS, t)),
-                         mul_sat((G1_WORDS + FR_WORDS) * PI_TERMS + 2 * G1_WORDS, mc)),
-                 flag_words(fold_flags(log_e, wires, mc)));
+  Carve c; FoldLayout l{};
+  l.den = c.words(den_words(n_pub, mc));
+  l.k = c.words(mul_sat(FR_WORDS, t));
+  l.bases = c.words(mul_sat(G1_WORDS, t));
+  l.pbases = c.words(mul_sat(G1_WORDS * PI_TERMS, mc));
+  l.psc = c.words(mul_sat(FR_WORDS * PI_TERMS, mc));
+  l.C = c.words(mul_sat(G1_WORDS, mc));
+  l.PI = c.words(mul_sat(G1_WORDS, mc));
+  l.binf = c.bytes(t);
+  l.pbinf = c.bytes(mul_sat(PI_TERMS, mc));
+  l.cinf = c.bytes(mc);
+  l.pinf = c.bytes(mc);
+  c.round();
+  l.bytes = c.at; return l;
 }
-constexpr size_t fold_chunk_bytes(int log_e, int wires, size_t n_pub, size_t mc) { return mul_sat(fold_chunk_words(log_e, wires, n_pub, mc), sizeof(uint64_t)); }
+constexpr size_t fold_chunk_bytes(int log_e, int wires, size_t n_pub, size_t mc) { return fold_layout(log_e, wires, n_pub, mc).bytes; }
+// its flag bytes, from the first flag to the end of the last array of them (pinf, mc bytes)
+constexpr size_t fold_flags(int log_e, int wires, size_t mc) { return add_sat(fold_layout(log_e, wires, 0, mc).pinf, mc) - fold_layout(log_e, wires, 0, mc).binf; }
+constexpr size_t fold_chunk_words(int log_e, int wires, size_t n_pub, size_t mc) { return words_of(fold_chunk_bytes(log_e, wires, n_pub, mc)); }
 // whole proofs per chunk under `budget` bytes: 0 when not even one fits (the rule of plonk_open_plan::instances_per_chunk)
 constexpr size_t proofs_per_chunk(int log_e, int wires, size_t n_pub, size_t m, size_t budget) {
   if (!m || fold_chunk_bytes(log_e, wires, n_pub, 1) > budget) return 0;
@@ -95,7 +112,19 @@ constexpr size_t proofs_per_chunk(int log_e, int wires, size_t n_pub, size_t m, 
 }
 
 // ---- the per-proof flags: the fold's row (C, pi [8][m] each, y and the zeros of z [4][m] each, the two flag arrays) on top of the fold's chunk --
-constexpr size_t verify_words(size_t m) { return add_sat(mul_sat(2 * G1_WORDS + 2 * FR_WORDS, m), flag_words(mul_sat(2, m))); }
+struct VerifyLayout { size_t C, PI, y, z, cinf, pinf, bytes; };
+constexpr VerifyLayout verify_layout(size_t m) {
+  Carve c; VerifyLayout l{};
+  l.C = c.words(mul_sat(G1_WORDS, m));
+  l.PI = c.words(mul_sat(G1_WORDS, m));
+  l.y = c.words(mul_sat(FR_WORDS, m));
+  l.z = c.words(mul_sat(FR_WORDS, m));
+  l.cinf = c.bytes(m);
+  l.pinf = c.bytes(m);
+  c.round();
+  l.bytes = c.at; return l;
+}
+constexpr size_t verify_words(size_t m) { return words_of(verify_layout(m).bytes); }
 
 // ---- the weighted form: the scalars of all m proofs, rho k of the own terms [4][(W + E + 3) m] (the layout of proof_xy: the multi-scalar
 // multiplication reads the proofs in place), rho and rho u [4][2 m] beside the gathered opening points [8][2 m], the columns of the two-level
@@ -105,11 +134,40 @@ constexpr size_t column_s(int wires) { return key_points(wires); }
 constexpr size_t column_bad(int wires) { return key_points(wires) + 1; }
 constexpr size_t weighted_parts(size_t m) { return lane_tiles(m); }
 constexpr size_t WEIGHTED_POINTS = 5;                    // the own terms' sum, the opening points' sum, the key terms' sum, M1, s G1gen
-constexpr size_t weighted_words(int log_e, int wires, size_t n_pub, size_t m) {
+struct WeightedLayout {
+  size_t den, k, y, sc_own, sc_open, obases, partial, ksum, s, bad, m_own, m2, m_key, m1, sg, pxy, qxy;      // u64 arrays
+  size_t obinf, f_own, f2, f_key, f1, fsg, pinf, qinf, bytes;                                                // flags, and the total
+};
+constexpr WeightedLayout weighted_layout(int log_e, int wires, size_t n_pub, size_t m) {
   const size_t cols = weighted_columns(wires);
-  return add_sat(add_sat(add_sat(scalars_scratch_words(n_pub, m), mul_sat(FR_WORDS, add_sat(term_count(log_e, wires, m), m))),
-                         add_sat(mul_sat(FR_WORDS, proof_count(log_e, wires, m)), mul_sat((FR_WORDS + G1_WORDS) * PI_TERMS, m))),
-                 add_sat(add_sat(mul_sat(mul_sat(FR_WORDS, cols), add_sat(weighted_parts(m), 1)), WEIGHTED_POINTS * G1_WORDS + 2 * (G1_WORDS + G2_WORDS)),
-                         flag_words(add_sat(mul_sat(PI_TERMS, m), WEIGHTED_POINTS + 4))));
+  Carve c; WeightedLayout l{};
+  l.den = c.words(den_words(n_pub, m));
+  l.k = c.words(mul_sat(FR_WORDS, term_count(log_e, wires, m)));
+  l.y = c.words(mul_sat(FR_WORDS, m));
+  l.sc_own = c.words(mul_sat(FR_WORDS, proof_count(log_e, wires, m)));
+  l.sc_open = c.words(mul_sat(FR_WORDS * PI_TERMS, m));
+  l.obases = c.words(mul_sat(G1_WORDS * PI_TERMS, m));
+  l.partial = c.words(mul_sat(mul_sat(FR_WORDS, cols), weighted_parts(m)));
+  l.ksum = c.words(FR_WORDS * key_points(wires));
+  l.s = c.words(FR_WORDS);
+  l.bad = c.words(FR_WORDS);
+  l.m_own = c.words(G1_WORDS);
+  l.m2 = c.words(G1_WORDS);
+  l.m_key = c.words(G1_WORDS);
+  l.m1 = c.words(G1_WORDS);
+  l.sg = c.words(G1_WORDS);
+  l.pxy = c.words(2 * G1_WORDS);
+  l.qxy = c.words(2 * G2_WORDS);
+  l.obinf = c.bytes(mul_sat(PI_TERMS, m));
+  l.f_own = c.bytes(1);
+  l.f2 = c.bytes(1);
+  l.f_key = c.bytes(1);
+  l.f1 = c.bytes(1);
+  l.fsg = c.bytes(1);
+  l.pinf = c.bytes(2);
+  l.qinf = c.bytes(2);
+  c.round();
+  l.bytes = c.at; return l;
 }
+constexpr size_t weighted_words(int log_e, int wires, size_t n_pub, size_t m) { return words_of(weighted_layout(log_e, wires, n_pub, m).bytes); }
 }  // namespace plonk_verify_plan

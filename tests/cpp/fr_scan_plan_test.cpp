@@ -13,6 +13,7 @@ using namespace fr_scan_plan;
 static int fails = 0;
 static size_t checked = 0;
 #define EXPECT(cond, ...) do { ++checked; if (!(cond)) { ++fails; printf("FAIL %s:%d %s  ", __FILE__, __LINE__, #cond); printf(__VA_ARGS__); printf("\n"); } } while (0)
+#include "layout_check.hpp"
 
 static void constants_and_pins() {
   EXPECT(SCAN_BLOCK == 256 && SCAN_LANE_ELEMS == 8 && SCAN_CHUNK == 2048 && SCAN_TOTALS_TILE_MAX == 256 && SCAN_TOTALS_TILE_DEFAULT == 256, "constants");
@@ -120,12 +121,46 @@ static void bytes_and_scratch() {
   EXPECT(permutation_scratch_bytes(28, (size_t)1 << 40) == SIZE_MAX && wires_bytes(28, 32, (size_t)1 << 40) == SIZE_MAX, "saturates");
 }
 
+// The layout of every scratch lease: the regions in order with their sizes in u64 words (flags in bytes), and offsets and totals as the chain
+// of pointers in the launch code gave them before the layouts, written out by hand
+
+static void layouts() {
+  {  // 4 chunks x 3 rows = 12 items: totals [4][12], then a flag byte per item
+    const ScanLayout l = scan_layout(6153, 3, true);
+    const Region r[] = {WORDS(l, totals, 48), BYTES(l, zflag, 12)};
+    EXPECT(layout_ok("ratio scan", r, l.bytes) && l.totals == 0 && l.zflag == 384 && l.bytes == 396, "ratio scan: %zu %zu", l.zflag, l.bytes);
+  }
+  {
+    const ScanLayout l = scan_layout(6153, 3, false);
+    const Region r[] = {WORDS(l, totals, 48), BYTES(l, zflag, 0)};
+    EXPECT(layout_ok("plain scan", r, l.bytes) && l.zflag == 384 && l.bytes == 384, "plain scan: %zu", l.bytes);
+  }
+  {  // one chunk: nothing
+    const ScanLayout l = scan_layout(2048, 100, true);
+    const Region r[] = {WORDS(l, totals, 0), BYTES(l, zflag, 0)};
+    EXPECT(layout_ok("one chunk", r, l.bytes) && l.bytes == 0, "one chunk: %zu", l.bytes);
+  }
+  EXPECT(scan_layout(SIZE_MAX, (size_t)1 << 20, true).bytes == SIZE_MAX, "saturates");
+  {  // n = 8, m = 2: the 4 roots, then num and den [2][4][8]
+    const PermutationLayout l = permutation_layout(3, 2);
+    const Region r[] = {WORDS(l, roots, 16), WORDS(l, num, 64), WORDS(l, den, 64)};
+    EXPECT(layout_ok("permutation", r, l.bytes) && l.num == 128 && l.den == 640 && l.bytes == 1152, "permutation: %zu %zu %zu", l.num, l.den, l.bytes);
+  }
+  {  // n = 1: no roots
+    const PermutationLayout l = permutation_layout(0, 1);
+    const Region r[] = {WORDS(l, roots, 0), WORDS(l, num, 4), WORDS(l, den, 4)};
+    EXPECT(layout_ok("permutation n = 1", r, l.bytes) && l.num == 0 && l.den == 32 && l.bytes == 64, "n = 1: %zu", l.bytes);
+  }
+  EXPECT(permutation_layout(28, (size_t)1 << 40).bytes == SIZE_MAX, "saturates");
+}
+
 int main() {
   constants_and_pins();
   items_and_live_lanes();
   tile_walk();
   routes_and_apply();
   bytes_and_scratch();
+  layouts();
   if (fails) {
     printf("%d of %zu checks failed\n", fails, checked);
     return 1;

@@ -14,6 +14,7 @@ using namespace g1_ntt_plan;
 static int fails = 0;
 static size_t checked = 0;
 #define EXPECT(cond, ...) do { ++checked; if (!(cond)) { ++fails; if (fails < 40) { printf("FAIL %s:%d %s  ", __FILE__, __LINE__, #cond); printf(__VA_ARGS__); printf("\n"); } } } while (0)
+#include "layout_check.hpp"
 
 static const long long PINS[] = {1, 2, -1};
 
@@ -132,10 +133,34 @@ static void grids_tables_and_scratch() {
   EXPECT(disjoint(1000, 1064, 64) && disjoint(1064, 1000, 64) && !disjoint(1000, 1063, 64) && !disjoint(1063, 1000, 64) && !disjoint(1000, 1000, 64), "ranges");
 }
 
+// The layout of every scratch lease: the regions in order with their sizes in u64 words (flags in bytes), and offsets and totals as the chain
+// of pointers in the launch code gave them before the layouts, written out by hand
+static void layouts() {
+  {  // n = 8: one block of lanes multiplies, 256 KB of tables FIRST; the twiddles land on the byte behind them
+    const ScratchLayout l = scratch_layout(3, 1, false, -1);
+    const Region r[] = {BYTES(l, tables, 262144), WORDS(l, twiddles, 16), WORDS(l, buf[0], 96), WORDS(l, buf[1], 96)};
+    EXPECT(layout_ok("n = 8", r, l.bytes) && l.tables == 0 && l.twiddles == 262144 && l.buf[0] == 262272 && l.buf[1] == 263040 && l.bytes == 263808, "n = 8: %zu", l.bytes);
+  }
+  {  // n = 2, inverse: the closing scale alone multiplies; one buffer
+    const ScratchLayout l = scratch_layout(1, 2, true, -1);
+    const Region r[] = {BYTES(l, tables, 262144), WORDS(l, twiddles, 4), WORDS(l, buf[0], 48), WORDS(l, buf[1], 0)};
+    EXPECT(layout_ok("n = 2 inverse", r, l.bytes) && l.twiddles == 262144 && l.buf[0] == 262176 && l.bytes == 262560, "n = 2 inverse: %zu", l.bytes);
+  }
+  {  // n = 2, forward: no tables
+    const ScratchLayout l = scratch_layout(1, 1, false, -1);
+    const Region r[] = {BYTES(l, tables, 0), WORDS(l, twiddles, 4), WORDS(l, buf[0], 24), WORDS(l, buf[1], 0)};
+    EXPECT(layout_ok("n = 2", r, l.bytes) && l.twiddles == 0 && l.buf[0] == 32 && l.bytes == 224, "n = 2: %zu", l.bytes);
+  }
+  EXPECT(scratch_layout(0, 3, false, -1).bytes == 0 && scratch_layout(28, (size_t)1 << 33, false, -1).bytes == SAT, "n = 1 leases nothing; saturates");
+  // the tables are whole KB for every grid a pin can ask for, so the words behind them are aligned
+  for (const long long pin : {-1ll, 1ll, 7ll, 4096ll, 1ll << 40}) EXPECT(table_bytes(20, 3, true, pin) % 1024 == 0, "pin %lld", pin);
+}
+
 int main() {
   stages_and_indices();
   closing_and_ping_pong();
   grids_tables_and_scratch();
+  layouts();
   if (fails) {
     printf("%d of %zu checks FAILED\n", fails, checked);
     return 1;

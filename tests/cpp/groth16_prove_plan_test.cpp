@@ -13,6 +13,7 @@ using namespace g16_plan;
 static int fails = 0;
 static size_t checked = 0;
 #define EXPECT(cond, ...) do { ++checked; if (!(cond)) { ++fails; printf("FAIL %s:%d %s  ", __FILE__, __LINE__, #cond); printf(__VA_ARGS__); printf("\n"); } } while (0)
+#include "layout_check.hpp"
 
 static void spmv_geometry() {
   EXPECT(G16_BLOCK == 256 && SPMV_FLUSH == 16 && SPMV_LANES_LOG_MAX == 6 && SPMV_LANE_ENTRIES == 8 && G16_COSET_SHIFT == 5, "constants");
@@ -90,11 +91,51 @@ static void limits_of_the_route_tests() {
   EXPECT(prove_budget_bytes(3, 65539, 2, 1) == 4199488 && prove_budget_bytes(3, 65539, 2, 2) == 8398776 && 32 * (65539 + 65536) == 4194400, "n_vars = 2^16 + 3");
 }
 
+// The layout of every scratch lease: the regions in order with their sizes in u64 words (flags in bytes), and offsets and totals as the chain
+// of pointers in the launch code gave them before the layouts, written out by hand
+static void layouts() {
+  {
+    const QuotLayout l = quot_layout(3, 2);
+    const Region r[] = {WORDS(l, g, 4), WORDS(l, x, 192), WORDS(l, y, 192)};
+    EXPECT(layout_ok("quotient", r, l.bytes) && l.x == 32 && l.y == 1568 && l.bytes == 3104, "quotient: %zu", l.bytes);
+  }
+  {
+    const QuotLayout l = quot_layout(0, 1);
+    const Region r[] = {WORDS(l, g, 4), WORDS(l, x, 12), WORDS(l, y, 12)};
+    EXPECT(layout_ok("quotient n = 1", r, l.bytes) && l.x == 32 && l.y == 128 && l.bytes == 224, "n = 1: %zu", l.bytes);
+  }
+  EXPECT(quot_layout(28, (size_t)1 << 40).bytes == SIZE_MAX, "saturates");
+  {  // n = 8, 7 variables, 2 inputs (4 private), ONE witness: 28 flag bytes, padded to 32
+    const ProveLayout l = prove_layout(3, 7, 2, 1);
+    const Region r[] = {WORDS(l, zc, 28), WORDS(l, zl, 16), WORDS(l, quot.g, 4), WORDS(l, quot.x, 96), WORDS(l, quot.y, 96), WORDS(l, hq, 28), WORDS(l, raw1, 32),
+                        WORDS(l, raw2, 16), WORDS(l, p, 136), WORDS(l, q, 96), WORDS(l, f, 12), BYTES(l, raw1_inf, 4), BYTES(l, raw2_inf, 1), BYTES(l, p_inf, 17),
+                        BYTES(l, q_inf, 6)};
+    EXPECT(layout_ok("prove", r, l.bytes) && l.zl == 224 && l.quot.g == 352 && l.quot.x == 384 && l.quot.y == 1152 && l.quot.bytes == 1920 && l.hq == 1920, "prove: %zu", l.hq);
+    EXPECT(l.raw1 == 2144 && l.p == 2528 && l.f == 4384 && l.raw1_inf == 4480 && l.raw2_inf == 4484 && l.p_inf == 4485 && l.q_inf == 4502 && l.bytes == 4512, "prove: %zu", l.bytes);
+  }
+  {  // two witnesses: every region twice as long but g
+    const ProveLayout l = prove_layout(3, 7, 2, 2);
+    const Region r[] = {WORDS(l, zc, 56), WORDS(l, zl, 32), WORDS(l, quot.g, 4), WORDS(l, quot.x, 192), WORDS(l, quot.y, 192), WORDS(l, hq, 56), WORDS(l, raw1, 64),
+                        WORDS(l, raw2, 32), WORDS(l, p, 272), WORDS(l, q, 192), WORDS(l, f, 24), BYTES(l, raw1_inf, 8), BYTES(l, raw2_inf, 2), BYTES(l, p_inf, 34),
+                        BYTES(l, q_inf, 12)};
+    EXPECT(layout_ok("prove 2", r, l.bytes) && l.quot.g == 704 && l.raw1_inf == 8928 && l.bytes == 8984, "two witnesses: %zu", l.bytes);
+  }
+  {  // n = 1, one variable, no input: no private part and no h
+    const ProveLayout l = prove_layout(0, 1, 0, 1);
+    const Region r[] = {WORDS(l, zc, 4), WORDS(l, zl, 0), WORDS(l, quot.g, 4), WORDS(l, quot.x, 12), WORDS(l, quot.y, 12), WORDS(l, hq, 0), WORDS(l, raw1, 32),
+                        WORDS(l, raw2, 16), WORDS(l, p, 136), WORDS(l, q, 96), WORDS(l, f, 12), BYTES(l, raw1_inf, 4), BYTES(l, raw2_inf, 1), BYTES(l, p_inf, 17),
+                        BYTES(l, q_inf, 6)};
+    EXPECT(layout_ok("prove n = 1", r, l.bytes) && l.zl == 32 && l.quot.g == 32 && l.hq == 256 && l.raw1 == 256 && l.raw1_inf == 2592 && l.bytes == 2624, "n = 1: %zu", l.bytes);
+  }
+  EXPECT(prove_layout(20, (size_t)1 << 20, 1, SIZE_MAX / 4).bytes == SIZE_MAX && spmv_scratch_bytes(1000, 3) == 96000 && spmv_scratch_bytes(SIZE_MAX / 4, 2) == SIZE_MAX, "saturate");
+}
+
 int main() {
   limits_of_the_route_tests();
   spmv_geometry();
   quotient_scratch();
   prove_chunks();
+  layouts();
   if (fails) { printf("%d of %zu checks failed\n", fails, checked); return 1; }
   printf("OK %zu checks\n", checked);
   return 0;

@@ -15,6 +15,7 @@ using namespace kzg_cells_plan;
 static int fails = 0;
 static size_t checked = 0;
 #define EXPECT(cond, ...) do { ++checked; if (!(cond)) { ++fails; printf("FAIL %s:%d %s  ", __FILE__, __LINE__, #cond); printf(__VA_ARGS__); printf("\n"); } } while (0)
+#include "layout_check.hpp"
 
 static const size_t TOP = SIZE_MAX;
 
@@ -181,12 +182,65 @@ static void scratch() {
   EXPECT(verify_scratch_bytes() == 8 * (16 + 16 + 32 + 1), "F, P, two pairs, one word of flags");
 }
 
+// The layout of every scratch lease: the regions in order with their sizes in u64 words (flags in bytes), and offsets and totals as the chain
+// of pointers in the launch code gave them before the layouts, written out by hand
+static void layouts() {
+  {  // by columns, every region there: 256 roots; 16384 entries; 192 keys; W in 8 slices; S, its transform, S in 4 slices
+    const FoldLayout l = fold_layout(ROUTE_COLUMNS, 7, 6, 8192, 64);
+    const Region r[] = {WORDS(l, roots, 256), WORDS(l, keys, 16384), WORDS(l, perm, 16384), WORDS(l, cnt, 192), WORDS(l, start, 193), WORDS(l, next, 192),
+                        WORDS(l, wpart, 2048), WORDS(l, body, 32768), WORDS(l, a, 32768), WORDS(l, spart, 131072)};
+    EXPECT(layout_ok("fold by columns", r, l.bytes) && l.keys == 2048 && l.perm == 133120 && l.cnt == 264192 && l.start == 265728 && l.next == 267272, "groups: %zu", l.next);
+    EXPECT(l.wpart == 268808 && l.body == 285192 && l.a == 547336 && l.spart == 809480 && l.bytes == 1858056, "by columns: %zu", l.bytes);
+  }
+  {  // by rows: the interpolants [16][4][64] are the body, and nothing is behind them
+    const FoldLayout l = fold_layout(ROUTE_ROWS, 7, 6, 16, 4);
+    const Region r[] = {WORDS(l, roots, 256), WORDS(l, keys, 16), WORDS(l, perm, 16), WORDS(l, cnt, 4), WORDS(l, start, 5), WORDS(l, next, 4), WORDS(l, wpart, 0),
+                        WORDS(l, body, 4096), WORDS(l, a, 0), WORDS(l, spart, 0)};
+    EXPECT(layout_ok("fold by rows", r, l.bytes) && l.keys == 2048 && l.cnt == 2304 && l.start == 2336 && l.next == 2376 && l.body == 2408 && l.bytes == 35176, "by rows: %zu", l.bytes);
+  }
+  {  // by columns, small: c = 4, l = 2, 3 rows, 2 commitments, no launch joins slices
+    const FoldLayout l = fold_layout(ROUTE_COLUMNS, 2, 1, 3, 2);
+    const Region r[] = {WORDS(l, roots, 8), WORDS(l, keys, 6), WORDS(l, perm, 6), WORDS(l, cnt, 6), WORDS(l, start, 7), WORDS(l, next, 6), WORDS(l, wpart, 0),
+                        WORDS(l, body, 32), WORDS(l, a, 32), WORDS(l, spart, 0)};
+    EXPECT(layout_ok("fold small", r, l.bytes) && l.keys == 64 && l.start == 208 && l.next == 264 && l.body == 312 && l.a == 568 && l.bytes == 824, "small: %zu", l.bytes);
+  }
+  {  // c = 1, l = 1, one row, no commitment: no roots and no keys
+    const FoldLayout l = fold_layout(ROUTE_ROWS, 0, 0, 1, 0);
+    const Region r[] = {WORDS(l, roots, 0), WORDS(l, keys, 1), WORDS(l, perm, 1), WORDS(l, cnt, 0), WORDS(l, start, 1), WORDS(l, next, 0), WORDS(l, wpart, 0),
+                        WORDS(l, body, 4), WORDS(l, a, 0), WORDS(l, spart, 0)};
+    EXPECT(layout_ok("fold of one", r, l.bytes) && l.perm == 8 && l.start == 16 && l.body == 24 && l.bytes == 56, "one row: %zu", l.bytes);
+  }
+  EXPECT(fold_layout(ROUTE_COLUMNS, 0, 0, TOP, 1).bytes == SAT && fold_layout(ROUTE_ROWS, 0, 0, 1, TOP).bytes == SAT, "saturate");
+  {  // l = 4, 3 rows, 2 commitments: 5 flags of the bases, one each of the two points, in 5 + 8 bytes
+    const ReduceLayout l = reduce_layout(2, 3, 2);
+    const Region r[] = {WORDS(l, w, 8), WORDS(l, a, 16), WORDS(l, r, 12), WORDS(l, rz, 12), WORDS(l, sc, 20), WORDS(l, bases, 40), WORDS(l, m1, 8), WORDS(l, at, 8),
+                        BYTES(l, binf, 5), BYTES(l, m1inf, 1), BYTES(l, atinf, 1)};
+    EXPECT(layout_ok("reduce", r, l.bytes) && l.a == 64 && l.r == 192 && l.sc == 384 && l.bases == 544 && l.m1 == 864 && l.binf == 992 && l.m1inf == 997 && l.atinf == 998 &&
+               l.bytes == 1005, "reduce: %zu", l.bytes);
+  }
+  {  // no row and no commitment
+    const ReduceLayout l = reduce_layout(2, 0, 0);
+    const Region r[] = {WORDS(l, w, 0), WORDS(l, a, 16), WORDS(l, r, 0), WORDS(l, rz, 0), WORDS(l, sc, 0), WORDS(l, bases, 0), WORDS(l, m1, 8), WORDS(l, at, 8),
+                        BYTES(l, binf, 0), BYTES(l, m1inf, 1), BYTES(l, atinf, 1)};
+    EXPECT(layout_ok("reduce of none", r, l.bytes) && l.a == 0 && l.m1 == 128 && l.binf == 256 && l.atinf == 257 && l.bytes == 264, "empty: %zu", l.bytes);
+  }
+  EXPECT(reduce_layout(2, TOP, 2).bytes == SAT && reduce_layout(2, 2, TOP).bytes == SAT, "saturate");
+  {
+    const VerifyLayout l = verify_layout();
+    const Region r[] = {WORDS(l, f, 8), WORDS(l, p, 8), WORDS(l, pxy, 16), WORDS(l, qxy, 32), BYTES(l, finf, 1), BYTES(l, pinf_one, 1), BYTES(l, pinf, 2),
+                        BYTES(l, qinf, 2), BYTES(l, flag, 1), BYTES(l, one, 1)};
+    EXPECT(layout_ok("verify", r, l.bytes) && l.p == 64 && l.pxy == 128 && l.qxy == 256 && l.finf == 512 && l.pinf == 514 && l.qinf == 516 && l.flag == 518 && l.one == 519 &&
+               l.bytes == 520, "verify: %zu", l.bytes);
+  }
+}
+
 int main() {
   limits();
   routes_and_keys();
   mac_kernel();
   horner();
   scratch();
+  layouts();
   if (fails) {
     printf("%d of %zu checks failed\n", fails, checked);
     return 1;

@@ -18,6 +18,7 @@ namespace g1 = g1_ntt_plan;
 static int fails = 0;
 static size_t checked = 0;
 #define EXPECT(cond, ...) do { ++checked; if (!(cond)) { ++fails; if (fails < 40) { printf("FAIL %s:%d %s  ", __FILE__, __LINE__, #cond); printf(__VA_ARGS__); printf("\n"); } } } while (0)
+#include "layout_check.hpp"
 
 static const long long PINS[] = {1, 3, -1};
 
@@ -239,6 +240,54 @@ static void rules_and_saturation() {
   EXPECT(fr_bytes(20, 7, (size_t)1 << 32) == SAT && table_xy_bytes(20, 7) == (size_t)1 << 34, "bytes");
 }
 
+// The layout of every scratch lease: the regions in order with their sizes in u64 words (flags in bytes), and offsets and totals as the chain
+// of pointers in the launch code gave them before the layouts, written out by hand
+static void layouts() {
+  {  // c = 4, l = 2: 2 arrays of 8 points, [2][8][8] words then 16 flags
+    const PrepareLayout l = prepare_layout(2, 1);
+    const Region r[] = {WORDS(l, xy, 128), BYTES(l, inf, 16)};
+    EXPECT(layout_ok("prepare", r, l.bytes) && l.inf == 1024 && l.bytes == 1040, "prepare: %zu", l.bytes);
+  }
+  {
+    const PrepareLayout l = prepare_layout(0, 0);
+    const Region r[] = {WORDS(l, xy, 16), BYTES(l, inf, 2)};
+    EXPECT(layout_ok("prepare of one", r, l.bytes) && l.inf == 128 && l.bytes == 130, "c = l = 1: %zu", l.bytes);
+  }
+  EXPECT(prepare_layout(60, 60).bytes == SAT, "saturates");
+  {  // c = 2, l = 2, one polynomial, two planes: one block of lanes, 256 KB of tables FIRST; the twiddles of 4 and of 2 points behind them
+    const ScratchLayout l = scratch_layout(1, 1, 1, 1, -1);
+    const Region r[] = {BYTES(l, tables, 262144), WORDS(l, tw_wide, 8), WORDS(l, tw, 4), WORDS(l, buf[0], 48), WORDS(l, buf[1], 48), WORDS(l, planes, 96),
+                        WORDS(l, padded, 32), WORDS(l, f, 32)};
+    EXPECT(layout_ok("open, two planes", r, l.bytes) && l.tw_wide == 262144 && l.tw == 262208 && l.buf[0] == 262240 && l.buf[1] == 262624 && l.planes == 263008 &&
+               l.padded == 263776 && l.f == 264032 && l.bytes == 264288, "two planes: %zu", l.bytes);
+  }
+  {  // one plane: the fused stage writes buffer 0 and there is no plane buffer
+    const ScratchLayout l = scratch_layout(1, 1, 1, 0, -1);
+    const Region r[] = {BYTES(l, tables, 262144), WORDS(l, tw_wide, 8), WORDS(l, tw, 4), WORDS(l, buf[0], 48), WORDS(l, buf[1], 48), WORDS(l, planes, 0),
+                        WORDS(l, padded, 32), WORDS(l, f, 32)};
+    EXPECT(layout_ok("open, one plane", r, l.bytes) && l.planes == 263008 && l.padded == 263008 && l.f == 263264 && l.bytes == 263520, "one plane: %zu", l.bytes);
+  }
+  EXPECT(scratch_layout(0, 3, 5, 0, -1).bytes == 0 && scratch_layout(0, 3, 5, 0, -1).f == 0, "c = 1 leases nothing");
+  for (const long long pin : {-1ll, 1ll, 7ll, 4096ll, 1ll << 40}) EXPECT(table_bytes(10, 3, 2, pin) % 1024 == 0, "the tables are whole KB: pin %lld", pin);
+  {
+    const ReduceLayout l = reduce_layout(1, 3);
+    const Region r[] = {WORDS(l, r, 24), WORDS(l, rc_xy, 24), BYTES(l, rc_inf, 3)};
+    EXPECT(layout_ok("reduce", r, l.bytes) && l.rc_xy == 192 && l.rc_inf == 384 && l.bytes == 387, "reduce: %zu", l.bytes);
+    const ReduceLayout one = reduce_layout(0, 1);
+    const Region q[] = {WORDS(one, r, 4), WORDS(one, rc_xy, 8), BYTES(one, rc_inf, 1)};
+    EXPECT(layout_ok("reduce of one", q, one.bytes) && one.rc_xy == 32 && one.rc_inf == 96 && one.bytes == 97 && reduce_layout(27, SIZE_MAX).bytes == SAT, "one row: %zu", one.bytes);
+  }
+  {
+    const VerifyLayout l = verify_layout(3);
+    const Region r[] = {WORDS(l, cred, 24), WORDS(l, z, 12), WORDS(l, y, 12), BYTES(l, cred_inf, 3), BYTES(l, in_rng, 3)};
+    EXPECT(layout_ok("verify", r, l.bytes) && l.z == 192 && l.y == 288 && l.cred_inf == 384 && l.in_rng == 387 && l.bytes == 390, "verify: %zu", l.bytes);
+    const VerifyLayout one = verify_layout(1);
+    const Region q[] = {WORDS(one, cred, 8), WORDS(one, z, 4), WORDS(one, y, 4), BYTES(one, cred_inf, 1), BYTES(one, in_rng, 1)};
+    EXPECT(layout_ok("verify of one", q, one.bytes) && one.z == 64 && one.y == 96 && one.cred_inf == 128 && one.bytes == 130 && verify_layout(SIZE_MAX).bytes == SAT, "one row: %zu",
+           one.bytes);
+  }
+}
+
 int main() {
   for (int log_c = 1; log_c <= 9; ++log_c)
     for (int log_l = 0; log_c + log_l <= 9; ++log_l)
@@ -249,6 +298,7 @@ int main() {
   table_of_x();
   twist_and_rows();
   rules_and_saturation();
+  layouts();
   if (fails) {
     printf("%d of %zu checks FAILED\n", fails, checked);
     return 1;

@@ -13,6 +13,7 @@ using namespace kzg_evals_plan;
 static int fails = 0;
 static size_t checked = 0;
 #define EXPECT(cond, ...) do { ++checked; if (!(cond)) { ++fails; printf("FAIL %s:%d %s  ", __FILE__, __LINE__, #cond); printf(__VA_ARGS__); printf("\n"); } } while (0)
+#include "layout_check.hpp"
 
 static void chunk_geometry() {
   EXPECT(EVALS_BLOCK == 256 && EVALS_LANE_ELEMS == 8 && EVALS_CHUNK == 2048 && EVALS_LOG_N_MAX == 28, "constants");
@@ -117,11 +118,33 @@ static void lone_inversion() {
   EXPECT(memcmp(o, zero, sizeof(o)) == 0, "inverse(0) ends with 0");
 }
 
+// The layout of every scratch lease: the regions in order with their sizes in u64 words (flags in bytes), and offsets and totals as the chain
+// of pointers in the launch code gave them before the layouts, written out by hand
+static void layouts() {
+  {  // n = 4096: two chunks a polynomial, 6 items; the 29 root slots first
+    const QuotientLayout l = quotient_layout(12, 3, false);
+    const Region r[] = {WORDS(l, roots, 116), WORDS(l, totals, 24), WORDS(l, hit, 3), WORDS(l, y, 12)};
+    EXPECT(layout_ok("quotient", r, l.bytes) && l.totals == 928 && l.hit == 1120 && l.y == 1144 && l.bytes == 1240, "quotient: %zu", l.bytes);
+  }
+  {  // the caller takes y: none in scratch
+    const QuotientLayout l = quotient_layout(12, 3, true);
+    const Region r[] = {WORDS(l, roots, 116), WORDS(l, totals, 24), WORDS(l, hit, 3), WORDS(l, y, 0)};
+    EXPECT(layout_ok("quotient, y out", r, l.bytes) && l.y == 1144 && l.bytes == 1144, "y out: %zu", l.bytes);
+  }
+  {
+    const QuotientLayout l = quotient_layout(0, 1, false);
+    const Region r[] = {WORDS(l, roots, 116), WORDS(l, totals, 4), WORDS(l, hit, 1), WORDS(l, y, 4)};
+    EXPECT(layout_ok("quotient of one", r, l.bytes) && l.totals == 928 && l.hit == 960 && l.y == 968 && l.bytes == 1000, "n = m = 1: %zu", l.bytes);
+  }
+  EXPECT(quotient_layout(0, SIZE_MAX, true).bytes == SAT && open_scratch_bytes(3, 2) == 512 && open_scratch_bytes(28, (size_t)1 << 40) == SAT, "saturate");
+}
+
 int main() {
   chunk_geometry();
   batch_inv_plan();
   quotient_plan();
   lone_inversion();
+  layouts();
   if (fails) { printf("%d of %zu checks failed\n", fails, checked); return 1; }
   printf("OK %zu checks\n", checked);
   return 0;

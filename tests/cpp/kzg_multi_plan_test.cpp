@@ -13,6 +13,7 @@ using namespace kzgm_plan;
 static int fails = 0;
 static size_t checked = 0;
 #define EXPECT(cond, ...) do { ++checked; if (!(cond)) { ++fails; printf("FAIL %s:%d %s  ", __FILE__, __LINE__, #cond); printf(__VA_ARGS__); printf("\n"); } } while (0)
+#include "layout_check.hpp"
 
 static void groups() {
   const uint64_t ok[] = {0, 0, 3, 3, 4, 9, 9}, dec[] = {0, 3, 2, 9}, late[] = {1, 3, 9}, shortfall[] = {0, 3, 8}, one[] = {0, 9}, none[] = {0, 0, 0};
@@ -111,11 +112,55 @@ static void combine_chunks() {
   EXPECT(b.route == Route::MSM && b.g_end == 1 && b.terms == ((size_t)1 << 33), "2^33");
 }
 
+// The layout of every scratch lease: the regions in order with their sizes in u64 words (flags in bytes), and offsets and totals as the chain
+// of pointers in the launch code gave them before the layouts, written out by hand
+static void layouts() {
+  {
+    const OpenLayout l = open_layout(2049, 14, 2);
+    const Region r[] = {WORDS(l, gs, 3), WORDS(l, pow, 56), WORDS(l, zs, 56), WORDS(l, f, 16392), WORDS(l, yf, 8)};
+    EXPECT(layout_ok("open", r, l.bytes) && l.pow == 24 && l.zs == 472 && l.f == 920 && l.yf == 132056 && l.bytes == 132120, "open: %zu", l.bytes);
+    const OpenLayout one = open_layout(1, 1, 1);
+    const Region q[] = {WORDS(one, gs, 2), WORDS(one, pow, 4), WORDS(one, zs, 4), WORDS(one, f, 4), WORDS(one, yf, 4)};
+    EXPECT(layout_ok("open of one", q, one.bytes) && one.pow == 16 && one.f == 80 && one.yf == 112 && one.bytes == 144, "one: %zu", one.bytes);
+    EXPECT(open_layout((size_t)1 << 40, 1, (size_t)1 << 40).bytes == SIZE_MAX, "saturates");
+  }
+  {
+    const CombineLayout l = combine_layout(14, 2);
+    const Region r[] = {WORDS(l, gs, 3), WORDS(l, pow, 56)};
+    EXPECT(layout_ok("combine", r, l.bytes) && l.pow == 24 && l.bytes == 472 && combine_layout(1, 1).pow == 16 && combine_layout(1, 1).bytes == 48, "combine: %zu", l.bytes);
+    EXPECT(combine_layout(SIZE_MAX / 2, 1).bytes == SIZE_MAX && offset_bytes(2) == 24 && offset_bytes(SIZE_MAX / 4) == SIZE_MAX, "saturates");
+  }
+  {  // a chunk of the combined commitments: (4 n + 8 n + 8 n + w_acc + 8 n_seg) words + 2 n + n_seg bytes.  3 groups of 2 terms, w_acc = 5
+    const ChunkLayout l = chunk_layout(6, 3, 5);
+    const Region r[] = {WORDS(l, sc, 24), WORDS(l, bases, 48), WORDS(l, prod, 48), WORDS(l, acc, 5), WORDS(l, part, 24), BYTES(l, flags, 6), BYTES(l, prod_inf, 6),
+                        BYTES(l, part_inf, 3)};
+    EXPECT(layout_ok("chunk", r, l.bytes) && l.bases == 192 && l.prod == 576 && l.acc == 960 && l.part == 1000 && l.flags == 1192 && l.prod_inf == 1198 && l.part_inf == 1204 &&
+               l.bytes == (24 + 48 + 48 + 5 + 24) * 8 + 12 + 3, "segments: %zu", l.bytes);
+  }
+  {  // one group of 5 terms through the multi-scalar multiplication: no words for a segmented sum
+    const ChunkLayout l = chunk_layout(5, 1, 0);
+    const Region r[] = {WORDS(l, sc, 20), WORDS(l, bases, 40), WORDS(l, prod, 40), WORDS(l, acc, 0), WORDS(l, part, 8), BYTES(l, flags, 5), BYTES(l, prod_inf, 5),
+                        BYTES(l, part_inf, 1)};
+    EXPECT(layout_ok("chunk msm", r, l.bytes) && l.acc == 800 && l.part == 800 && l.flags == 864 && l.prod_inf == 869 && l.part_inf == 874 && l.bytes == 108 * 8 + 10 + 1,
+           "msm: %zu", l.bytes);
+    EXPECT(chunk_layout(SIZE_MAX / 4, 1, 0).bytes == SIZE_MAX, "saturates");
+  }
+  {
+    const VerifyLayout l = verify_layout(9);
+    const Region r[] = {WORDS(l, cf, 72), WORDS(l, yf, 36), BYTES(l, cf_inf, 9)};
+    EXPECT(layout_ok("verify", r, l.bytes) && l.yf == 576 && l.cf_inf == 864 && l.bytes == 880, "verify: %zu", l.bytes);
+    const VerifyLayout one = verify_layout(1);
+    const Region q[] = {WORDS(one, cf, 8), WORDS(one, yf, 4), BYTES(one, cf_inf, 1)};
+    EXPECT(layout_ok("verify of one", q, one.bytes) && one.yf == 64 && one.cf_inf == 96 && one.bytes == 104 && verify_layout(SIZE_MAX / 8).bytes == SIZE_MAX, "one: %zu", one.bytes);
+  }
+}
+
 int main() {
   groups();
   lincomb_geometry();
   scratch();
   combine_chunks();
+  layouts();
   if (fails) { printf("%d of %zu checks failed\n", fails, checked); return 1; }
   printf("OK %zu checks\n", checked);
   return 0;

@@ -18,6 +18,7 @@ namespace g1 = g1_ntt_plan;
 static int fails = 0;
 static size_t checked = 0;
 #define EXPECT(cond, ...) do { ++checked; if (!(cond)) { ++fails; if (fails < 40) { printf("FAIL %s:%d %s  ", __FILE__, __LINE__, #cond); printf(__VA_ARGS__); printf("\n"); } } } while (0)
+#include "layout_check.hpp"
 
 static const long long PINS[] = {1, 3, -1};
 
@@ -181,12 +182,38 @@ static void sizes_tables_and_scratch() {
   EXPECT(disjoint(1000, 64, 1064, 8) && disjoint(1064, 8, 1000, 64) && !disjoint(1000, 64, 1063, 8) && !disjoint(1007, 8, 1000, 64) && !disjoint(1000, 64, 1000, 64), "ranges");
 }
 
+// The layout of every scratch lease: the regions in order with their sizes in u64 words (flags in bytes), and offsets and totals as the chain
+// of pointers in the launch code gave them before the layouts, written out by hand
+static void layouts() {
+  {
+    const PrepareLayout l = prepare_layout(2);
+    const Region r[] = {WORDS(l, xy, 64), BYTES(l, inf, 8)};
+    EXPECT(layout_ok("prepare", r, l.bytes) && l.inf == 512 && l.bytes == 520 && prepare_layout(0).inf == 128 && prepare_layout(0).bytes == 130 && prepare_layout(60).bytes == SAT,
+           "prepare: %zu", l.bytes);
+  }
+  {  // n = 4, 3 polynomials: one block of lanes, 256 KB of tables FIRST; the twiddles of 8 and of 4 points on the bytes behind them; P and F inside buffer 1
+    const ScratchLayout l = scratch_layout(2, 3, -1);
+    const Region r[] = {BYTES(l, tables, 262144), WORDS(l, tw_wide, 16), WORDS(l, tw, 8), WORDS(l, buf[0], 288), WORDS(l, buf[1], 288)};
+    EXPECT(layout_ok("open", r, l.bytes) && l.tw_wide == 262144 && l.tw == 262272 && l.buf[0] == 262336 && l.buf[1] == 264640 && l.bytes == 266944, "open: %zu", l.bytes);
+    EXPECT(l.padded == 264640 && l.f == 265408 && l.f + 96 * 8 <= l.bytes, "P and F: %zu %zu", l.padded, l.f);
+  }
+  {
+    const ScratchLayout l = scratch_layout(1, 1, -1);
+    const Region r[] = {BYTES(l, tables, 262144), WORDS(l, tw_wide, 8), WORDS(l, tw, 4), WORDS(l, buf[0], 48), WORDS(l, buf[1], 48)};
+    EXPECT(layout_ok("open n = 2", r, l.bytes) && l.tw == 262208 && l.buf[0] == 262240 && l.buf[1] == 262624 && l.bytes == 263008 && l.padded == 262624 && l.f == 262752,
+           "n = 2: %zu", l.bytes);
+  }
+  EXPECT(scratch_layout(0, 5, -1).bytes == 0 && scratch_layout(27, (size_t)1 << 40, -1).bytes == SAT, "n = 1 leases nothing; saturates");
+  for (const long long pin : {-1ll, 1ll, 7ll, 4096ll, 1ll << 40}) EXPECT(table_bytes(10, 3, pin) % 1024 == 0, "the tables are whole KB: pin %lld", pin);
+}
+
 int main() {
   for (int log_n = 1; log_n <= 10; ++log_n)
     for (const long long pin : PINS) whole_call(log_n, log_n <= 8 ? 3 : 1, pin);
   for (int log_n = 11; log_n <= OPEN_ALL_LOG_N_MAX; ++log_n) probes(log_n);
   table_of_x();
   sizes_tables_and_scratch();
+  layouts();
   if (fails) {
     printf("%d of %zu checks FAILED\n", fails, checked);
     return 1;

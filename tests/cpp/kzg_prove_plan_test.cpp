@@ -11,6 +11,7 @@ using namespace kzg_plan;
 static int fails = 0;
 static size_t checked = 0;
 #define EXPECT(cond, ...) do { ++checked; if (!(cond)) { ++fails; printf("FAIL %s:%d %s  ", __FILE__, __LINE__, #cond); printf(__VA_ARGS__); printf("\n"); } } while (0)
+#include "layout_check.hpp"
 
 static const char* name(Route r) { return r == Route::SHORT ? "SHORT" : r == Route::BUCKET ? "BUCKET" : "MSM_EACH"; }
 
@@ -69,9 +70,46 @@ static void commit_routes() {
   }
 }
 
+// The layout of every scratch lease: the regions in order with their sizes in u64 words (flags in bytes), and offsets and totals as the chain
+// of pointers in the launch code gave them before the layouts, written out by hand
+static void layouts() {
+  {
+    const QuotLayout l = quot_layout(2049, 5);
+    const Region r[] = {WORDS(l, totals, 40), WORDS(l, carries, 40)};
+    EXPECT(layout_ok("quotient", r, l.bytes) && l.carries == 320 && l.bytes == 640, "quotient: %zu", l.bytes);
+    EXPECT(quot_layout(2048, 5).bytes == 0 && quot_layout(2048, 5).carries == 0 && quot_layout(2049, SIZE_MAX / 2).bytes == SIZE_MAX, "one chunk leases nothing; saturates");
+    EXPECT(coeffs_bytes(3, 5) == 4 * 3 * 5 * 8 && coeffs_bytes(1, 1) == 32 && coeffs_bytes((size_t)1 << 59, 1) == SIZE_MAX, "4 len m words of quotients or coefficients");
+  }
+  {  // a multi-scalar multiplication per polynomial: (8 m + (canonical ? 0 : 4 len)) words + m bytes
+    const MsmEachLayout l = msm_each_layout(3, 5, false);
+    const Region r[] = {WORDS(l, pts, 40), WORDS(l, sc, 12), BYTES(l, inf, 5)};
+    EXPECT(layout_ok("msm each", r, l.bytes) && l.sc == 320 && l.inf == 416 && l.bytes == (8 * 5 + 4 * 3) * 8 + 5, "msm each: %zu", l.bytes);
+    const MsmEachLayout c = msm_each_layout(3, 5, true);
+    const Region q[] = {WORDS(c, pts, 40), WORDS(c, sc, 0), BYTES(c, inf, 5)};
+    EXPECT(layout_ok("msm each, canonical", q, c.bytes) && c.sc == 320 && c.inf == 320 && c.bytes == 8 * 5 * 8 + 5, "canonical: %zu", c.bytes);
+    EXPECT(msm_each_layout(3, 1, false).inf == 160 && msm_each_layout(3, 1, false).bytes == (8 + 12) * 8 + 1 && msm_each_layout(SIZE_MAX, 1, false).bytes == SIZE_MAX, "m = 1; saturates");
+  }
+  {  // the short route: (4 n + 8 n + 8 n + w_acc + (direct ? 0 : 8 per_chunk)) words + n + per_chunk bytes.  2 polynomials of 3 terms a chunk, w_acc = 7
+    const ShortLayout l = short_layout(3, 2, 7, false);
+    const Region r[] = {WORDS(l, sc, 24), WORDS(l, bases, 48), WORDS(l, prod, 48), WORDS(l, acc, 7), WORDS(l, part, 16), BYTES(l, prod_inf, 6), BYTES(l, part_inf, 2)};
+    EXPECT(layout_ok("short", r, l.bytes) && l.bases == 192 && l.prod == 576 && l.acc == 960 && l.part == 1016 && l.prod_inf == 1144 && l.part_inf == 1150 &&
+               l.bytes == (24 + 48 + 48 + 7 + 16) * 8 + 6 + 2, "short: %zu", l.bytes);
+  }
+  {  // one chunk: the segmented sum writes the caller's array, no sums in scratch
+    const ShortLayout l = short_layout(3, 2, 7, true);
+    const Region r[] = {WORDS(l, sc, 24), WORDS(l, bases, 48), WORDS(l, prod, 48), WORDS(l, acc, 7), WORDS(l, part, 0), BYTES(l, prod_inf, 6), BYTES(l, part_inf, 2)};
+    EXPECT(layout_ok("short, direct", r, l.bytes) && l.part == 1016 && l.prod_inf == 1016 && l.part_inf == 1022 && l.bytes == (24 + 48 + 48 + 7) * 8 + 6 + 2, "direct: %zu", l.bytes);
+    const ShortLayout d = short_layout(3, 5, 0, true);
+    const Region q[] = {WORDS(d, sc, 60), WORDS(d, bases, 120), WORDS(d, prod, 120), WORDS(d, acc, 0), WORDS(d, part, 0), BYTES(d, prod_inf, 15), BYTES(d, part_inf, 5)};
+    EXPECT(layout_ok("short, one stage", q, d.bytes) && d.acc == 2400 && d.prod_inf == 2400 && d.part_inf == 2415 && d.bytes == 300 * 8 + 15 + 5, "one stage: %zu", d.bytes);
+    EXPECT(short_layout(SIZE_MAX, 2, 0, false).bytes == SIZE_MAX, "saturates");
+  }
+}
+
 int main() {
   quotient_geometry();
   commit_routes();
+  layouts();
   if (fails) { printf("%d of %zu checks failed\n", fails, checked); return 1; }
   printf("OK %zu checks\n", checked);
   return 0;

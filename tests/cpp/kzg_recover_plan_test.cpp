@@ -14,6 +14,7 @@ using namespace kzg_recover_plan;
 static int fails = 0;
 static size_t checked = 0;
 #define EXPECT(cond, ...) do { ++checked; if (!(cond)) { ++fails; printf("FAIL %s:%d %s  ", __FILE__, __LINE__, #cond); printf(__VA_ARGS__); printf("\n"); } } while (0)
+#include "layout_check.hpp"
 
 static const size_t TOP = SIZE_MAX, M20 = (size_t)1 << 20;
 
@@ -169,6 +170,28 @@ static void scratch() {
   EXPECT(transforms(false) == 3 && transforms(true) == 4, "the floor of a call");
 }
 
+// The layout of every scratch lease: the regions in order with their sizes in u64 words (flags in bytes), and offsets and totals as the chain
+// of pointers in the launch code gave them before the layouts, written out by hand
+static void layouts() {
+  {  // a layout of the cells alone: log_c <= 12, so nothing here can saturate
+    const VanishLayout l = vanish_layout(3);
+    const Region r[] = {WORDS(l, consts, 8), WORDS(l, roots, 16)};
+    EXPECT(layout_ok("vanish", r, l.bytes) && l.roots == 64 && l.bytes == 192 && vanish_layout(0).roots == 64 && vanish_layout(0).bytes == 64, "vanish: %zu", l.bytes);
+  }
+  {  // c = 8, l = 4, 3 rows: the u32 flags of 3 rows in 2 words
+    const RecoverLayout l = recover_layout(3, 2, 3);
+    const Region r[] = {WORDS(l, v.consts, 8), WORDS(l, v.roots, 16), WORDS(l, zd, 96), WORDS(l, zc, 96), WORDS(l, zci, 96), WORDS(l, flags, 2), WORDS(l, buf, 384)};
+    EXPECT(layout_ok("recover", r, l.bytes) && l.v.roots == 64 && l.zd == 192 && l.zc == 960 && l.zci == 1728 && l.flags == 2496 && l.buf == 2512 && l.bytes == 5584,
+           "recover: %zu", l.bytes);
+  }
+  {  // c = 1, l = 2, one row: no roots
+    const RecoverLayout l = recover_layout(0, 1, 1);
+    const Region r[] = {WORDS(l, v.consts, 8), WORDS(l, v.roots, 0), WORDS(l, zd, 4), WORDS(l, zc, 4), WORDS(l, zci, 4), WORDS(l, flags, 1), WORDS(l, buf, 8)};
+    EXPECT(layout_ok("recover of one", r, l.bytes) && l.zd == 64 && l.zc == 96 && l.zci == 128 && l.flags == 160 && l.buf == 168 && l.bytes == 232, "one row: %zu", l.bytes);
+    EXPECT(recover_layout(3, 2, SIZE_MAX / 2).bytes == SAT, "saturates");
+  }
+}
+
 int main() {
   limits();
   callers_arrays();
@@ -178,6 +201,7 @@ int main() {
   element_kernels();
   status_kernel();
   scratch();
+  layouts();
   if (fails) {
     printf("%d of %zu checks failed\n", fails, checked);
     return 1;

@@ -11,6 +11,7 @@ using namespace ntt_plan;
 static int fails = 0;
 static size_t checked = 0;
 #define EXPECT(cond, ...) do { ++checked; if (!(cond)) { ++fails; printf("FAIL %s:%d %s  ", __FILE__, __LINE__, #cond); printf(__VA_ARGS__); printf("\n"); } } while (0)
+#include "layout_check.hpp"
 
 static void passes_and_stages() {
   EXPECT(NTT_LOG_N_MAX == 28 && NTT_BLOCK == 256 && NTT_TILE_LOG == 10 && NTT_STAGES_MAX == 10 && NTT_STAGES_DEFAULT == 5 && NTT_CONST_WORDS == 4, "constants");
@@ -106,11 +107,33 @@ static void n_inverses() {
   }
 }
 
+// The layout of every scratch lease: the regions in order with their sizes in u64 words (flags in bytes), and offsets and totals as the chain
+// of pointers in the launch code gave them before the layouts, written out by hand
+static void layouts() {
+  {
+    const ScratchLayout l = scratch_layout(3, 2, 2);
+    const Region r[] = {WORDS(l, consts, 4), WORDS(l, table, 16), WORDS(l, buf, 64)};
+    EXPECT(layout_ok("two steps", r, l.bytes) && l.table == 32 && l.buf == 160 && l.bytes == 672, "two steps: %zu", l.bytes);
+  }
+  {  // one step writes out: no buffer
+    const ScratchLayout l = scratch_layout(3, 2, 1);
+    const Region r[] = {WORDS(l, consts, 4), WORDS(l, table, 16), WORDS(l, buf, 0)};
+    EXPECT(layout_ok("one step", r, l.bytes) && l.buf == 160 && l.bytes == 160, "one step: %zu", l.bytes);
+  }
+  {  // n = 1: no table
+    const ScratchLayout l = scratch_layout(0, 1, 1);
+    const Region r[] = {WORDS(l, consts, 4), WORDS(l, table, 0), WORDS(l, buf, 0)};
+    EXPECT(layout_ok("n = 1", r, l.bytes) && l.table == 32 && l.bytes == 32, "n = 1: %zu", l.bytes);
+  }
+  EXPECT(scratch_layout(28, SIZE_MAX / 4, 2).bytes == SIZE_MAX, "saturates");
+}
+
 int main() {
   passes_and_stages();
   tiles_and_grids();
   table_and_scratch();
   n_inverses();
+  layouts();
   if (fails) {
     printf("%d of %zu checks FAILED\n", fails, checked);
     return 1;

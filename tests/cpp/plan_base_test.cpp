@@ -1,5 +1,5 @@
 // CPU-only check of what every plan header counts with (sylow_amd/csrc/plan_base.hpp): the saturating product and sum at the sentinel, on
-// both sides of SAT / b and with a zero operand, the elements of a domain, the rule for a pinned grid, the two range tests where they agree
+// both sides of SAT / b and with a zero operand, the carver of a scratch lease (empty, aligned, misaligned, saturated), the elements of a domain, the rule for a pinned grid, the two range tests where they agree
 // (touching, overlapping) and where they must not (an empty range inside a non-empty one), and the aliasing table of an entry point on two
 // inputs and three outputs.  Expected values are written out by hand.  Built with -fsanitize=address,undefined by tests/test_plan_base.py:
 // host code only.
@@ -29,6 +29,36 @@ static void saturating() {
   EXPECT(add_sat(SAT - 2, 1) == SAT - 1 && add_sat(1, SAT - 2) == SAT - 1 && add_sat(SAT - 1, 1) == SAT && add_sat(SAT - 1, 2) == SAT && add_sat(2, SAT - 1) == SAT,
          "the last sum that fits, the sum that is the sentinel, the first that wraps");
   EXPECT(add_sat(0, 0) == 0 && add_sat(0, 7) == 7 && add_sat(7, 0) == 7 && add_sat(1, 2) == 3, "a zero operand");
+}
+
+// the carver of a scratch lease: offsets in bytes, a word region only on a multiple of 8, SAT for good once it is reached
+static void carving() {
+  Carve none;
+  EXPECT(none.at == 0, "an empty lease");
+  Carve c;
+  EXPECT(c.words(3) == 0 && c.at == 24 && c.words(0) == 24 && c.at == 24 && c.bytes(5) == 24 && c.at == 29 && c.bytes(0) == 29 && c.at == 29, "words, bytes and empty regions: %zu", c.at);
+  c.round();
+  EXPECT(c.at == 32, "rounded up to a word: %zu", c.at);
+  c.round();
+  EXPECT(c.at == 32 && c.words(1) == 32 && c.at == 40, "rounding an aligned offset moves nothing, and words may follow: %zu", c.at);
+  Carve odd;
+  odd.bytes(3);
+  EXPECT(odd.words(1) == SAT && odd.at == SAT, "words behind bytes that were not rounded: the whole lease is refused");
+  Carve big;
+  EXPECT(big.words(SAT) == 0 && big.at == SAT && big.bytes(1) == SAT && big.at == SAT && big.words(1) == SAT && big.at == SAT && big.bytes(0) == SAT && big.at == SAT, "SAT stays");
+  big.round();
+  EXPECT(big.at == SAT, "through a rounding too");
+  Carve edge;
+  EXPECT(edge.words(SAT / 8) == 0 && edge.at == SAT - 7, "the last word region that fits: %zx", edge.at);
+  edge.round();
+  EXPECT(edge.at == SAT - 7 && edge.bytes(7) == SAT - 7 && edge.at == SAT, "SAT - 7 is aligned; 7 bytes more reach the sentinel");
+  Carve top;
+  top.bytes(SAT - 3);
+  top.round();
+  EXPECT(top.at == SAT, "a rounding that would wrap saturates");
+  Carve sum;
+  sum.bytes(SAT - 8);
+  EXPECT(sum.bytes(9) == SAT - 8 && sum.at == SAT && words_of(SAT) == SAT && words_of(24) == 3 && words_of(0) == 0 && words_of(SAT - 7) == SAT / 8, "a sum that would wrap; words_of");
 }
 
 static void domains_and_pins() {
@@ -96,6 +126,7 @@ static void tables() {
 
 int main() {
   saturating();
+  carving();
   domains_and_pins();
   ranges();
   tables();

@@ -14,6 +14,7 @@ using namespace plonk_open_plan;
 static int fails = 0;
 static size_t checked = 0;
 #define EXPECT(cond, ...) do { ++checked; if (!(cond)) { ++fails; printf("FAIL %s:%d %s  ", __FILE__, __LINE__, #cond); printf(__VA_ARGS__); printf("\n"); } } while (0)
+#include "layout_check.hpp"
 
 static void constants_and_pins() {
   EXPECT(PO_BLOCK == 256 && PO_FLUSH == 16 && PO_WEIGHT_ROUND == 16 && PO_WIRES_MIN == 2 && PO_WIRES_MAX == 32 && PO_LOG_MAX == 28 && PO_EVAL_CHUNK == 2048, "constants");
@@ -186,6 +187,42 @@ static void limits_of_the_route_tests() {
   EXPECT(chunk_size(5, 2, 4) == 1 && point_words(2) == 16 && point_words(1) == 8, "the last chunk of a_two");
 }
 
+// The layout of every scratch lease: the regions in order with their sizes in u64 words (flags in bytes), and offsets and totals as the chain
+// of pointers in the launch code gave them before the layouts, written out by hand
+static void layouts() {
+  {  // n = 4, W = 3: 7 slots of one chunk each, 2 instances
+    const EvaluateLayout l = evaluate_layout(2, 3, 5, 6, 2);
+    const Region r[] = {WORDS(l, pts, 16), WORDS(l, partials, 56)};
+    EXPECT(layout_ok("evaluate", r, l.bytes) && l.partials == 128 && l.bytes == 576, "evaluate: %zu", l.bytes);
+    EXPECT(evaluate_layout(2, 2, 1, 1, 1).partials == 64 && evaluate_layout(2, 2, 1, 1, 1).bytes == 224 && evaluate_layout(2, 3, 5, 6, SIZE_MAX / 8).bytes == SIZE_MAX,
+           "one instance; saturates");
+  }
+  {  // E = 2: 16 weight slots; the caller takes only F, so r (6 coefficients) lies behind the partials
+    const LineariseLayout l = linearise_layout(2, 1, 3, 6, 8, 2, true);
+    const Region r[] = {WORDS(l, pts, 16), WORDS(l, weights, 128), WORDS(l, rz, 8), WORDS(l, partials, 8), WORDS(l, r_buf, 48)};
+    EXPECT(layout_ok("linearise, own r", r, l.bytes) && l.weights == 128 && l.rz == 1152 && l.partials == 1216 && l.r_buf == 1280 && l.bytes == 1664, "own r: %zu", l.bytes);
+    const LineariseLayout o = linearise_layout(2, 1, 3, 6, 8, 2, false);
+    const Region q[] = {WORDS(o, pts, 16), WORDS(o, weights, 128), WORDS(o, rz, 8), WORDS(o, partials, 8), WORDS(o, r_buf, 0)};
+    EXPECT(layout_ok("linearise", q, o.bytes) && o.partials == 1216 && o.r_buf == 1280 && o.bytes == 1280 && linearise_layout(2, 1, 3, 6, 8, SIZE_MAX / 8, true).bytes == SIZE_MAX,
+           "r to the caller: %zu", o.bytes);
+  }
+  {  // the full route, 3 instances a chunk, an SRS of 8 points: 6 flag bytes, padded to 8
+    const OpenLayout l = open_layout(2, 1, 3, 5, 6, 8, 3);
+    const Region r[] = {WORDS(l, ev.pts, 24), WORDS(l, ev.partials, 84), WORDS(l, weights, 192), WORDS(l, F, 96), WORDS(l, Z, 96), WORDS(l, yf, 12), WORDS(l, yz, 12),
+                        WORDS(l, p1, 24), WORDS(l, p2, 24), BYTES(l, f1, 3), BYTES(l, f2, 3)};
+    EXPECT(layout_ok("open", r, l.bytes) && l.ev.partials == 192 && l.ev.bytes == 864 && l.weights == 864 && l.F == 2400 && l.Z == 3168 && l.yf == 3936 && l.yz == 4032, "open: %zu", l.yz);
+    EXPECT(l.p1 == 4128 && l.p2 == 4320 && l.f1 == 4512 && l.f2 == 4515 && l.bytes == 4520, "open: %zu", l.bytes);
+  }
+  {
+    const OpenLayout l = open_layout(2, 1, 3, 5, 6, 8, 1);
+    const Region r[] = {WORDS(l, ev.pts, 8), WORDS(l, ev.partials, 28), WORDS(l, weights, 64), WORDS(l, F, 32), WORDS(l, Z, 32), WORDS(l, yf, 4), WORDS(l, yz, 4),
+                        WORDS(l, p1, 8), WORDS(l, p2, 8), BYTES(l, f1, 1), BYTES(l, f2, 1)};
+    EXPECT(layout_ok("open of one", r, l.bytes) && l.weights == 288 && l.F == 800 && l.Z == 1056 && l.yf == 1312 && l.p1 == 1376 && l.f1 == 1504 && l.f2 == 1505 && l.bytes == 1512,
+           "one instance: %zu", l.bytes);
+    EXPECT(open_layout(2, 1, 3, 5, 6, 8, SIZE_MAX / 8).bytes == SIZE_MAX, "saturates");
+  }
+}
+
 int main() {
   limits_of_the_route_tests();
   constants_and_pins();
@@ -193,6 +230,7 @@ int main() {
   eval_items_and_chunk_edges();
   fold_tiles_and_lengths();
   chunks_and_scratch();
+  layouts();
   if (fails) {
     printf("%d of %zu checks failed\n", fails, checked);
     return 1;

@@ -13,6 +13,7 @@ using namespace plonk_quotient_plan;
 static int fails = 0;
 static size_t checked = 0;
 #define EXPECT(cond, ...) do { ++checked; if (!(cond)) { ++fails; printf("FAIL %s:%d %s  ", __FILE__, __LINE__, #cond); printf(__VA_ARGS__); printf("\n"); } } while (0)
+#include "layout_check.hpp"
 
 static void constants_and_pins() {
   EXPECT(PQ_BLOCK == 256 && PQ_FLUSH == 16 && PQ_COSET_SHIFT == 5 && PQ_WIRES_MIN == 2 && PQ_WIRES_MAX == 32 && PQ_LOG_MAX == 28 && STATUS_NOT_DIVISIBLE == 1, "constants");
@@ -159,6 +160,37 @@ static void limits_of_the_route_tests() {
          "two and not three");
 }
 
+// The layout of every scratch lease: the regions in order with their sizes in u64 words (flags in bytes), and offsets and totals as the chain
+// of pointers in the launch code gave them before the layouts, written out by hand
+static void layouts() {
+  {  // n = 4, E = 2, W = 2: 7 rows.  A layout of the circuit alone: log_n + log_e <= 28, so nothing here can saturate
+    const PrepareLayout l = prepare_layout(2, 1, 2);
+    const Region r[] = {WORDS(l, g, 4), WORDS(l, roots, 16), WORDS(l, coeff, 112), WORDS(l, l1, 16), WORDS(l, padded, 224)};
+    EXPECT(layout_ok("prepare", r, l.bytes) && l.roots == 32 && l.coeff == 160 && l.l1 == 1056 && l.padded == 1184 && l.bytes == 2976, "prepare: %zu", l.bytes);
+    const PrepareLayout o = prepare_layout(0, 0, 2);
+    const Region q[] = {WORDS(o, g, 4), WORDS(o, roots, 0), WORDS(o, coeff, 28), WORDS(o, l1, 4), WORDS(o, padded, 28)};
+    EXPECT(layout_ok("prepare N = 1", q, o.bytes) && o.coeff == 32 && o.l1 == 256 && o.padded == 288 && o.bytes == 512, "N = 1: %zu", o.bytes);
+  }
+  {
+    const EvalsLayout l = evals_layout(2, 1, 2, 3);
+    const Region r[] = {WORDS(l, roots, 16), WORDS(l, consts, 72)};
+    EXPECT(layout_ok("evals", r, l.bytes) && l.consts == 128 && l.bytes == 704 && evals_layout(0, 0, 2, 1).consts == 0 && evals_layout(0, 0, 2, 1).bytes == 192 &&
+               evals_layout(2, 1, 2, SIZE_MAX / 8).bytes == SIZE_MAX, "evals: %zu", l.bytes);
+  }
+  {  // the full route, 3 columns, chunks of 2 instances; a short last chunk keeps the constants of 2 and packs its buffers behind them
+    const ChunkLayout l = chunk_layout(2, 1, 2, 3, 2, 2);
+    const Region r[] = {WORDS(l, g, 4), WORDS(l, roots, 16), WORDS(l, consts, 48), WORDS(l, a, 192), WORDS(l, b, 192)};
+    EXPECT(layout_ok("chunk", r, l.bytes) && l.roots == 32 && l.consts == 160 && l.a == 544 && l.b == 2080 && l.bytes == 3616 && l.bytes == chunk_bytes(2, 1, 2, 3, 2), "chunk: %zu", l.bytes);
+    const ChunkLayout s = chunk_layout(2, 1, 2, 3, 2, 1);
+    const Region q[] = {WORDS(s, g, 4), WORDS(s, roots, 16), WORDS(s, consts, 48), WORDS(s, a, 96), WORDS(s, b, 96)};
+    EXPECT(layout_ok("short chunk", q, s.bytes) && s.a == 544 && s.b == 1312 && s.bytes == 2080 && s.bytes <= l.bytes, "the last chunk: %zu", s.bytes);
+    const ChunkLayout p = chunk_layout(2, 1, 2, 4, 1, 1);
+    const Region t[] = {WORDS(p, g, 4), WORDS(p, roots, 16), WORDS(p, consts, 24), WORDS(p, a, 128), WORDS(p, b, 128)};
+    EXPECT(layout_ok("chunk of one with public inputs", t, p.bytes) && p.a == 352 && p.b == 1376 && p.bytes == 2400, "one instance: %zu", p.bytes);
+    EXPECT(chunk_layout(2, 1, 2, 3, SIZE_MAX / 8, SIZE_MAX / 8).bytes == SIZE_MAX, "saturates");
+  }
+}
+
 int main() {
   limits_of_the_route_tests();
   constants_and_pins();
@@ -166,6 +198,7 @@ int main() {
   items_and_tail_tiles();
   degree_bound_and_tail();
   chunks_and_scratch();
+  layouts();
   if (fails) {
     printf("%d of %zu checks failed\n", fails, checked);
     return 1;

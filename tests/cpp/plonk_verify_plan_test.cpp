@@ -13,6 +13,7 @@ using namespace plonk_verify_plan;
 static int fails = 0;
 static size_t checked = 0;
 #define EXPECT(cond, ...) do { ++checked; if (!(cond)) { ++fails; printf("FAIL %s:%d %s  ", __FILE__, __LINE__, #cond); printf(__VA_ARGS__); printf("\n"); } } while (0)
+#include "layout_check.hpp"
 
 static void constants_and_pins() {
   EXPECT(PV_BLOCK == 256 && FR_WORDS == 4 && G1_WORDS == 8 && G2_WORDS == 16 && PI_TERMS == 2 && STATUS_ZETA_IN_DOMAIN == 2 && WEIGHTED_POINTS == 5, "constants");
@@ -77,11 +78,68 @@ static void chunks() {
   EXPECT(proofs_per_chunk(2, 3, SIZE_MAX / 2, 4, (size_t)1 << 30) == 0, "a size that saturates is refused");
 }
 
+// The layout of every scratch lease: the regions in order with their sizes in u64 words (flags in bytes), and offsets and totals as the chain
+// of pointers in the launch code gave them before the layouts, written out by hand
+static void layouts() {
+  {  // W = 3, E = 4: 18 terms; 3 public inputs; ONE proof: 22 flag bytes, padded to 24
+    const FoldLayout l = fold_layout(2, 3, 3, 1);
+    const Region r[] = {WORDS(l, den, 24), WORDS(l, k, 72), WORDS(l, bases, 144), WORDS(l, pbases, 16), WORDS(l, psc, 8), WORDS(l, C, 8), WORDS(l, PI, 8), BYTES(l, binf, 18),
+                        BYTES(l, pbinf, 2), BYTES(l, cinf, 1), BYTES(l, pinf, 1)};
+    EXPECT(layout_ok("fold", r, l.bytes) && l.k == 192 && l.bases == 768 && l.pbases == 1920 && l.psc == 2048 && l.C == 2112 && l.PI == 2176 && l.binf == 2240 && l.pbinf == 2258 &&
+               l.cinf == 2260 && l.pinf == 2261 && l.bytes == 2264, "one proof: %zu", l.bytes);
+  }
+  {
+    const FoldLayout l = fold_layout(2, 3, 3, 2);
+    const Region r[] = {WORDS(l, den, 48), WORDS(l, k, 144), WORDS(l, bases, 288), WORDS(l, pbases, 32), WORDS(l, psc, 16), WORDS(l, C, 16), WORDS(l, PI, 16), BYTES(l, binf, 36),
+                        BYTES(l, pbinf, 4), BYTES(l, cinf, 2), BYTES(l, pinf, 2)};
+    EXPECT(layout_ok("fold 2", r, l.bytes) && l.k == 384 && l.bases == 1536 && l.pbases == 3840 && l.C == 4224 && l.binf == 4480 && l.cinf == 4520 && l.pinf == 4522 && l.bytes == 4528,
+           "two proofs: %zu", l.bytes);
+  }
+  {  // no public inputs: no denominators
+    const FoldLayout l = fold_layout(2, 3, 0, 1);
+    const Region r[] = {WORDS(l, den, 0), WORDS(l, k, 72), WORDS(l, bases, 144), WORDS(l, pbases, 16), WORDS(l, psc, 8), WORDS(l, C, 8), WORDS(l, PI, 8), BYTES(l, binf, 18),
+                        BYTES(l, pbinf, 2), BYTES(l, cinf, 1), BYTES(l, pinf, 1)};
+    EXPECT(layout_ok("fold, n_pub = 0", r, l.bytes) && l.k == 0 && l.bases == 576 && l.binf == 2048 && l.pinf == 2069 && l.bytes == 2072, "no public inputs: %zu", l.bytes);
+    EXPECT(fold_layout(2, 3, 3, SIZE_MAX / 8).bytes == SIZE_MAX && scalars_scratch_bytes(3, 2) == 384 && scalars_scratch_bytes(SIZE_MAX / 4, 2) == SIZE_MAX, "saturate");
+  }
+  {
+    const VerifyLayout l = verify_layout(9);
+    const Region r[] = {WORDS(l, C, 72), WORDS(l, PI, 72), WORDS(l, y, 36), WORDS(l, z, 36), BYTES(l, cinf, 9), BYTES(l, pinf, 9)};
+    EXPECT(layout_ok("verify", r, l.bytes) && l.PI == 576 && l.y == 1152 && l.z == 1440 && l.cinf == 1728 && l.pinf == 1737 && l.bytes == 1752, "9 proofs: %zu", l.bytes);
+    const VerifyLayout o = verify_layout(1);
+    const Region q[] = {WORDS(o, C, 8), WORDS(o, PI, 8), WORDS(o, y, 4), WORDS(o, z, 4), BYTES(o, cinf, 1), BYTES(o, pinf, 1)};
+    EXPECT(layout_ok("verify of one", q, o.bytes) && o.y == 128 && o.z == 160 && o.cinf == 192 && o.pinf == 193 && o.bytes == 200 && verify_layout(SIZE_MAX / 8).bytes == SIZE_MAX,
+           "one proof: %zu", o.bytes);
+  }
+  {  // the weighted form, 2 proofs: K = 8 key points, P = 10 own, 10 columns in one part; 13 flag bytes, padded to 16
+    const WeightedLayout l = weighted_layout(2, 3, 3, 2);
+    const Region r[] = {WORDS(l, den, 48), WORDS(l, k, 144), WORDS(l, y, 8), WORDS(l, sc_own, 80), WORDS(l, sc_open, 16), WORDS(l, obases, 32), WORDS(l, partial, 40),
+                        WORDS(l, ksum, 32), WORDS(l, s, 4), WORDS(l, bad, 4), WORDS(l, m_own, 8), WORDS(l, m2, 8), WORDS(l, m_key, 8), WORDS(l, m1, 8), WORDS(l, sg, 8),
+                        WORDS(l, pxy, 16), WORDS(l, qxy, 32), BYTES(l, obinf, 4), BYTES(l, f_own, 1), BYTES(l, f2, 1), BYTES(l, f_key, 1), BYTES(l, f1, 1), BYTES(l, fsg, 1),
+                        BYTES(l, pinf, 2), BYTES(l, qinf, 2)};
+    EXPECT(layout_ok("weighted", r, l.bytes) && l.k == 384 && l.y == 1536 && l.sc_own == 1600 && l.sc_open == 2240 && l.obases == 2368 && l.partial == 2624 && l.ksum == 2944 &&
+               l.s == 3200 && l.bad == 3232 && l.m_own == 3264, "weighted: %zu", l.m_own);
+    EXPECT(l.m2 == 3328 && l.m_key == 3392 && l.m1 == 3456 && l.sg == 3520 && l.pxy == 3584 && l.qxy == 3712 && l.obinf == 3968 && l.f_own == 3972 && l.f2 == 3973 &&
+               l.f_key == 3974 && l.f1 == 3975 && l.fsg == 3976 && l.pinf == 3977 && l.qinf == 3979 && l.bytes == 3984, "weighted: %zu", l.bytes);
+  }
+  {  // one proof without public inputs
+    const WeightedLayout l = weighted_layout(2, 3, 0, 1);
+    const Region r[] = {WORDS(l, den, 0), WORDS(l, k, 72), WORDS(l, y, 4), WORDS(l, sc_own, 40), WORDS(l, sc_open, 8), WORDS(l, obases, 16), WORDS(l, partial, 40),
+                        WORDS(l, ksum, 32), WORDS(l, s, 4), WORDS(l, bad, 4), WORDS(l, m_own, 8), WORDS(l, m2, 8), WORDS(l, m_key, 8), WORDS(l, m1, 8), WORDS(l, sg, 8),
+                        WORDS(l, pxy, 16), WORDS(l, qxy, 32), BYTES(l, obinf, 2), BYTES(l, f_own, 1), BYTES(l, f2, 1), BYTES(l, f_key, 1), BYTES(l, f1, 1), BYTES(l, fsg, 1),
+                        BYTES(l, pinf, 2), BYTES(l, qinf, 2)};
+    EXPECT(layout_ok("weighted of one", r, l.bytes) && l.k == 0 && l.y == 576 && l.sc_own == 608 && l.partial == 1120 && l.ksum == 1440 && l.m_own == 1760 && l.pxy == 2080 &&
+               l.qxy == 2208 && l.obinf == 2464 && l.f_own == 2466 && l.pinf == 2471 && l.qinf == 2473 && l.bytes == 2480, "one proof: %zu", l.bytes);
+    EXPECT(weighted_layout(2, 3, 3, SIZE_MAX / 8).bytes == SIZE_MAX, "saturates");
+  }
+}
+
 int main() {
   constants_and_pins();
   terms_and_offsets();
   scratch_sums();
   chunks();
+  layouts();
   if (fails) {
     printf("%d of %zu checks failed\n", fails, checked);
     return 1;

@@ -177,6 +177,27 @@ def test_combine_against_the_discrete_logarithms(engine):
     assert np.array_equal(chunked[0], cf) and np.array_equal(chunked[1], cf_inf) and through_msm[1][2] == 1
 
 
+def test_combine_in_chunks_of_groups_longer_than_one_fold(engine):
+    """Groups of 17 and 18 terms, one more than a lane of the segmented sum folds: the sum runs in two stages and takes its words of the
+    chunk's lease.  Under a limit of 40 slots the groups {17, 2} are one chunk of two segments that goes through its own sums, the group of
+    18 the next one: every region of a chunk's lease is in use.  The same words as under the default limit, where all three are one chunk."""
+    rng = random.Random(0xE5)
+    sizes = [17, 2, 18]
+    gs = M.offsets(sizes)
+    logs = [rng.randrange(1, R) for _ in range(gs[-1])]
+    y = [rng.randrange(1 << 256) for _ in logs]
+    gamma = [rng.randrange(1 << 256) for _ in sizes]
+    c_xy, c_inf = commitments(logs)
+    whole = check_combine(engine, logs, y, gs, gamma, c_xy, c_inf)
+    try:
+        engine.set_scratch_limit(40 * SLOT)
+        chunked = check_combine(engine, logs, y, gs, gamma, c_xy, c_inf)
+    finally:
+        engine.set_scratch_limit(0)
+    for a, b in zip(whole, chunked):
+        assert np.array_equal(a, b)
+
+
 def test_round_trips_through_the_verifier(engine, srs):
     from sylow_amd import api
     api.set_engine(engine)

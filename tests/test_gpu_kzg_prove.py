@@ -164,6 +164,23 @@ def test_commit_in_chunks_under_a_scratch_limit(engine, srs):
         assert np.array_equal(a, b) and np.array_equal(a, c)
 
 
+def test_commit_in_short_chunks_of_polynomials_longer_than_one_fold(engine, srs):
+    """17 coefficients, one more than a lane of the segmented sum folds, so the sum runs in two stages and takes its words of the lease; a
+    limit that holds two of the five polynomials, so the chunks are 2, 2 and a last one of 1 and the sums pass through scratch: every region
+    of the short route's lease is in use."""
+    rng = random.Random(0xB4)
+    m, n = 5, 17
+    polys = [rand_poly(rng, n) for _ in range(m)]
+    whole = check_commit(engine, srs, polys)
+    try:
+        engine.set_scratch_limit(2 * n * K["KZG_SHORT_BYTES_PER_TERM"])
+        chunked = check_commit(engine, srs, polys)
+    finally:
+        engine.set_scratch_limit(0)
+    for a, b in zip(whole, chunked):
+        assert np.array_equal(a, b)
+
+
 # ---- the opening -------------------------------------------------------------------------------------------------------------------
 def check_open(engine, srs, polys, zs):
     n = len(polys[0])
