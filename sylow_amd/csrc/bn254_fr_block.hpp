@@ -1,6 +1,7 @@
 // bn254_fr_block.hpp -- what a block of BLOCK lanes does together over Fr, once, for the units that walk an array chunk by chunk
-// (kzg_evals.hip, fr_scan.hip): an element of a struct-of-arrays row mod r, the inverse of one value on a lone lane, the inverses of the
-// lane totals of a chunk through ONE inversion, and the prefix of the lane totals under + or *.  The lanes that take part and the doubling
+// (kzg_evals.hip, fr_scan.hip) or add a column up in two levels (the weighted checks): an element of a struct-of-arrays row mod r, the
+// inverse of one value on a lone lane, the inverses of the lane totals of a chunk through ONE inversion, the sum of the lane values, the
+// join of a column's partial sums, and the prefix of the lane totals under + or *.  The lanes that take part and the doubling
 // steps are kzg_evals_plan.hpp's.  All but the lone inversion are forced inline: a unit that includes this compiles the same device code as
 // one that spells them out.  Included after host.hpp or common.hpp.
 #pragma once
@@ -53,6 +54,31 @@ BN_DEV Fp block_inverses(const Fp& T, u32 (*pre)[8], u32 (*suf)[8], u32 (*inv)[8
     if (t + 1 < live) r = fr_mul(r, lds_get(suf, t + 1));
   }
   return r;
+}
+
+// Every thread of the block calls it: lane 0 gets the sum of the block's values mod r (the other lanes partial sums).  A modular sum is
+// exact and canonical: the order of the tree does not show in the words.  Ends on a barrier, so `part` is free for the next call.
+BN_DEV Fp block_sum(Fp v, u32 (*part)[8]) {
+  const int t = threadIdx.x;
+  lds_put(part, t, v);
+  __syncthreads();
+#pragma unroll 1
+  for (int off = BLOCK / 2; off > 0; off >>= 1) {
+    if (t < off) {                                             // reads rows off .. 2 off - 1, writes rows below off
+      v = fr_add(v, lds_get(part, t + off));
+      lds_put(part, t, v);
+    }
+    __syncthreads();
+  }
+  return v;
+}
+// The join of the weighted checks, a block per column: lane 0 gets the sum of the `parts` partials of column c of partial [4][cols * parts]
+// (the partial of (column, part) at index column * parts + part), what the blocks of the level before left through block_sum.
+BN_DEV Fp column_sum(const u64* partial, size_t cols, size_t parts, size_t c, u32 (*part)[8]) {
+  Fp acc = fr_zero();
+#pragma unroll 1
+  for (size_t k = threadIdx.x; k < parts; k += BLOCK) acc = fr_add(acc, load_plain(partial, cols * parts, c * parts + k, 0));
+  return block_sum(acc, part);
 }
 
 // The two operations of a scan over Fr: PRODUCT false is +, with the identity 0; true is *, with the identity 1.

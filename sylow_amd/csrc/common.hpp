@@ -69,6 +69,36 @@ BN_DEV G1W g1w_load_proj(const u64* a, size_t stride, size_t i) {
 BN_DEV void g1w_store_proj(u64* a, size_t stride, size_t i, const G1W& r) {
   store_fp(a, stride, i, 0, f29_to_fp(r.x)); store_fp(a, stride, i, 4, f29_to_fp(r.y)); store_fp(a, stride, i, 8, f29_to_fp(r.z));
 }
+// an affine SoA point on the carry-free core; a FLAGGED point is (0 : 1 : 0) whatever its coordinate words hold (inf NULL: none is flagged)
+BN_DEV G1W load_g1w_flagged(const u64* xy, const uint8_t* inf, size_t n, size_t i) {
+  const bool z = inf && inf[i];
+  G1W q;
+  q.x = OpsF29::select(f29_from_fp_reduced(load_fp(xy, n, i, 0)), OpsF29::zero(), z);
+  q.y = OpsF29::select(f29_from_fp_reduced(load_fp(xy, n, i, 4)), OpsF29::one(), z);
+  q.z = OpsF29::select(OpsF29::one(), OpsF29::zero(), z);
+  return q;
+}
+// a projective point on the carry-free core -> canonical affine coordinates and the identity flag: the one inversion of a lane's walk.
+// k_kzg_fold (kzg.hip) and k_groth16_vk_x (groth16.hip) keep this line spelt out: behind the call their registers are numbered differently
+// (docs/DESIGN_LOG.md, "One block sum, join and closing pair across the weighted checks")
+BN_DEV void g1w_to_affine(Fp& x, Fp& y, bool& inf, const G1W& p) { g1_to_affine(x, y, inf, G1P{f29_to_fp(p.x), f29_to_fp(p.y), f29_to_fp(p.z)}); }
+
+// Slot i in {0, 1} of the SoA pair list of stride 2 that closes a weighted check, e(A, G2gen) e(-B, tau) == 1, from an affine G1 point and its
+// flag: slot 0 is (A, G2gen); slot 1 is (-B, tau), y negated (reduced like Fp::new on the way) against the caller's 16 words.  pxy [8][2],
+// qxy [16][2], one flag each; a flagged slot is dropped by the product whatever its words hold.
+BN_DEV void store_closing_pair(int i, const Fp& x, const Fp& y, bool inf, const u64* tau, u64* pxy, uint8_t* pinf, u64* qxy, uint8_t* qinf) {
+  store_fp(pxy, 2, i, 0, x);
+  store_fp(pxy, 2, i, 4, i == 0 ? y : fp_neg(y));
+  pinf[i] = inf ? 1 : 0;
+  if (i == 0) {
+#pragma unroll
+    for (int c = 0; c < 4; ++c) store_fp(qxy, 2, 0, 4 * c, fp_const(C_G2_GEN[c]));
+  } else {
+#pragma unroll
+    for (int w = 0; w < 16; ++w) qxy[(size_t)w * 2 + 1] = tau[w];
+  }
+  qinf[i] = 0;
+}
 
 BN_DEV int wave_max(int v) {
 #pragma unroll

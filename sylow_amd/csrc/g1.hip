@@ -147,7 +147,7 @@ __global__ void HEAVY_BOUNDS k_g1_generator_mul(const u64* ks, const i32* __rest
     res = proj_add_lazy<OpsF29>(res, q1);                        // leaves out of line: inlined (OpsF29I) this loop measured 3.25 against 3.14 ms per 2^20
   }
   Fp x, y; bool rinf;
-  g1_to_affine(x, y, rinf, G1P{f29_to_fp(res.x), f29_to_fp(res.y), f29_to_fp(res.z)});
+  g1w_to_affine(x, y, rinf, res);
   store_fp(oxy, n, i, 0, x); store_fp(oxy, n, i, 4, y);
   oinf[i] = rinf ? 1 : 0;
 }
@@ -168,14 +168,7 @@ __global__ void HEAVY_BOUNDS k_g1_sum_fold_affine(const u64* pxy, const uint8_t*
   if (t >= L) return;
   G1W res = proj_zero<OpsF29>();
 #pragma unroll 1
-  for (size_t i = t; i < n; i += L) {
-    const bool inf = pinf && pinf[i];
-    G1W q;                                              // the identity joins as (0 : 1 : 0): the formulas are complete
-    q.x = OpsF29::select(f29_from_fp_reduced(load_fp(pxy, n, i, 0)), OpsF29::zero(), inf);
-    q.y = OpsF29::select(f29_from_fp_reduced(load_fp(pxy, n, i, 4)), OpsF29::one(), inf);
-    q.z = OpsF29::select(OpsF29::one(), OpsF29::zero(), inf);
-    res = proj_add_lazy<OpsF29>(res, q);
-  }
+  for (size_t i = t; i < n; i += L) res = proj_add_lazy<OpsF29>(res, load_g1w_flagged(pxy, pinf, n, i));      // the formulas are complete
   g1w_store_proj(acc, acc_stride, t, res);
 }
 // m projective points of acc (stride `stride`) -> L partial sums, in place
@@ -225,20 +218,11 @@ __global__ void HEAVY_BOUNDS k_g1_seg_fold(const u64* in, const uint8_t* inf, si
 #pragma unroll 1
   for (size_t k = part; k < m; k += parts) {
     const size_t i = k * n_seg + seg;
-    G1W q;
-    if (AFFINE_IN) {
-      const bool z = inf && inf[i];                     // a flagged point is (0 : 1 : 0) whatever its coordinate words hold
-      q.x = OpsF29::select(f29_from_fp_reduced(load_fp(in, stride_in, i, 0)), OpsF29::zero(), z);
-      q.y = OpsF29::select(f29_from_fp_reduced(load_fp(in, stride_in, i, 4)), OpsF29::one(), z);
-      q.z = OpsF29::select(OpsF29::one(), OpsF29::zero(), z);
-    } else {
-      q = g1w_load_proj(in, stride_in, i);
-    }
-    res = proj_add_lazy<OpsF29>(res, q);
+    res = proj_add_lazy<OpsF29>(res, AFFINE_IN ? load_g1w_flagged(in, inf, stride_in, i) : g1w_load_proj(in, stride_in, i));
   }
   if (AFFINE_OUT) {
     Fp x, y; bool rinf;
-    g1_to_affine(x, y, rinf, G1P{f29_to_fp(res.x), f29_to_fp(res.y), f29_to_fp(res.z)});
+    g1w_to_affine(x, y, rinf, res);
     store_fp(out, stride_out, seg, 0, x); store_fp(out, stride_out, seg, 4, y);
     oinf[seg] = rinf ? 1 : 0;
   } else {

@@ -4,8 +4,11 @@
 //   library's own stream-ordered calls.  The per-proof pairing check lives with the line-table kernels it reuses (groth16_pair.hpp,
 //   compiled as the tail of plk_multi.hip).
 #include "host.hpp"
+#include "bn254_fr_block.hpp"
+#include "weighted_plan.hpp"
 
 namespace g16 {
+static_assert(weighted_plan::WEIGHTED_BLOCK == BLOCK, "a part of a column sum is one block of BLOCK lanes");
 // ------------------------------------------------------------------ vk_x: shared bases, one proof per lane ----------
 // Window tables, built once per call by one lane per base: T[b][d] = d IC_b, d = 0..15, projective carry-free digits in the 7 x 16-byte
 // entry of ProjTableGlobal (bn254_pairing.hpp), 1792 bytes per base -- a verifying key of 17 bases is 30 KB, resident in L2 and mostly in
@@ -53,7 +56,7 @@ __global__ void HEAVY_BOUNDS k_groth16_vk_x(const uint8_t* table, const u64* inp
   }
   res = proj_add_lazy<OpsF29I>(res, tab_of(table, 0).get(1));      // + 1 IC_0
   Fp x, y; bool rinf;
-  g1_to_affine(x, y, rinf, G1P{f29_to_fp(res.x), f29_to_fp(res.y), f29_to_fp(res.z)});
+  g1_to_affine(x, y, rinf, G1P{f29_to_fp(res.x), f29_to_fp(res.y), f29_to_fp(res.z)});      // spelt out: see g1w_to_affine (common.hpp)
   store_fp(oxy, n, i, 0, x); store_fp(oxy, n, i, 4, y);
   oinf[i] = rinf ? 1 : 0;
 }
@@ -74,26 +77,7 @@ __global__ void __launch_bounds__(BLOCK) k_groth16_weighted_prep(const u64* weig
 // all mod r.  A modular sum is exact, so the order of the reduction does not show in the result.  Two levels, so that a few columns
 // still fill the GPU: block (col, part) of k_groth16_fr_sums adds up rows part * BLOCK + t, + parts * BLOCK, ... of its column and leaves one
 // partial; k_groth16_fr_sums_join, one block per column, adds the column's partials.  out [4][cols + 1]: the columns, then s once more
-// (the scalar of alpha) -- the scalar array that goes with k_groth16_weighted_prep's bases.
-constexpr size_t FR_ROWS_PER_LANE = 8, FR_PARTS_MAX = BLOCK;
-BN_DEV Fp fr_block_sum(Fp acc, u32 (*part)[8]) {          // every thread of the block calls it; thread 0 gets the sum
-  const int t = threadIdx.x;
-#pragma unroll
-  for (int w = 0; w < 8; ++w) part[t][w] = acc.v[w];
-  __syncthreads();
-#pragma unroll 1
-  for (int h = BLOCK / 2; h > 0; h >>= 1) {
-    if (t < h) {
-      const Fp a = fp_from_limbs(part[t][0], part[t][1], part[t][2], part[t][3], part[t][4], part[t][5], part[t][6], part[t][7]);
-      const Fp b = fp_from_limbs(part[t + h][0], part[t + h][1], part[t + h][2], part[t + h][3], part[t + h][4], part[t + h][5], part[t + h][6], part[t + h][7]);
-      const Fp s = fr_add(a, b);
-#pragma unroll
-      for (int w = 0; w < 8; ++w) part[t][w] = s.v[w];
-    }
-    __syncthreads();
-  }
-  return fp_from_limbs(part[0][0], part[0][1], part[0][2], part[0][3], part[0][4], part[0][5], part[0][6], part[0][7]);
-}
+// (the scalar of alpha) -- the scalar array that goes with k_groth16_weighted_prep's bases.  The number of parts: weighted_plan.hpp.
 // partial [4][cols * parts]: the partial of (col, part) at index col * parts + part
 __global__ void __launch_bounds__(BLOCK) k_groth16_fr_sums(const u64* wr, const u64* inputs, size_t n, size_t cols, size_t parts, u64* partial) {
   __shared__ u32 part[BLOCK][8];
@@ -105,16 +89,13 @@ __global__ void __launch_bounds__(BLOCK) k_groth16_fr_sums(const u64* wr, const 
     const Fp r = load_plain(wr, n, i, 0);
     acc = fr_add(acc, col == 0 ? r : fr_mul(r, fr_reduce_plain(load_plain(inputs, n_in, (col - 1) * n + i, 0))));
   }
-  const Fp s = fr_block_sum(acc, part);
+  const Fp s = block_sum(acc, part);
   if (threadIdx.x == 0) store_plain(partial, cols * parts, col * parts + pt, 0, s);
 }
 __global__ void __launch_bounds__(BLOCK) k_groth16_fr_sums_join(const u64* partial, size_t cols, size_t parts, u64* out) {
   __shared__ u32 part[BLOCK][8];
   const size_t col = blockIdx.x;
-  Fp acc = fp_from_limbs(0, 0, 0, 0, 0, 0, 0, 0);
-#pragma unroll 1
-  for (size_t k = threadIdx.x; k < parts; k += BLOCK) acc = fr_add(acc, load_plain(partial, cols * parts, col * parts + k, 0));
-  const Fp s = fr_block_sum(acc, part);
+  const Fp s = column_sum(partial, cols, parts, col, part);
   if (threadIdx.x == 0) {
     store_plain(out, cols + 1, col, 0, s);
     if (col == 0) store_plain(out, cols + 1, cols, 0, s);
@@ -138,23 +119,15 @@ __global__ void __launch_bounds__(BLOCK) k_groth16_weighted_pairs(const u64* ra,
     return;
   }
   const int which = (int)(i - n);
-  auto load = [](const u64* xy, const uint8_t* flags, size_t stride, size_t k) {      // the identity joins as (0 : 1 : 0): the formulas are complete
-    const bool z = flags[k] != 0;
-    G1W q;
-    q.x = OpsF29::select(f29_from_fp_reduced(load_fp(xy, stride, k, 0)), OpsF29::zero(), z);
-    q.y = OpsF29::select(f29_from_fp_reduced(load_fp(xy, stride, k, 4)), OpsF29::one(), z);
-    q.z = OpsF29::select(OpsF29::one(), OpsF29::zero(), z);
-    return q;
-  };
-  G1W p = proj_zero<OpsF29>();
+  G1W p = proj_zero<OpsF29>();                            // the identity joins as (0 : 1 : 0): the formulas are complete
   if (which == 1) {
 #pragma unroll 1
-    for (size_t j = 0; j < cols; ++j) p = proj_add_lazy<OpsF29>(p, load(prod, prod_inf, cols + 1, j));
+    for (size_t j = 0; j < cols; ++j) p = proj_add_lazy<OpsF29>(p, load_g1w_flagged(prod, prod_inf, cols + 1, j));
   } else {
-    p = which == 0 ? load(prod, prod_inf, cols + 1, cols) : load(sc, sc_inf, 1, 0);
+    p = which == 0 ? load_g1w_flagged(prod, prod_inf, cols + 1, cols) : load_g1w_flagged(sc, sc_inf, 1, 0);
   }
   Fp x, y; bool inf;
-  g1_to_affine(x, y, inf, G1P{f29_to_fp(p.x), f29_to_fp(p.y), f29_to_fp(p.z)});
+  g1w_to_affine(x, y, inf, p);
   if (!inf) y = fp_neg(y);
   store_fp(pxy, m, i, 0, x); store_fp(pxy, m, i, 4, y);
   pinf[i] = inf ? 1 : 0;
@@ -184,17 +157,18 @@ int32_t sylow_hip_groth16_batch_verify_weighted(const uint64_t* vk_alpha, const 
                                                 const uint64_t* inputs, const uint64_t* weights, size_t n, uint64_t* gt_out, uint8_t* is_one, void* stream) {
   ARGCHK((gt_out || is_one) && (n == 0 || (vk_alpha && vk_beta && vk_gamma && vk_delta && vk_ic && a_xy && b_xy && c_xy && weights && (inputs || !n_inputs))));
   if (!n) return sylow_hip_pairing_product_batch(nullptr, nullptr, nullptr, nullptr, 0, 1, gt_out, is_one, stream);
+  using namespace weighted_plan;
+  const Groth16WeightedLayout l = groth16_weighted_layout(n, n_inputs);
+  ARGCHK(l.bytes != SAT);
   hipStream_t st = (hipStream_t)stream;
-  const size_t cols = n_inputs + 1, nb = cols + 1, m = n + 3;
-  const size_t by_rows = (n + BLOCK * g16::FR_ROWS_PER_LANE - 1) / (BLOCK * g16::FR_ROWS_PER_LANE), parts = by_rows < g16::FR_PARTS_MAX ? by_rows : g16::FR_PARTS_MAX;
-  // scratch (u64 words): weights mod r [4][n], r_i A_i [8][n], bases / scalars / products of the l + 2 per-call terms, sum_i r_i C_i [8],
-  // the pair list [8 + 16][n + 3]; then the flags
-  const size_t w_wr = 4 * n, w_ra = 8 * n, w_bases = 8 * nb, w_sums = 4 * nb, w_prod = 8 * nb, w_sc = 8, w_p = 8 * m, w_q = 16 * m, w_part = 4 * cols * parts;
+  const size_t cols = groth16_columns(n_inputs), nb = groth16_bases(n_inputs), m = groth16_pairs(n), parts = groth16_parts(n);
   host::Lease ws;
-  int32_t rc = ws.acquire((w_wr + w_ra + w_bases + w_sums + w_prod + w_sc + w_p + w_q + w_part) * sizeof(u64) + n + nb + 1 + 2 * m, st);
+  int32_t rc = ws.acquire(l.bytes, st);
   if (rc != SYLOW_HIP_OK) return rc;
-  u64 *wr = (u64*)ws.p, *ra = wr + w_wr, *bases = ra + w_ra, *sums = bases + w_bases, *prod = sums + w_sums, *sc = prod + w_prod, *pxy = sc + w_sc, *qxy = pxy + w_p, *partial = qxy + w_q;
-  uint8_t *ra_inf = (uint8_t*)(partial + w_part), *prod_inf = ra_inf + n, *sc_inf = prod_inf + nb, *pinf = sc_inf + 1, *qinf = pinf + m;
+  u64 *wr = ws.at<u64>(l.wr), *ra = ws.at<u64>(l.ra), *bases = ws.at<u64>(l.bases), *sums = ws.at<u64>(l.sums), *prod = ws.at<u64>(l.prod), *sc = ws.at<u64>(l.sc),
+      *pxy = ws.at<u64>(l.pxy), *qxy = ws.at<u64>(l.qxy), *partial = ws.at<u64>(l.partial);
+  uint8_t *ra_inf = ws.at<uint8_t>(l.ra_inf), *prod_inf = ws.at<uint8_t>(l.prod_inf), *sc_inf = ws.at<uint8_t>(l.sc_inf), *pinf = ws.at<uint8_t>(l.pinf),
+          *qinf = ws.at<uint8_t>(l.qinf);
   g16::k_groth16_weighted_prep<<<GRID(n > nb ? n : nb)>>>(weights, n, wr, vk_ic, vk_alpha, cols, bases);
   g16::k_groth16_fr_sums<<<dim3((unsigned)cols, (unsigned)parts), dim3(BLOCK), 0, st>>>(wr, inputs, n, cols, parts, partial);
   g16::k_groth16_fr_sums_join<<<dim3((unsigned)cols), dim3(BLOCK), 0, st>>>(partial, cols, parts, sums);

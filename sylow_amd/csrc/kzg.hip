@@ -3,8 +3,11 @@
 //   the shape of the same-signer BLS check, whose entry points live with the fused kernel they launch: plk_verify.hip),
 //   the Fr preparation of the weighted one-boolean test, and that test itself, composed from the library's own stream-ordered calls.
 #include "host.hpp"
+#include "bn254_fr_block.hpp"
+#include "weighted_plan.hpp"
 
 namespace kzg {
+static_assert(weighted_plan::WEIGHTED_BLOCK == BLOCK, "the preparation runs a lane per opening in blocks of BLOCK lanes");
 // any 256-bit word -> its residue mod r as eight limbs (the rule of sylow_hip_evm_ecmul_batch)
 BN_DEV void load_scalar_mod_r(u32 (&k)[8], const u64* base, size_t n, size_t i) {
   const Fp s = fr_reduce_plain(load_plain(base, n, i, 0));
@@ -82,15 +85,6 @@ BN_DEV G1W glv_walk(G1W t1, const u32 (&k)[8], G1TableGlobal& tab) {
   }
   return res;
 }
-// an affine SoA point on the carry-free core; a FLAGGED point is (0 : 1 : 0) whatever its coordinate words hold
-BN_DEV G1W load_g1w_flagged(const u64* xy, const uint8_t* inf, size_t n, size_t i) {
-  const bool z = inf && inf[i];
-  G1W q;
-  q.x = OpsF29::select(f29_from_fp_reduced(load_fp(xy, n, i, 0)), OpsF29::zero(), z);
-  q.y = OpsF29::select(f29_from_fp_reduced(load_fp(xy, n, i, 4)), OpsF29::one(), z);
-  q.z = OpsF29::select(OpsF29::one(), OpsF29::zero(), z);
-  return q;
-}
 
 // ------------------------------------------------------------------ the fold: one opening per lane, ONE accumulator ----------
 // F = z pi - y G1gen + C:  the GLV walk of z pi (above) leaves the accumulator projective; y G1gen is the 32 signed byte digits of y mod r
@@ -134,7 +128,7 @@ __global__ void HEAVY_BOUNDS k_kzg_fold(const u64* cxy, const uint8_t* cinf, con
     }
     res = proj_add_lazy<OpsF29>(res, load_g1w_flagged(cxy, cinf, n, i));
     Fp x, y; bool rinf;
-    g1_to_affine(x, y, rinf, G1P{f29_to_fp(res.x), f29_to_fp(res.y), f29_to_fp(res.z)});
+    g1_to_affine(x, y, rinf, G1P{f29_to_fp(res.x), f29_to_fp(res.y), f29_to_fp(res.z)});      // spelt out: see g1w_to_affine (common.hpp)
     store_fp(oxy, n, i, 0, x); store_fp(oxy, n, i, 4, y);
     oinf[i] = rinf ? 1 : 0;
     if (nxy) {
@@ -146,25 +140,6 @@ __global__ void HEAVY_BOUNDS k_kzg_fold(const u64* cxy, const uint8_t* cinf, con
 }
 
 // ------------------------------------------------------------------ the weighted test's scalar side ----------
-// every thread of the block calls it; thread 0 gets the sum mod r (a modular sum is exact: the order does not show in the result)
-BN_DEV Fp fr_block_sum(Fp acc, u32 (*part)[8]) {
-  const int t = threadIdx.x;
-#pragma unroll
-  for (int w = 0; w < 8; ++w) part[t][w] = acc.v[w];
-  __syncthreads();
-#pragma unroll 1
-  for (int h = BLOCK / 2; h > 0; h >>= 1) {
-    if (t < h) {
-      const Fp a = fp_from_limbs(part[t][0], part[t][1], part[t][2], part[t][3], part[t][4], part[t][5], part[t][6], part[t][7]);
-      const Fp b = fp_from_limbs(part[t + h][0], part[t + h][1], part[t + h][2], part[t + h][3], part[t + h][4], part[t + h][5], part[t + h][6], part[t + h][7]);
-      const Fp s = fr_add(a, b);
-#pragma unroll
-      for (int w = 0; w < 8; ++w) part[t][w] = s.v[w];
-    }
-    __syncthreads();
-  }
-  return fp_from_limbs(part[0][0], part[0][1], part[0][2], part[0][3], part[0][4], part[0][5], part[0][6], part[0][7]);
-}
 // Per opening: r_i mod r -> wr [4][n] and column i of sc [4][2n]; r_i z_i mod r -> column n + i of sc; C_i and pi_i (words and flags as given)
 // -> columns i and n + i of bases [8][2n] / binf [2n] -- the 2n terms of ONE multi-scalar multiplication; and r_i y_i mod r into the block's
 // partial sum, partial [4][gridDim.x].  Launched with exactly ceil(n / BLOCK) blocks.
@@ -185,16 +160,13 @@ __global__ void __launch_bounds__(BLOCK) k_kzg_weighted_prep(const u64* cxy, con
     binf[i] = (cinf && cinf[i]) ? 1 : 0;
     binf[n + i] = (pinf && pinf[i]) ? 1 : 0;
   }
-  const Fp s = fr_block_sum(acc, part);
+  const Fp s = block_sum(acc, part);
   if (threadIdx.x == 0) store_plain(partial, gridDim.x, blockIdx.x, 0, s);
 }
 // one block: s = sum of the partials = sum_i r_i y_i mod r, out [4][1]
 __global__ void __launch_bounds__(BLOCK) k_kzg_fr_join(const u64* partial, size_t parts, u64* out) {
   __shared__ u32 part[BLOCK][8];
-  Fp acc = fp_from_limbs(0, 0, 0, 0, 0, 0, 0, 0);
-#pragma unroll 1
-  for (size_t k = threadIdx.x; k < parts; k += BLOCK) acc = fr_add(acc, load_plain(partial, parts, k, 0));
-  const Fp s = fr_block_sum(acc, part);
+  const Fp s = column_sum(partial, 1, parts, 0, part);
   if (threadIdx.x == 0) store_plain(out, 1, 0, 0, s);
 }
 // The two literal pairs as one SoA pair list of stride 2: lane 0 writes (m1 - s G1gen, G2gen), lane 1 writes (-m2, tau_g2), with
@@ -210,18 +182,9 @@ __global__ void __launch_bounds__(64) k_kzg_weighted_pairs(const u64* m1, const 
     p = proj_add_lazy<OpsF29>(p, g);
   }
   Fp x, y; bool inf;
-  g1_to_affine(x, y, inf, G1P{f29_to_fp(p.x), f29_to_fp(p.y), f29_to_fp(p.z)});
-  if (i == 1 && !inf) y = fp_neg(y);
-  store_fp(pxy, 2, i, 0, x); store_fp(pxy, 2, i, 4, y);
-  pinf[i] = inf ? 1 : 0;
-  if (i == 0) {
-#pragma unroll
-    for (int c = 0; c < 4; ++c) store_fp(qxy, 2, 0, 4 * c, fp_const(C_G2_GEN[c]));
-  } else {
-#pragma unroll
-    for (int w = 0; w < 16; ++w) qxy[(size_t)w * 2 + 1] = tau[w];
-  }
-  qinf[i] = 0;
+  g1w_to_affine(x, y, inf, p);
+  if (i == 0) store_closing_pair(0, x, y, inf, tau, pxy, pinf, qxy, qinf);
+  else store_closing_pair(1, x, y, inf, tau, pxy, pinf, qxy, qinf);
 }
 }  // namespace kzg
 
@@ -255,17 +218,18 @@ int32_t sylow_hip_kzg_batch_verify_weighted(const uint64_t* tau_g2_xy, const uin
                                             uint64_t* gt_out, uint8_t* is_one, void* stream) {
   ARGCHK((gt_out || is_one) && (n == 0 || (tau_g2_xy && c_xy && z && y && pi_xy && weights)));
   if (!n) return sylow_hip_pairing_product_batch(nullptr, nullptr, nullptr, nullptr, 0, 1, gt_out, is_one, stream);
+  using namespace weighted_plan;
+  const KzgWeightedLayout l = kzg_weighted_layout(n);
+  ARGCHK(l.bytes != SAT);
   hipStream_t st = (hipStream_t)stream;
-  const size_t parts = (n + BLOCK - 1) / BLOCK;
-  // scratch (u64 words): weights mod r [4][n]; the 2n scalars and bases of the first multi-scalar multiplication; the block partials and s;
-  // m1, m2, s G1gen [8] each; the pair list [8 + 16][2]; then the flags
-  const size_t w_wr = 4 * n, w_sc = 8 * n, w_bases = 16 * n, w_part = 4 * parts, w_s = 4, w_pt = 8, w_p = 16, w_q = 32;
+  const size_t parts = kzg_parts(n);
   host::Lease ws;
-  int32_t rc = ws.acquire((w_wr + w_sc + w_bases + w_part + w_s + 3 * w_pt + w_p + w_q) * sizeof(u64) + 2 * n + 3 + 4, st);
+  int32_t rc = ws.acquire(l.bytes, st);
   if (rc != SYLOW_HIP_OK) return rc;
-  u64 *wr = (u64*)ws.p, *sc = wr + w_wr, *bases = sc + w_sc, *partial = bases + w_bases, *s = partial + w_part, *m1 = s + w_s, *m2 = m1 + w_pt, *sg = m2 + w_pt,
-      *pxy = sg + w_pt, *qxy = pxy + w_p;
-  uint8_t *binf = (uint8_t*)(qxy + w_q), *m1inf = binf + 2 * n, *m2inf = m1inf + 1, *sginf = m2inf + 1, *pinf = sginf + 1, *qinf = pinf + 2;
+  u64 *wr = ws.at<u64>(l.wr), *sc = ws.at<u64>(l.sc), *bases = ws.at<u64>(l.bases), *partial = ws.at<u64>(l.partial), *s = ws.at<u64>(l.s), *m1 = ws.at<u64>(l.m1),
+      *m2 = ws.at<u64>(l.m2), *sg = ws.at<u64>(l.sg), *pxy = ws.at<u64>(l.pxy), *qxy = ws.at<u64>(l.qxy);
+  uint8_t *binf = ws.at<uint8_t>(l.binf), *m1inf = ws.at<uint8_t>(l.m1inf), *m2inf = ws.at<uint8_t>(l.m2inf), *sginf = ws.at<uint8_t>(l.sginf),
+          *pinf = ws.at<uint8_t>(l.pinf), *qinf = ws.at<uint8_t>(l.qinf);
   kzg::k_kzg_weighted_prep<<<dim3((unsigned)parts), dim3(BLOCK), 0, st>>>(c_xy, c_inf, pi_xy, pi_inf, z, y, weights, n, wr, sc, bases, binf, partial);
   kzg::k_kzg_fr_join<<<1, BLOCK, 0, st>>>(partial, parts, s);
   rc = sylow_hip_g1_msm(bases, binf, sc, 2 * n, m1, m1inf, stream);                        // sum r_i C_i + sum (r_i z_i) pi_i

@@ -205,18 +205,8 @@ __global__ void __launch_bounds__(64) k_cells_pairs(const u64* f, const uint8_t*
                                                     u64* qxy, uint8_t* qinf) {
   const size_t i = TID;
   if (i >= 2) return;
-  const Fp x = load_fp(i == 0 ? f : p, 1, 0, 0), y = load_fp(i == 0 ? f : p, 1, 0, 4);
-  store_fp(pxy, 2, i, 0, x);
-  store_fp(pxy, 2, i, 4, i == 0 ? y : fp_neg(y));
-  pinf[i] = (i == 0 ? finf[0] : pinf_in[0]) ? 1 : 0;
-  if (i == 0) {
-#pragma unroll
-    for (int c = 0; c < 4; ++c) store_fp(qxy, 2, 0, 4 * c, fp_const(C_G2_GEN[c]));
-  } else {
-#pragma unroll
-    for (int w = 0; w < (int)G2_WORDS; ++w) qxy[(size_t)w * 2 + 1] = tau[w];
-  }
-  qinf[i] = 0;
+  if (i == 0) store_closing_pair(0, load_fp(f, 1, 0, 0), load_fp(f, 1, 0, 4), finf[0] != 0, tau, pxy, pinf, qxy, qinf);
+  else store_closing_pair(1, load_fp(p, 1, 0, 0), load_fp(p, 1, 0, 4), pinf_in[0] != 0, tau, pxy, pinf, qxy, qinf);
 }
 // is_one <- [Gt is the identity] AND the range flag; the flag itself where the caller wants it
 __global__ void __launch_bounds__(64) k_cells_close(const uint8_t* one, const uint8_t* flag, uint8_t* is_one, uint8_t* in_range_out) {

@@ -18,22 +18,8 @@ static_assert(EVALS_LOG_N_MAX == ntt_plan::NTT_LOG_N_MAX, "the domains of the tr
 constexpr int L = EVALS_LANE_ELEMS, CH = (int)EVALS_CHUNK, W_INV = EVALS_LOG_N_MAX;      // W_INV: the slot of w^-1
 
 struct Scalar : FrArg {};      // a kernel names its parameter types in its symbol: this one stays a type of this namespace so that the symbol does not move
-// elem, fr_inv_lone and block_inverses -- the chunk's ONE inversion -- are bn254_fr_block.hpp's: fr_scan.hip runs the same
-// Every thread of the block calls it: lane 0 gets the sum of the block's values (the other lanes partial sums).  Ends on a barrier.
-BN_DEV Fp block_sum(Fp v, u32 (*part)[8]) {
-  const int t = threadIdx.x;
-  lds_put(part, t, v);
-  __syncthreads();
-#pragma unroll 1
-  for (int off = BLOCK / 2; off > 0; off >>= 1) {
-    if (t < off) {                                             // reads rows off .. 2 off - 1, writes rows below off
-      v = fr_add(v, lds_get(part, t + off));
-      lds_put(part, t, v);
-    }
-    __syncthreads();
-  }
-  return v;
-}
+// elem, fr_inv_lone, block_inverses -- the chunk's ONE inversion -- and block_sum are bn254_fr_block.hpp's: fr_scan.hip and the weighted
+// checks run the same
 
 // ---- sylow_hip_fr_batch_inv ----------------------------------------------------------------------------------------------------------------
 // A block per chunk, walked with a stride of whole blocks.  Forward, a lane multiplies its L elements together and keeps the L prefix

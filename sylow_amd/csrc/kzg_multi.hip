@@ -5,7 +5,7 @@
 // Tiles, grids, the flush length, scratch and the chunks of the combined commitments: kzg_multi_plan.hpp -- nothing here decides one.
 #include "host.hpp"
 #include "bn254_fr_acc.hpp"
-#include "bn254_fr_dev.hpp"
+#include "bn254_fr_block.hpp"
 #include "kzg_multi_plan.hpp"
 
 namespace kzgm {
@@ -106,15 +106,8 @@ __global__ void __launch_bounds__(BLOCK) k_kzgm_fold_values(const u64* y, const 
     Fp s = fr_zero();
 #pragma unroll 1
     for (size_t j = gs[g] + (size_t)t; j < j1; j += BLOCK) s = fr_add(s, fr_mul(fr_reduce_plain(load_plain(y, m, j, 0)), load_plain(pow, m, j, 0)));
-    lds_put(part, t, s);
-    __syncthreads();
-#pragma unroll 1
-    for (int off = BLOCK / 2; off > 0; off >>= 1) {
-      if (t < off) lds_put(part, t, fr_add(lds_get(part, t), lds_get(part, t + off)));
-      __syncthreads();
-    }
-    if (t == 0) store_plain(yf, G, g, 0, lds_get(part, 0));
-    __syncthreads();                                          // part is free for the next group
+    s = block_sum(s, part);                                   // ends on a barrier: part is free for the next group
+    if (t == 0) store_plain(yf, G, g, 0, s);
   }
 }
 // The padded layout of `n_seg` groups from g0 on, `c` slots each, term-major (slot k of group g0 + s at index k n_seg + s, what

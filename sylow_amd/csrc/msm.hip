@@ -22,7 +22,7 @@ struct G1Lane {
   }
   static BN_DEV void finish(u64* oxy, uint8_t* oinf, int, const G1W& acc) {
     Fp x, y; bool inf;
-    g1_to_affine(x, y, inf, G1P{f29_to_fp(acc.x), f29_to_fp(acc.y), f29_to_fp(acc.z)});
+    g1w_to_affine(x, y, inf, acc);
     store_fp(oxy, 1, 0, 0, x); store_fp(oxy, 1, 0, 4, y);
     oinf[0] = inf ? 1 : 0;
   }

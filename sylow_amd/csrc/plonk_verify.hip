@@ -175,20 +175,6 @@ __global__ void __launch_bounds__(BLOCK) k_pv_veto(const uint8_t* status, size_t
 }
 
 // ------------------------------------------------------------------ the weighted form's scalar side ----------
-// every thread of the block calls it; thread 0 gets the sum mod r (a modular sum is exact: the order does not show in the result).  The
-// barrier in front frees `part` of the call before.
-BN_DEV Fp block_sum(const Fp& acc, u32 (*part)[8]) {
-  const int t = threadIdx.x;
-  __syncthreads();
-  lds_put(part, t, acc);
-  __syncthreads();
-#pragma unroll 1
-  for (int h = BLOCK / 2; h > 0; h >>= 1) {
-    if (t < h) lds_put(part, t, fr_add(lds_get(part, t), lds_get(part, t + h)));
-    __syncthreads();
-  }
-  return lds_get(part, 0);
-}
 // Per proof i, a lane each, launched with exactly ceil(m / BLOCK) blocks: rho_i = weights_i mod r; rho_i k_(c,i) for the proof's own terms
 // into sc_own [4][(W + E + 3) m] at the place of the point in proof_xy; rho_i and rho_i u_i into sc_open [4][2 m] at i and m + i beside
 // W_zeta and W_omega in obases [8][2 m] / obinf; and per column -- the 2 W + 2 key terms rho_i k_(c,i), then rho_i y_i, then 1 for a proof
@@ -229,11 +215,8 @@ __global__ void __launch_bounds__(BLOCK) k_pv_weighted_prep(const u64* k, const 
 // a block per column: the sum of its partials -- a key column into ksum [4][2 W + 2], s into s_out [4][1], the count into bad [4][1]
 __global__ void __launch_bounds__(BLOCK) k_pv_join(const u64* partial, size_t parts, int W, u64* ksum, u64* s_out, u64* bad) {
   __shared__ u32 part[BLOCK][8];
-  const size_t c = blockIdx.x, K = key_points(W), cols = weighted_columns(W);
-  Fp acc = fr_zero();
-#pragma unroll 1
-  for (size_t q = threadIdx.x; q < parts; q += BLOCK) acc = fr_add(acc, load_plain(partial, cols * parts, c * parts + q, 0));
-  const Fp s = block_sum(acc, part);
+  const size_t c = blockIdx.x, K = key_points(W);
+  const Fp s = column_sum(partial, weighted_columns(W), parts, c, part);
   if (threadIdx.x == 0) {
     if (c < K) store_plain(ksum, K, c, 0, s);
     else store_plain(c == column_s(W) ? s_out : bad, 1, 0, 0, s);
@@ -245,18 +228,8 @@ __global__ void __launch_bounds__(64) k_pv_pairs(const u64* m1s, const uint8_t* 
                                                  u64* qxy, uint8_t* qinf) {
   const size_t i = TID;
   if (i >= 2) return;
-  if (i == 0) {
-    store_fp(pxy, 2, 0, 0, load_fp(m1s, 1, 0, 0)); store_fp(pxy, 2, 0, 4, load_fp(m1s, 1, 0, 4));
-    pinf[0] = m1sinf[0] ? 1 : 0;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) store_fp(qxy, 2, 0, 4 * c, fp_const(C_G2_GEN[c]));
-  } else {
-    store_fp(pxy, 2, 1, 0, load_fp(m2, 1, 0, 0)); store_fp(pxy, 2, 1, 4, fp_neg(load_fp(m2, 1, 0, 4)));
-    pinf[1] = m2inf[0] ? 1 : 0;
-#pragma unroll
-    for (int w = 0; w < 16; ++w) qxy[(size_t)w * 2 + 1] = tau[w];
-  }
-  qinf[i] = 0;
+  if (i == 0) store_closing_pair(0, load_fp(m1s, 1, 0, 0), load_fp(m1s, 1, 0, 4), m1sinf[0] != 0, tau, pxy, pinf, qxy, qinf);
+  else store_closing_pair(1, load_fp(m2, 1, 0, 0), load_fp(m2, 1, 0, 4), m2inf[0] != 0, tau, pxy, pinf, qxy, qinf);
 }
 // is_one = 0 when a live proof's zeta lay in the domain
 __global__ void __launch_bounds__(64) k_pv_veto_one(const u64* bad, uint8_t* is_one) {

@@ -179,6 +179,34 @@ def test_weighted_gt_is_the_oracle_product_over_the_literal_pairs(engine, pools,
         assert np.array_equal(gt[0], want_gt) and is_one == want_one and np.array_equal(want_gt, M.ONE48) == want_one
 
 
+def test_weighted_at_2049_proofs_joins_two_parts_of_every_column_sum(engine, pools):
+    """2048 proofs are one part of a column sum (256 lanes of 8 rows); 2049 are two, so k_groth16_fr_sums_join adds more than one partial
+    per column.  The batch is the pool tiled (row i is pool row i mod 64) under distinct odd 64-bit weights: the literal pairs are linear in
+    r_i with the points and inputs fixed per pool row, so the product is the pool's under the sums of the weights that fall on each pool row,
+    and canonical Gt words make the two equal word for word.  Once all valid; once with exactly ONE invalid row, the last one (the row
+    past 2048), which the model carries as a 65th row under its own weight.  (The cap of 256 parts needs more than 524288 proofs: no GPU
+    test reaches it, tests/test_weighted_plan.py pins it on the host.)"""
+    n = 2049
+    assert (n - 1 + 8 * 256 - 1) // (8 * 256) == 1 and (n + 8 * 256 - 1) // (8 * 256) == 2
+    idx = np.arange(n) % POOL
+    w64 = (2 * np.arange(n, dtype=np.uint64) + np.uint64(1)) * np.uint64(0x9E3779B97F4A7C15)        # odd times odd mod 2^64: distinct, odd
+    assert len(np.unique(w64)) == n and (w64 & np.uint64(1)).all()
+    w = w64.tolist()
+    collapse = lambda rows: [sum(w[i] for i in rows if idx[i] == k) % M.R for k in range(POOL)]
+    good = pools.valid.take(idx)
+    gt, is_one = weighted(engine, good, w)
+    want_gt, literal = M.weighted_product(pools.valid, collapse(range(n)))
+    assert literal and np.array_equal(gt[0], want_gt) and np.array_equal(want_gt, M.ONE48) and is_one
+    bad_row = n - 1
+    one_bad = pools.valid.take(idx)
+    one_bad.a[bad_row, 4:8] = M.limbs([M.P - M.ints(one_bad.a[bad_row, 4:8])[0]])[0]                   # A negated: that proof alone fails
+    model = one_bad.take(list(range(POOL)) + [bad_row])
+    want_gt, literal = M.weighted_product(model, collapse(range(n - 1)) + [w[bad_row]])
+    assert literal and not np.array_equal(want_gt, M.ONE48)
+    gt, is_one = weighted(engine, one_bad, w)
+    assert np.array_equal(gt[0], want_gt) and not is_one
+
+
 def test_weighted_inputs_and_weights_are_any_256_bit_words(engine, pools):
     """inputs r - 1, r, r + 1, p, 2^256 - 1 on the weighted path (the column sums reduce them mod r), weights of the same kind: the Gt words
     are the oracle's product over the literal pairs, and equal those of the same batch with every word reduced by hand"""
