@@ -291,6 +291,25 @@ SIGNATURES_PVERIFY = {
     "sylow_pverify_batch_verify_weighted": [c_u64p] + _PV_PTS + _PV_IN + [c_u64p] + _PV_DIMS + [c_u64p, c_u8p, c_u8p, c_vp],
 }
 
+# the entry points of include/sylow_poseidon.h (batched Poseidon over Fr and Poseidon Merkle trees): a tenth table, bound by the same load().
+# Their prefix is sylow_poseidon_: the sets of symbols under the older prefixes are closed (the header says why)
+_c_i64 = ctypes.c_int64
+_PS_PATH = [c_u64p, c_u64p, c_u64p, c_u64p, c_i32, c_sz]                # table, leaf, index, siblings, depth, q
+SIGNATURES_POSEIDON = {
+    "sylow_poseidon_table_words": [c_i32],
+    "sylow_poseidon_prepare": [c_i32, c_u64p, c_vp],
+    "sylow_poseidon_permute_batch": [c_u64p, c_i32, c_u64p, c_sz, c_u64p, c_vp],
+    "sylow_poseidon_permute_batch_tuned": [c_u64p, c_i32, c_u64p, c_sz, c_i32, _c_i64, c_u64p, c_vp],
+    "sylow_poseidon_hash_batch": [c_u64p, c_i32, c_u64p, c_u64p, c_sz, c_u64p, c_vp],
+    "sylow_poseidon_hash_batch_tuned": [c_u64p, c_i32, c_u64p, c_u64p, c_sz, c_i32, _c_i64, c_u64p, c_vp],
+    "sylow_poseidon_merkle_build_batch": [c_u64p, c_u64p, c_i32, c_sz, c_u64p, c_u64p, c_vp],
+    "sylow_poseidon_merkle_build_batch_tuned": [c_u64p, c_u64p, c_i32, c_sz, _c_i64, _c_i64, c_u64p, c_u64p, c_vp],
+    "sylow_poseidon_merkle_open_batch": [c_u64p, c_u64p, c_i32, c_sz, c_u64p, c_u64p, c_sz, c_u64p, c_u8p, c_vp],
+    "sylow_poseidon_merkle_root_batch": _PS_PATH + [c_u64p, c_u8p, c_vp],
+    "sylow_poseidon_merkle_verify_batch": _PS_PATH + [c_u64p, c_sz, c_u8p, c_u8p, c_vp],
+    "sylow_poseidon_merkle_verify_batch_tuned": _PS_PATH + [c_u64p, c_sz, c_i32, _c_i64, c_u8p, c_u8p, c_vp],
+}
+
 # SYLOW_HIP_OPT_* of include/sylow_hip.h.  The LIBRARY reads no environment variable; this host layer does, once, when it loads the library:
 # SYLOW_HIP_<NAME>=<integer> becomes sylow_hip_set_option(<NAME>, value) -- what tests/test_gpu_routes.py and the A/B scripts under tools/ set
 OPTIONS = {"STAGGER": 0, "MULTI_TABLES": 1, "WIDE_TAIL": 2, "WIDE_PACK": 3, "AGG_FORK": 4, "SIGN_WIDE_MAX": 5, "WIDE_MAX": 6, "WIDE_VERIFY_MAX": 7,
@@ -344,7 +363,7 @@ def load():
         lib = ctypes.CDLL(LIB_PATH)
         for name, argtypes in list(SIGNATURES.items()) + list(SIGNATURES_KZG_POINTS.items()) + list(SIGNATURES_KZG_COSETS.items()) + \
                 list(SIGNATURES_KZG_RECOVER.items()) + list(SIGNATURES_KZG_CELLS.items()) + list(SIGNATURES_FR_SCAN.items()) + list(SIGNATURES_PLONK.items()) + list(SIGNATURES_POPEN.items()) + \
-                list(SIGNATURES_PVERIFY.items()):
+                list(SIGNATURES_PVERIFY.items()) + list(SIGNATURES_POSEIDON.items()):
             fn = getattr(lib, name)  # AttributeError if the symbol is missing
             fn.argtypes = argtypes
             fn.restype = _RESTYPE.get(name, c_i32)

@@ -18,8 +18,9 @@ HEADER_FR_SCAN = os.path.join(os.path.dirname(_HERE), "include", "sylow_hip_fr_s
 HEADER_PLONK = os.path.join(os.path.dirname(_HERE), "include", "sylow_plonk.h")                    # its entry points are sylow_plonk_*
 HEADER_POPEN = os.path.join(os.path.dirname(_HERE), "include", "sylow_popen.h")                    # its entry points are sylow_popen_*
 HEADER_PVERIFY = os.path.join(os.path.dirname(_HERE), "include", "sylow_pverify.h")                # its entry points are sylow_pverify_*
+HEADER_POSEIDON = os.path.join(os.path.dirname(_HERE), "include", "sylow_poseidon.h")              # its entry points are sylow_poseidon_*
 ITEMSIZE = {"u64": 8, "i64": 8, "u8": 1, "i32": 4, "void": 1}
-_EXPR_OK = re.compile(r"^[\w\s+*()]+$")
+_EXPR_OK = re.compile(r"^[\w\s+*()-]+$")      # `-`: the n - 1 nodes of a tree (sylow_poseidon.h)
 
 
 class Shape:
@@ -32,7 +33,7 @@ class Shape:
         """minimum element count for the call's integer arguments (None = not expressible: `[*]`)"""
         if self.expr == "*":
             return None
-        return int(eval(self.expr, {"__builtins__": {}}, values))      # expr is [\w+*() ] only (checked at parse time)
+        return int(eval(self.expr, {"__builtins__": {}}, values))      # expr is [\w+*()- ] only (checked at parse time)
 
     def nbytes(self, values):
         n = self.elements(values)
@@ -43,7 +44,7 @@ def parse(path: str = HEADER):
     """-> {entry point: (parameter names in order, {parameter: Shape})} for every annotated prototype"""
     text = open(path).read()
     out = {}
-    for m in re.finditer(r"/\* @shape ([^\n]*?) \*/\s*\n\s*int32_t\s+(sylow_(?:hip|plonk|popen|pverify)_\w+)\s*\(([^)]*)\)\s*;", text):
+    for m in re.finditer(r"/\* @shape ([^\n]*?) \*/\s*\n\s*int32_t\s+(sylow_(?:hip|plonk|popen|pverify|poseidon)_\w+)\s*\(([^)]*)\)\s*;", text):
         params = re.sub(r"/\*.*?\*/", " ", m.group(3))                  # inline remarks like `uint8_t* out /*[n][64]*/`
         names = [p.replace("*", " ").split()[-1] for p in " ".join(params.split()).split(",")]
         shapes = {}
@@ -67,7 +68,8 @@ def table():
     if _TABLE is None:
         try:
             _TABLE = {**parse(), **parse(HEADER_KZG_POINTS), **parse(HEADER_KZG_COSETS), **parse(HEADER_KZG_RECOVER),
-                      **parse(HEADER_KZG_CELLS), **parse(HEADER_FR_SCAN), **parse(HEADER_PLONK), **parse(HEADER_POPEN), **parse(HEADER_PVERIFY)}
+                      **parse(HEADER_KZG_CELLS), **parse(HEADER_FR_SCAN), **parse(HEADER_PLONK), **parse(HEADER_POPEN), **parse(HEADER_PVERIFY),
+                      **parse(HEADER_POSEIDON)}
         except OSError:            # the package deployed without the repo's include/ directory: no table, nothing to check
             _TABLE = {}
     return _TABLE

@@ -1174,6 +1174,75 @@ class PlonkVerifier:
         return engine().plonk_batch_verify_weighted(self.tau_g2, *args, _words(weights), self.log_n, self.log_e, proof_inf=inf)[1]
 
 
+class Poseidon:
+    """Poseidon over Fr of width t = 2 .. 17 as circomlib deploys it (include/sylow_poseidon.h): x^5, 8 full rounds, R_P by width, the
+    parameters from the paper's Grain generator.  The parameter table stays on the device (`table`).  Values are [.., 4] words or Python
+    ints, any 256-bit value taken mod r; results are canonical words."""
+
+    def __init__(self, t: int):
+        if not 2 <= int(t) <= 17:
+            raise ValueError("Poseidon: t = 2 .. 17")
+        self.t = int(t)
+        self.table = engine().poseidon_table(self.t)
+
+    def hash(self, inputs, init=None) -> np.ndarray:
+        """hash of every row of t - 1 inputs, [n, t - 1, 4] words or n lists of ints: [n, 4].  init [n, 4]: circomlibjs's initState."""
+        a = _fr_nd(inputs, 2)
+        if a.shape[1] != self.t - 1:
+            raise ValueError(f"Poseidon({self.t}).hash: rows of {self.t - 1} inputs")
+        return engine().poseidon_hash(self.table, a, None if init is None else _words(init))
+
+    def permute(self, states) -> np.ndarray:
+        """the permutation of every state, [n, t, 4] words or n lists of t ints: [n, t, 4]"""
+        a = _fr_nd(states, 2)
+        if a.shape[1] != self.t:
+            raise ValueError(f"Poseidon({self.t}).permute: states of {self.t} elements")
+        return engine().poseidon_permute(self.table, a)
+
+
+class PoseidonMerkleTree:
+    """m binary Merkle trees of 2^depth leaves each, node = Poseidon hash([left, right]) (include/sylow_poseidon.h).  build keeps leaves
+    and nodes on the device; open gathers paths from them; root_of and verify walk paths and need no tree."""
+
+    def __init__(self, depth: int, hasher: "Poseidon | None" = None):
+        if not 1 <= int(depth) <= 28:
+            raise ValueError("PoseidonMerkleTree: depth 1 .. 28")
+        self.depth = int(depth)
+        self.hasher = hasher if hasher is not None else Poseidon(3)
+        if self.hasher.t != 3:
+            raise ValueError("PoseidonMerkleTree: the hasher of a binary tree is Poseidon(3)")
+        self.m, self._leaves, self._nodes, self.roots = 0, None, None, None
+
+    def build(self, leaves) -> np.ndarray:
+        """leaves [m, 2^depth, 4] words or m lists of ints (one tree: [2^depth, 4] or one list): the roots [m, 4]"""
+        a = _fr_arrays(leaves)
+        a = np.ascontiguousarray(a[None] if a.ndim == 2 else a)
+        if a.shape[1] != 1 << self.depth:
+            raise ValueError("PoseidonMerkleTree.build: 2^depth leaves per tree")
+        e = engine()
+        self.m = a.shape[0]
+        self._leaves = e.to_device(np.ascontiguousarray(a.transpose(0, 2, 1))) if self.m else None
+        self._nodes, droot = e.poseidon_merkle_build_device(self.hasher.table, self._leaves, self.depth, self.m)
+        self.roots = e.from_device_soa(droot)[:self.m]
+        return self.roots
+
+    def open(self, index, tree=None):
+        """(siblings [q, depth, 4], status [q]) of the leaves `index` of the trees `tree` (None: tree 0); status bit 0 = out of range"""
+        index = np.asarray(index, dtype=np.uint64).reshape(-1)
+        tree = np.zeros_like(index) if tree is None else np.asarray(tree, dtype=np.uint64).reshape(-1)
+        return engine().poseidon_merkle_open(self._leaves, self._nodes, self.depth, self.m, tree, index)
+
+    def root_of(self, leaf, index, siblings):
+        """(roots [q, 4], status [q]) of q paths: leaf [q, 4], index [q], siblings [q, depth, 4]"""
+        return engine().poseidon_merkle_root(self.hasher.table, _words(leaf), index, siblings)
+
+    def verify(self, leaf, index, siblings, roots=None) -> np.ndarray:
+        """ok [q] bool: path i leads to roots (one root [4] / [1, 4] for all, or [q, 4]; None: the root of tree 0 of the last build)"""
+        roots = self.roots[:1] if roots is None else _words(roots)
+        ok, _ = engine().poseidon_merkle_verify(self.hasher.table, _words(leaf), index, siblings, roots)
+        return ok.astype(bool)
+
+
 def _fr_nd(values, *ndims):
     """words [..., 4] from a uint64 array of words or from nested lists of Python ints with one of the given numbers of dimensions"""
     if isinstance(values, np.ndarray) and values.dtype == np.uint64:

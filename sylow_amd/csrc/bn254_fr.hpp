@@ -4,7 +4,8 @@
 // Fr sits next to the hot path, not on it (Lagrange coefficients and polynomial evaluation in
 // examples/threshold_signing.rs:64-70,146-155): the batch kernels are HBM-bound, so the operands stay canonical
 // and products use the same Barrett reduction as the canonical-domain Fp multiply (fp_mulmod_plain) with
-// r's constants.  An Fr value is carried in the 8-limb Fp container.
+// r's constants.  An Fr value is carried in the 8-limb Fp container.  (Poseidon, poseidon.hip, is the one unit that is bound by this
+// arithmetic and not by HBM; it uses it as it stands: DESIGN.md §4.23 names the internal forms left for later.)
 #pragma once
 #include "bn254_fp.hpp"
 

@@ -2019,3 +2019,113 @@ class Engine:
         out = self.empty((1,), np.int32)
         self._call("sylow_hip_flags_all", dflags.ptr, dflags.shape[0], out.ptr)
         return int(out.download()[0])
+
+    # ---- Poseidon over Fr (include/sylow_poseidon.h): the circomlib instance, t = 2 .. 17.  The parameter table of a width is kept ON THE
+    # DEVICE by the caller; Fr batches are [.., 4] on the host, any 256-bit words taken mod r ----
+    def poseidon_table(self, t: int) -> DeviceArray:
+        """The parameter table of width t (sylow_poseidon_prepare): the round constants, then M, an element as 4 consecutive words.  Built
+        once per width; the call synchronises the stream once."""
+        words = int(self.lib.sylow_poseidon_table_words(int(t)))
+        if not words:
+            raise _lib.SylowHipError(f"poseidon: t = {t} is outside 2 .. 17")
+        table = self.empty((words // 4, 4))
+        self._call("sylow_poseidon_prepare", int(t), table.ptr)
+        return table
+
+    @staticmethod
+    def _poseidon_rows(values, width=None):
+        a = np.ascontiguousarray(values, dtype=np.uint64)
+        assert a.ndim == 3 and a.shape[2] == 4 and (width is None or a.shape[1] == width), a.shape
+        return a
+
+    def _poseidon_up(self, a):
+        """[n, c, 4] -> device [c][4][n] (None for an empty batch)"""
+        return self.to_device(np.ascontiguousarray(a.transpose(1, 2, 0))) if a.shape[0] and a.shape[1] else None
+
+    def poseidon_permute(self, table: DeviceArray, states, route=-1, max_blocks=-1):
+        """The permutation of n states [n, t, 4] (sylow_poseidon_permute_batch): canonical words [n, t, 4].  route 0 / 1 pins the narrow /
+        the wide kernel and max_blocks >= 1 caps the blocks (sylow_poseidon_permute_batch_tuned); the words depend on neither."""
+        a = self._poseidon_rows(states)
+        n, t = a.shape[0], a.shape[1]
+        din, dout = self._poseidon_up(a), self.empty((t, 4, max(n, 1)))
+        if route < 0 and max_blocks < 0:
+            self._call("sylow_poseidon_permute_batch", table.ptr, t, self._ptr(din), n, dout.ptr)
+        else:
+            self._call("sylow_poseidon_permute_batch_tuned", table.ptr, t, self._ptr(din), n, int(route), int(max_blocks), dout.ptr)
+        return np.ascontiguousarray(dout.download()[:, :, :n].transpose(2, 0, 1))
+
+    def poseidon_hash(self, table: DeviceArray, inputs, init=None, route=-1, max_blocks=-1):
+        """hash(inputs_i) for n rows of k inputs [n, k, 4] under the table of t = k + 1 (sylow_poseidon_hash_batch): canonical words [n, 4].
+        init [n, 4]: circomlibjs's initState (None: zeros).  route and max_blocks as for poseidon_permute."""
+        a = self._poseidon_rows(inputs)
+        n, k = a.shape[0], a.shape[1]
+        din, dout = self._poseidon_up(a), self.empty((4, max(n, 1)))
+        dinit = None if init is None or not n else self.to_device_soa(_aos(init, 4), 4)
+        assert dinit is None or dinit.shape == (4, n), dinit.shape
+        if route < 0 and max_blocks < 0:
+            self._call("sylow_poseidon_hash_batch", table.ptr, k, self._ptr(din), self._ptr(dinit), n, dout.ptr)
+        else:
+            self._call("sylow_poseidon_hash_batch_tuned", table.ptr, k, self._ptr(din), self._ptr(dinit), n, int(route), int(max_blocks), dout.ptr)
+        return self.from_device_soa(dout)[:n]
+
+    def poseidon_merkle_build_device(self, table3: DeviceArray, dleaves: DeviceArray, depth: int, m: int, wide_max=-1, max_blocks=-1):
+        """m trees over device leaves [m][4][2^depth] (sylow_poseidon_merkle_build_batch): device (nodes [m][4][2^depth - 1], roots [4][m])."""
+        n = 1 << depth
+        dnodes, droot = self.empty((max(m, 1), 4, n - 1)), self.empty((4, max(m, 1)))
+        if wide_max < 0 and max_blocks < 0:
+            self._call("sylow_poseidon_merkle_build_batch", table3.ptr, self._ptr(dleaves), int(depth), m, dnodes.ptr, droot.ptr)
+        else:
+            self._call("sylow_poseidon_merkle_build_batch_tuned", table3.ptr, self._ptr(dleaves), int(depth), m, int(wide_max), int(max_blocks), dnodes.ptr, droot.ptr)
+        return dnodes, droot
+
+    def poseidon_merkle_build(self, table3: DeviceArray, leaves, wide_max=-1, max_blocks=-1):
+        """The nodes of m binary trees over leaves [m, n, 4], n = 2^depth >= 2, node = hash([left, right]): (nodes [m, n - 1, 4], levels 1 ..
+        depth one after another with the root last, roots [m, 4]).  wide_max pins the item count up to which a level runs on the wide
+        kernel (sylow_poseidon_merkle_build_batch_tuned); the words do not depend on it."""
+        a = self._poseidon_rows(leaves)
+        m, n = a.shape[0], a.shape[1]
+        depth = n.bit_length() - 1
+        assert n == 1 << depth and depth >= 1, n
+        dleaves = self.to_device(np.ascontiguousarray(a.transpose(0, 2, 1))) if m else None
+        dnodes, droot = self.poseidon_merkle_build_device(table3, dleaves, depth, m, wide_max, max_blocks)
+        return np.ascontiguousarray(dnodes.download()[:m].transpose(0, 2, 1)), self.from_device_soa(droot)[:m]
+
+    def poseidon_merkle_open(self, dleaves, dnodes, depth: int, m: int, tree, index):
+        """The siblings of q leaves of trees held on the device (sylow_poseidon_merkle_open_batch): (siblings [q, depth, 4], level 0 first,
+        status [q]: bit 0 = tree or index out of range, the row zeros)."""
+        tree, index = (np.ascontiguousarray(x, dtype=np.uint64).reshape(-1) for x in (tree, index))
+        q = tree.shape[0]
+        assert index.shape[0] == q
+        dt, di = (self.to_device(x) if q else None for x in (tree, index))
+        dsib, dst = self.empty((int(depth), 4, max(q, 1))), self.empty((max(q, 1),), np.uint8)
+        self._call("sylow_poseidon_merkle_open_batch", self._ptr(dleaves), self._ptr(dnodes), int(depth), m, self._ptr(dt), self._ptr(di), q, dsib.ptr, dst.ptr)
+        return np.ascontiguousarray(dsib.download()[:, :, :q].transpose(2, 0, 1)), dst.download()[:q]
+
+    def _poseidon_paths_up(self, leaf, index, siblings):
+        leaf, index = _aos(leaf, 4), np.ascontiguousarray(index, dtype=np.uint64).reshape(-1)
+        sib = self._poseidon_rows(siblings)
+        q, depth = leaf.shape[0], sib.shape[1]
+        assert index.shape[0] == q and sib.shape[0] == q
+        return q, depth, (self.to_device_soa(leaf, 4) if q else None), (self.to_device(index) if q else None), self._poseidon_up(sib)
+
+    def poseidon_merkle_root(self, table3: DeviceArray, leaf, index, siblings):
+        """The root each of q paths leads to (sylow_poseidon_merkle_root_batch): leaf [q, 4], index [q], siblings [q, depth, 4] ->
+        (roots [q, 4], status [q]); bit k of index set: the node is the right child at level k."""
+        q, depth, dl, di, ds = self._poseidon_paths_up(leaf, index, siblings)
+        dr, dst = self.empty((4, max(q, 1))), self.empty((max(q, 1),), np.uint8)
+        self._call("sylow_poseidon_merkle_root_batch", table3.ptr, self._ptr(dl), self._ptr(di), self._ptr(ds), depth, q, dr.ptr, dst.ptr)
+        return self.from_device_soa(dr)[:q], dst.download()[:q]
+
+    def poseidon_merkle_verify(self, table3: DeviceArray, leaf, index, siblings, roots, route=-1, max_blocks=-1):
+        """(ok [q], status [q]) for q paths against roots [1, 4] (one root for all) or [q, 4] (sylow_poseidon_merkle_verify_batch): ok_i = the
+        recomputed root equals the root mod r, and 0 wherever status is not 0."""
+        q, depth, dl, di, ds = self._poseidon_paths_up(leaf, index, siblings)
+        roots = _aos(roots, 4)
+        droots = self.to_device_soa(roots, 4)
+        dok, dst = self.empty((max(q, 1),), np.uint8), self.empty((max(q, 1),), np.uint8)
+        if route < 0 and max_blocks < 0:
+            self._call("sylow_poseidon_merkle_verify_batch", table3.ptr, self._ptr(dl), self._ptr(di), self._ptr(ds), depth, q, droots.ptr, roots.shape[0], dok.ptr, dst.ptr)
+        else:
+            self._call("sylow_poseidon_merkle_verify_batch_tuned", table3.ptr, self._ptr(dl), self._ptr(di), self._ptr(ds), depth, q, droots.ptr, roots.shape[0],
+                       int(route), int(max_blocks), dok.ptr, dst.ptr)
+        return dok.download()[:q], dst.download()[:q]
